@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- batched AFSK demodulation throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (sync search + symbol correlator + squelch + Hamming decode +
 byte pack: afsk_demod_batch_uniform for a one-rate batch, afsk_demod_batch for a mixed one) over one
@@ -30,10 +30,11 @@ rates, {value, frac, match_rate} per sub-record); the full record (per-rate tabl
 tens of KB) goes to gpurun_out/bench_full_n<N>.json, named in the line as `full_record`.  Nothing large goes to
 stderr either: the driver keeps one ~8 KB tail of both streams.
 
-Timing: a timed region is EXACTLY K steps between two fences (barrier + synchronize on both sides);
-when one region is shorter than --min-region-ms (50 ms) the K-step region is repeated and `value` /
-`ms_per_step` are those of the MEDIAN region (`timed_regions`, `timed_region_ms`).  HIP events inside the
-regions give the per-step median (`event_ms_per_step_median`) and the average launch duration of the
+Timing: a timed region is EXACTLY K steps between two fences (barrier + synchronize on both sides).
+The headline times ONE such region, so --steps is the number of timed steps and `ms_per_step` = region / K.
+For the sub-records, when one region is shorter than --min-region-ms (50 ms) the K-step region is repeated
+and `value` / `ms_per_step` are those of the MEDIAN region (`timed_regions`, `timed_region_ms`).  HIP events
+inside the regions give the per-step median (`event_ms_per_step_median`) and the average launch duration of the
 SAME median region, which the roofline uses (`roofline.kernel_ms`).
 
 Launching: `python bench.py --gpus N` with N > 1 from a bare interpreter starts N rank processes
@@ -45,6 +46,12 @@ The line carries `roofline` (HBM-read bound; algorithmic bytes / HIP-event kerne
 N = 1, `cpu_baseline` (the CPU oracle -- a C port of the reference -- timed on this box's host
 cores on a bounded sample, also the match-rate checker).  oracle/ is used as the checker only,
 after the timed regions.
+
+--dump-outputs DIR: after the headline's timed steps, the arrays a caller of the timed entry receives for the
+LAST timed step (rank 0's shard) go to DIR/<name>.npy -- bytes as float32, nbytes / nbits / clock_idx /
+term_frame / status as float64 (both exact) -- at most 64 MB in all: beyond that, a fixed seeded sample of
+streams (DIR/stream_index.npy).  The inputs are a pure function of the arguments, so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -392,14 +399,15 @@ def median(v):
 
 
 def measure(ctx: Ctx, sh: Shard, steps: int, warmup: int, preroll_ms: float, gather_every: int = 0,
-            min_region_ms: float = 50.0, max_regions: int = 64, with_gather: bool = True):
+            min_region_ms: float = 50.0, max_regions: int = 64, with_gather: bool = True, keep_last: bool = False):
     """Pre-roll, W warm-up steps, then timed regions of EXACTLY K steps between two fences each: one
     region, or -- when a region is shorter than min_region_ms -- as many as add up to it; the reported
     region is the median one.  Every step writes its own output slot; with a process group the slots
     of G consecutive steps are gathered by ONE collective on a side stream while the next group
     runs.  with_gather=False: the same regions (fences and the max over ranks included) without the
     exchange of the decoded records -- `value_no_gather`, so that weak-scaling efficiency and the cost of
-    the gather separate."""
+    the gather separate.  keep_last: aux["last"] holds the host copy of the last timed
+    step's outputs."""
     from afskmodem_amd import _native, batch
     torch, dist = ctx.torch, ctx.dist
     cur, comm = ctx.cur, (ctx.comm if with_gather else None)
@@ -628,6 +636,8 @@ def measure(ctx: Ctx, sh: Shard, steps: int, warmup: int, preroll_ms: float, gat
         "host_issue_ms_per_step": round(host_issue_s / max(steps, 1) * 1e3, 5),
     }
     aux = {"res": res, "got_payloads": got_payloads}
+    if keep_last and steps > 0:
+        aux["last"] = slots[(steps - 1) % nslots].cpu()
 
     if comm is not None:
         # Every rank's slice of the last gathered group, on every rank: (a) its checksum equals
@@ -677,6 +687,34 @@ def measure(ctx: Ctx, sh: Shard, steps: int, warmup: int, preroll_ms: float, gat
                                 "bytes_per_rank": int(G * flat_sz), "measured": len(gms)}
     del out_all, slots, gath_bufs
     return rec, aux
+
+
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 4242
+DUMP_FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
+
+
+def dump_outputs(d: str, res) -> dict:
+    """Write one step's outputs (a HostDemodResult) as DIR/<name>.npy: bytes [n, stride] as float32, the int32 arrays
+    as float64.  When all of it would pass DUMP_CAP_BYTES, a fixed seeded sample of streams (sorted; the same at every
+    run with the same arguments) is written instead, and its indices as DIR/stream_index.npy."""
+    n, stride = res.bytes.shape
+    per_stream = 4 * stride + 8 * len(DUMP_FIELDS)
+    idx = None
+    if n * per_stream > DUMP_CAP_BYTES - 8192:              # (8 KB: the .npy headers)
+        k = (DUMP_CAP_BYTES - 8192) // (per_stream + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+    pick = (lambda a: a) if idx is None else (lambda a: a[idx])
+    os.makedirs(d, exist_ok=True)
+    arrays = {"bytes": pick(res.bytes).astype(np.float32)}
+    for f in DUMP_FIELDS:
+        arrays[f] = pick(getattr(res, f)).astype(np.float64)
+    if idx is not None:
+        arrays["stream_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "files": sorted(arrays), "streams": n if idx is None else int(idx.size), "streams_total": n,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def oracle_match(sh: Shard, res, got_payloads, x_dev, ns: int, n_threads: int):
@@ -1006,13 +1044,14 @@ def _run_rank(args, hb: Heartbeat, dog: Watchdog) -> None:
     if ctx.comm is not None and not args.no_value_no_gather:
         # N > 1: the SAME K-step regions first without the exchange of the decoded records ...
         hb.beat("timing without the gather")
-        rec_ng, _ = measure(ctx, sh, args.steps, args.warmup, args.preroll_ms, args.gather_every, args.min_region_ms,
+        rec_ng, _ = measure(ctx, sh, args.steps, args.warmup, args.preroll_ms, args.gather_every, 0.0,
                             with_gather=False)
         hb.beat("timed without the gather")
     # ... then (the headline) with it: every step's records are exchanged inside the timed region
     hb.beat("warm-up + timed region")
+    # (min_region_ms 0: one region of exactly --steps steps)
     rec, aux = measure(ctx, sh, args.steps, args.warmup, args.preroll_ms if rec_ng is None else min(args.preroll_ms, 50.0),
-                       args.gather_every, args.min_region_ms)
+                       args.gather_every, 0.0, keep_last=bool(args.dump_outputs))
     hb.beat("timed" + (" and gathered" if ctx.comm is not None else ""))
     attach_traffic(rec, main_name, sh.n_local, src_hash)
     out = {
@@ -1049,6 +1088,8 @@ def _run_rank(args, hb: Heartbeat, dog: Watchdog) -> None:
         "host_threads_per_rank": cores,
     }
     out["config"]["bauds"] = list(sh.bauds)       # (--workload custom --bauds ... replaces the table entry)
+    if args.dump_outputs and rank == 0 and "last" in aux:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, aux.pop("last"))
     for k in ("ranks_seen", "gather_mode", "gather_check", "gather_check_on_every_rank", "gather_every_steps",
               "gathers_in_timed_region", "gather_ms"):
         if k in rec:
@@ -1219,7 +1260,8 @@ def main() -> None:
                          "giving one explicitly drops the sub-records unless --sub lists them")
     ap.add_argument("--sub", default=None, help="comma list of sub-records: workloads and/or f1_modulate,f2_gate,f3_wav_ingest,f5_wav_egress,rates_4096,rates_65536 ('' = none)")
     ap.add_argument("--min-region-ms", type=float, default=50.0,
-                    help="repeat the K-step timed region until the regions add up to this (0 = exactly one region)")
+                    help="sub-records: repeat the K-step timed region until the regions add up to this (0 = exactly one "
+                         "region); the headline always times one region of exactly --steps steps")
     ap.add_argument("--entry", default="auto", choices=["auto", "mixed"],
                     help="auto = one-rate shards use afsk_demod_batch_uniform, several rates afsk_demod_batch_grouped; "
                          "mixed = always the per-stream entry afsk_demod_batch (A/B)")
@@ -1261,6 +1303,8 @@ def main() -> None:
                          "had been measured -- and the exit code is non-zero.  0 = no limit")
     ap.add_argument("--pg-timeout-s", type=float, default=90.0,
                     help="torch.distributed process-group timeout: rendezvous and every collective")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0's shard) to DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--no-value-no-gather", action="store_true",
                     help="N > 1: skip the extra K-step regions without the gather (value_no_gather)")
     args = ap.parse_args()

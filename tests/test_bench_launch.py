@@ -402,3 +402,61 @@ def test_rider_rows_live_outside_bench_py_and_import_on_cpu():
     line = bench.compact_line(full, None)
     assert line["sub_records"]["f3_wav_ingest"] == {"error": full["sub_records"]["f3_wav_ingest"]["error"][:120]}
     assert line["value"] == full["value"] and len(json.dumps(line)) < bench.LINE_CAP
+
+
+def test_dump_outputs_writes_the_step_exactly_and_caps_at_64_mb(tmp_path):
+    """--dump-outputs: every output array of one step as <name>.npy (float32 / float64, exact); a step whose outputs
+    would pass 64 MB is written as a fixed seeded sample of streams, the same at every call."""
+    import numpy as np
+    import bench
+    from afskmodem_amd.batch import HostDemodResult
+    rng = np.random.default_rng(5)
+    for n, stride in ((4096, 88), (65536, 896)):
+        res = HostDemodResult(rng.integers(0, 256, (n, stride), dtype=np.uint8),
+                              *(rng.integers(-1, 48000, n).astype(np.int32) for _ in bench.DUMP_FIELDS))
+        dirs = [tmp_path / f"{n}_{k}" for k in range(2)]
+        infos = [bench.dump_outputs(str(d), res) for d in dirs]
+        assert infos[0]["files"] == infos[1]["files"] and infos[0]["streams"] == infos[1]["streams"]
+        assert sum(f.stat().st_size for f in dirs[0].iterdir()) <= 64 << 20
+        sampled = "stream_index" in infos[0]["files"]
+        assert sampled == (n == 65536)
+        idx = np.load(dirs[0] / "stream_index.npy").astype(np.int64) if sampled else np.arange(n)
+        assert sampled == (idx.size < n) and np.array_equal(idx, np.unique(idx))
+        b = np.load(dirs[0] / "bytes.npy")
+        assert b.dtype == np.float32 and np.array_equal(b, res.bytes[idx])
+        for f in bench.DUMP_FIELDS:
+            a = np.load(dirs[0] / f"{f}.npy")
+            assert a.dtype == np.float64 and np.array_equal(a, getattr(res, f)[idx]), f
+        for f in infos[0]["files"]:
+            assert np.array_equal(np.load(dirs[0] / f"{f}.npy"), np.load(dirs[1] / f"{f}.npy")), f
+
+
+def test_visible_gpus_skips_topology_nodes_it_may_not_read(monkeypatch):
+    """A container given one GPU of a machine sees every KFD topology node but may not read the others'
+    properties (EPERM): those are GPUs it cannot use, not an unreadable topology -- so `--gpus 2` is refused there."""
+    import glob
+    import io
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import bench_launch
+    nodes = {0: "simd_count 0\n", 1: PermissionError, 2: "simd_count 1024\ndrm_render_minor 144\n", 3: PermissionError}
+    path = "/sys/class/kfd/kfd/topology/nodes/%d/properties"
+
+    def fake_open(p, *a, **k):
+        v = nodes[int(p.split("/")[-2])]
+        if v is PermissionError:
+            raise PermissionError(1, "Operation not permitted", p)
+        return io.StringIO(v)
+
+    monkeypatch.setattr(os.path, "isdir", lambda p: p == "/sys/class/kfd")
+    monkeypatch.setattr(glob, "glob", lambda pat: [path % i for i in nodes])
+    monkeypatch.setattr(bench_launch, "open", fake_open, raising=False)
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.delenv(var, raising=False)
+    assert bench_launch.visible_gpus() == 1
+    nodes[3] = "simd_count 1024\n"
+    assert bench_launch.visible_gpus() == 2
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "0")
+    assert bench_launch.visible_gpus() == 1
+    for i in nodes:
+        nodes[i] = PermissionError
+    assert bench_launch.visible_gpus() is None

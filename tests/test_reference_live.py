@@ -1,16 +1,21 @@
-"""Live cross-check against the UNMODIFIED reference, in the one place it exists: the build container
-(/root/reference; the GPU boxes do not have it, so this module is CPU-only and skips itself there).
-The committed fixture (tests/golden/reference_vectors.json) pins fixed cases; here the imported
-reference itself runs next to the CPU oracle and the product's host-side mirror on randomised inputs
-that are not in the fixture -- framing (ref:452-469 + the .wav quirk :239-244), ECC (:132-175), the
-primitives (:94-107, :287-296), the sync search (:322-339) and whole decodes (:354-381, :420-427)."""
+"""Cross-check against the UNMODIFIED reference on randomised inputs that are not in the main fixture.
+The inputs are drawn here from a fixed seed; what the reference answered for each of them was recorded by
+running it (tests/golden/make_live_vectors.py) into tests/golden/reference_live_vectors.json, so this module
+needs nothing outside the repository.  The recorded fixture also holds every input (or its SHA-256), and each
+test checks that it regenerates exactly those inputs before comparing.  The CPU oracle and the product's
+host-side mirror are held against the reference's answers on framing (ref:452-469 + the .wav quirk :239-244),
+ECC (:132-175), the primitives (:94-107, :287-296), the sync search (:322-339) and whole decodes
+(:354-381, :420-427).
+
+Each section is a pair: `<section>_cases(seed)` draws the inputs, `<section>_reference(ref, case)` asks the
+imported reference about one of them (used only by the recorder)."""
 from __future__ import annotations
 
 import contextlib
+import hashlib
 import io
+import json
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -18,151 +23,202 @@ import pytest
 import afskmodem_amd as product
 from oracle import afsk_oracle as O
 
-REF_FILE = "/root/reference/afskmodem.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_FILE), reason="the reference only exists in the build container")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_live_vectors.json")
+SEED = 20261007
+SECTIONS = ("framing", "ecc", "primitives", "decodes", "degenerate")
 
 
-@pytest.fixture(scope="module")
-def ref():
-    """import afskmodem from /root/reference in place, with a stub `pyaudio` (its only missing
-    dependency: audio-device I/O, off the hot path) -- nothing of it is copied."""
-    saved = sys.modules.get("pyaudio")
-    stub = types.ModuleType("pyaudio")
-    stub.paInt16 = 8
+def fp(v):
+    """JSON form of a value: bytes -> hex; arrays / lists of more than 64 elements -> length + SHA-256 of their
+    int64 (or float64) bytes, shorter ones -> a list; anything else unchanged."""
+    if isinstance(v, (bytes, bytearray)):
+        return {"hex": bytes(v).hex()}
+    if isinstance(v, (list, tuple, np.ndarray)):
+        a = np.asarray(v)
+        a = a.astype(np.int64) if a.dtype.kind in "biu" or a.size == 0 else a.astype(np.float64)
+        if a.size <= 64:
+            return a.tolist()
+        return {"n": int(a.size), "sha256": hashlib.sha256(a.tobytes()).hexdigest()}
+    return v
 
-    class _Stream:
-        def start_stream(self): pass
-        def stop_stream(self): pass
-        def close(self): pass
-        def read(self, n): return b"\x00" * (2 * n)
-        def write(self, *a, **k): pass
 
-    class _PA:
-        def open(self, **kw): return _Stream()
-
-    stub.Stream, stub.PyAudio = _Stream, _PA
-    sys.modules["pyaudio"] = stub
-    sys.path.insert(0, os.path.dirname(REF_FILE))
-    no_bytecode = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True          # /root/reference is read-only for us: no __pycache__ there
+def outcome(fn):
     try:
-        import afskmodem as mod  # type: ignore
-    finally:
-        sys.dont_write_bytecode = no_bytecode
-        sys.path.remove(os.path.dirname(REF_FILE))
-    mod.LOG_LEVEL = 5
-    yield mod
-    sys.modules.pop("afskmodem", None)
-    if saved is None:
-        sys.modules.pop("pyaudio", None)
-    else:
-        sys.modules["pyaudio"] = saved
+        return fp(fn())
+    except BaseException as e:  # noqa: BLE001
+        return f"raises {type(e).__name__}: {e}"
 
 
-def _seed() -> int:
-    """Fixed by default so that a red run can be repeated; AFSK_LIVE_SEED=random draws a fresh one (25
-    such runs were green when this file was added), AFSK_LIVE_SEED=<int> picks one."""
-    v = os.environ.get("AFSK_LIVE_SEED", "20261007")
-    return int.from_bytes(os.urandom(4), "little") if v == "random" else int(v)
-
-
-def _ref_decode(ref, frames, baud, amp_end=14000):
-    r = ref.Receiver(baud, 18000, amp_end)
-    with contextlib.redirect_stdout(io.StringIO()):
-        bits = r._Receiver__decodeBits([int(v) for v in frames])
-        data = b"" if bits == "" else r._Receiver__bitsToBytes(ref.ECC.decode(bits))
-    return bits, data
-
-
-def test_framing_matches_the_live_reference(ref):
-    rng = np.random.default_rng(_seed())
+# ----------------------------------------------------------------------------------------------- the sections
+def framing_cases(seed):
+    rng = np.random.default_rng(seed)
+    cases = []
     for baud in (1200, 300, 2400, 600, 4000, 480, 160, 12000, 24):
         for tt in (0.5, 0.1, 0.0):
             data = rng.integers(0, 256, int(rng.integers(0, 12)), dtype=np.uint8).tobytes()
-            want = np.asarray(ref.Transmitter(baud, tt)._Transmitter__getFrames(data), np.int64)
-            got_o = O.get_frames(data, baud, tt)
-            got_p = product.Transmitter(baud, tt).frames(data)
-            assert np.array_equal(got_o, want), ("oracle", baud, tt, data.hex())
-            assert np.array_equal(got_p, want), ("product", baud, tt, data.hex())
-            wav = np.frombuffer(ref.SoundOutput._SoundOutput__convertFrames([int(v) for v in want]), "<i2")
-            assert np.array_equal(O.wav_convert(got_o), wav), (baud, tt)
+            cases.append({"baud": baud, "tt": tt, "data": data})
+    return cases
 
 
-def test_ecc_matches_the_live_reference(ref):
-    rng = np.random.default_rng(_seed())
-    for _ in range(200):
-        bits = "".join(rng.choice(["0", "1"], int(rng.integers(0, 90))))
-        assert O.ecc_encode(bits) == ref.ECC.encode(bits) == product.ECC.encode(bits), bits
-        assert O.ecc_decode(bits) == ref.ECC.decode(bits) == product.ECC.decode(bits), bits
+def framing_reference(ref, c):
+    want = ref.Transmitter(c["baud"], c["tt"])._Transmitter__getFrames(c["data"])
+    wav = np.frombuffer(ref.SoundOutput._SoundOutput__convertFrames([int(v) for v in want]), "<i2")
+    return {"frames": fp(want), "wav": fp(wav)}
 
 
-def test_primitives_match_the_live_reference(ref):
-    rng = np.random.default_rng(_seed())
+def ecc_cases(seed):
+    rng = np.random.default_rng(seed)
+    return [{"bits": "".join(rng.choice(["0", "1"], int(rng.integers(0, 90))))} for _ in range(200)]
+
+
+def ecc_reference(ref, c):
+    return {"encode": ref.ECC.encode(c["bits"]), "decode": ref.ECC.decode(c["bits"])}
+
+
+def primitives_cases(seed):
+    rng = np.random.default_rng(seed)
     edge = np.array([-32768, -32767, -513, -512, -511, -1, 0, 1, 511, 512, 513, 32766, 32767], np.int16)
-    r = ref.Receiver(1200)
+    cases = []
     for n in (4, 20, 40, 160, 2048):
         for _ in range(20):
             a = rng.choice(edge, n) if rng.random() < 0.5 else rng.integers(-32768, 32768, n).astype(np.int16)
             b = rng.integers(-32768, 32768, n).astype(np.int16)
-            la, lb = [int(v) for v in a], [int(v) for v in b]
-            assert O.get_amplitude(a) == ref.Waveforms.getAmplitude(la)
-            assert O.get_diff(a, b) == ref.Waveforms.getDiff(la, lb)
-            assert O.amplify(a).tolist() == r._Receiver__amplify(la)
+            cases.append({"a": a, "b": b})
+    return cases
 
 
-def test_decodes_match_the_live_reference(ref):
-    """Whole decodes on inputs drawn fresh every run: clean bursts with a random lead, noisy bursts,
-    garbage -- bits, bytes and the clock index against the reference's own __decodeBits."""
-    seed = _seed()
+def primitives_reference(ref, c):
+    la, lb = [int(v) for v in c["a"]], [int(v) for v in c["b"]]
+    return {"amplitude": ref.Waveforms.getAmplitude(la), "diff": ref.Waveforms.getDiff(la, lb),
+            "amplify": fp(ref.Receiver(1200)._Receiver__amplify(la))}
+
+
+def decodes_cases(seed):
+    """Clean bursts with a random lead, noisy bursts, garbage."""
     rng = np.random.default_rng(seed)
+    cases = []
     for baud in (1200, 2400, 300, 800, 6000, 375):
         bf = 48000 // baud
         data = rng.integers(0, 256, int(rng.integers(1, 6)), dtype=np.uint8).tobytes()
         tt = max(0.1, 8.0 / baud)
         w = O.wav_convert(O.get_frames(data, baud, tt))
         lead = int(rng.integers(0, 3 * bf))
-        cases = [
+        xs = [
             ("clean+lead", np.concatenate([np.zeros(lead, np.int16), w])),
             ("noisy", O.add_noise(w, seed & 0xFFFF, 1, int(rng.integers(1 << 19, 1 << 22)))),
             ("garbage", O.add_noise(np.zeros(5000 + 6 * bf, np.int16), seed & 0xFFFF, 2, 1 << 22)),
         ]
-        for tag, x in cases:
+        for tag, x in xs:
             amp_end = int(rng.choice([14000, 14000, 9000, 20000]))
-            bits, want = _ref_decode(ref, x, baud, amp_end)
-            got_bits, ci, tf = O.decode_bits(x, baud, amp_end)
-            assert got_bits == bits, (tag, baud, seed)
-            assert O.load_frames(x, baud, amp_end) == want, (tag, baud, seed)
-            rci = ref.Receiver(baud)._Receiver__recoverClockIndex([int(v) for v in x])
-            assert O.recover_clock_index(x, baud) == rci == ci, (tag, baud, seed)
+            cases.append({"tag": tag, "baud": baud, "amp_end": amp_end, "x": x})
+    return cases
 
 
-def test_degenerate_constructor_arguments_match_the_live_reference(ref):
-    """Negative rates and negative training times, drawn fresh every run: construction, templates and the
-    Transmitter's frames of the host mirror against the imported reference (outcome by outcome: the same
-    value or the same exception text) -- the committed fixture holds a fixed list (`degenerate_api`)."""
-    seed = _seed()
+def decodes_reference(ref, c):
+    """Bits, bytes and the clock index from the reference's own __decodeBits / __recoverClockIndex."""
+    frames = [int(v) for v in c["x"]]
+    r = ref.Receiver(c["baud"], 18000, c["amp_end"])
+    with contextlib.redirect_stdout(io.StringIO()):
+        bits = r._Receiver__decodeBits(frames)
+        data = b"" if bits == "" else r._Receiver__bitsToBytes(ref.ECC.decode(bits))
+    rci = ref.Receiver(c["baud"])._Receiver__recoverClockIndex(frames)
+    return {"bits": bits, "data": fp(data), "clock_idx": rci}
+
+
+def degenerate_cases(seed):
+    """Negative rates and negative training times."""
     rng = np.random.default_rng(seed)
-
-    def outcome(fn):
-        try:
-            return fn()
-        except BaseException as e:  # noqa: BLE001
-            return f"raises {type(e).__name__}: {e}"
-
     divisors = [d for d in range(1, 48001) if 48000 % d == 0]
     bauds = [-int(rng.choice(divisors)) for _ in range(12)] + [-int(rng.integers(1, 100000)) for _ in range(6)] + [0]
-    for baud in bauds:
-        for name in ("getSpaceTone", "getMarkTone", "getTrainingCycle"):
-            assert outcome(lambda: getattr(product.Waveforms, name)(baud)) == \
-                   outcome(lambda: getattr(ref.Waveforms, name)(baud)), (name, baud, seed)
-        assert outcome(lambda: bool(product.Receiver(baud))) == outcome(lambda: bool(ref.Receiver(baud))), (baud, seed)
-        want = outcome(lambda: ref.Transmitter(baud)._Transmitter__getFrames(b"xy"))
-        got = outcome(lambda: product.Transmitter(baud).frames(b"xy").tolist())
-        assert got == want, (baud, seed)
+    cases = [{"baud": b} for b in bauds]
     for _ in range(8):
         baud = int(rng.choice([300, 1200, 2400, 6000]))
         tt = -float(rng.random() * rng.choice([0.001, 1.0, 50.0]))
         data = rng.integers(0, 256, 3, dtype=np.uint8).tobytes()
-        rt, pt = ref.Transmitter(baud, tt), product.Transmitter(baud, tt)
-        assert pt.ts_cycles == rt._Transmitter__ts_cycles, (baud, tt, seed)
-        assert pt.frames(data).tolist() == rt._Transmitter__getFrames(data), (baud, tt, seed)
+        cases.append({"baud": baud, "tt": tt, "data": data})
+    return cases
+
+
+def _degenerate_ask(mod, c, frames_of):
+    """Outcome by outcome (the same value or the same exception text) of one module: the reference or the mirror."""
+    baud = c["baud"]
+    if "tt" in c:
+        t = mod.Transmitter(baud, c["tt"])
+        return {"ts_cycles": outcome(lambda: frames_of(t, None)), "frames": outcome(lambda: frames_of(t, c["data"]))}
+    got = {name: outcome(lambda: getattr(mod.Waveforms, name)(baud))
+           for name in ("getSpaceTone", "getMarkTone", "getTrainingCycle")}
+    got["receiver"] = outcome(lambda: bool(mod.Receiver(baud)))
+    got["frames"] = outcome(lambda: frames_of(mod.Transmitter(baud), b"xy"))
+    return got
+
+
+def degenerate_reference(ref, c):
+    return _degenerate_ask(ref, c, lambda t, d: t._Transmitter__ts_cycles if d is None else t._Transmitter__getFrames(d))
+
+
+def case_key(c) -> dict:
+    return {k: fp(v) for k, v in c.items()}
+
+
+# ----------------------------------------------------------------------------------------------- the tests
+@pytest.fixture(scope="module")
+def recorded():
+    with open(FIXTURE) as f:
+        doc = json.load(f)
+    assert doc["seed"] == SEED and sorted(doc["sections"]) == sorted(SECTIONS)
+    return doc
+
+
+def _pairs(recorded, section):
+    """(case, the reference's recorded answer) for every input this module draws in `section`."""
+    cases = globals()[f"{section}_cases"](recorded["seed"])
+    rec = recorded["sections"][section]
+    assert len(cases) == len(rec), section
+    for i, (c, r) in enumerate(zip(cases, rec)):
+        assert case_key(c) == r["case"], (section, i, "the inputs drawn here are not the recorded ones")
+        yield c, r["ref"]
+
+
+def test_framing_matches_the_live_reference(recorded):
+    for c, want in _pairs(recorded, "framing"):
+        baud, tt, data = c["baud"], c["tt"], c["data"]
+        got_o = O.get_frames(data, baud, tt)
+        got_p = product.Transmitter(baud, tt).frames(data)
+        assert fp(got_o) == want["frames"], ("oracle", baud, tt, data.hex())
+        assert fp(got_p) == want["frames"], ("product", baud, tt, data.hex())
+        assert fp(O.wav_convert(got_o)) == want["wav"], (baud, tt)
+
+
+def test_ecc_matches_the_live_reference(recorded):
+    for c, want in _pairs(recorded, "ecc"):
+        bits = c["bits"]
+        assert O.ecc_encode(bits) == want["encode"] == product.ECC.encode(bits), bits
+        assert O.ecc_decode(bits) == want["decode"] == product.ECC.decode(bits), bits
+
+
+def test_primitives_match_the_live_reference(recorded):
+    for c, want in _pairs(recorded, "primitives"):
+        a, b = c["a"], c["b"]
+        assert O.get_amplitude(a) == want["amplitude"]
+        assert O.get_diff(a, b) == want["diff"]
+        assert fp(O.amplify(a).tolist()) == want["amplify"]
+
+
+def test_decodes_match_the_live_reference(recorded):
+    """Whole decodes: bits, bytes and the clock index against the reference's own __decodeBits."""
+    for c, want in _pairs(recorded, "decodes"):
+        x, baud, amp_end, tag = c["x"], c["baud"], c["amp_end"], c["tag"]
+        got_bits, ci, tf = O.decode_bits(x, baud, amp_end)
+        assert got_bits == want["bits"], (tag, baud)
+        assert fp(O.load_frames(x, baud, amp_end)) == want["data"], (tag, baud)
+        assert O.recover_clock_index(x, baud) == want["clock_idx"] == ci, (tag, baud)
+
+
+def test_degenerate_constructor_arguments_match_the_live_reference(recorded):
+    """Negative rates and negative training times: construction, templates and the Transmitter's frames of the
+    host mirror against the reference (outcome by outcome: the same value or the same exception text) -- the
+    main fixture holds a fixed list (`degenerate_api`)."""
+    for c, want in _pairs(recorded, "degenerate"):
+        got = _degenerate_ask(product, c, lambda t, d: t.ts_cycles if d is None else t.frames(d).tolist())
+        assert got == want, c

@@ -69,22 +69,30 @@ def free_port() -> int:
 def visible_gpus() -> int | None:
     """GPUs this process could use, counted WITHOUT touching HIP or importing torch: the KFD topology in sysfs
     (a node with simd_count > 0 is a GPU), narrowed by a HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES list.
-    None when the topology cannot be read (the launcher then lets the ranks fail loudly themselves)."""
+    A node whose properties this process may not read (a container given only some of the machine's GPUs)
+    is not one it can use.  None when no node can be read (the launcher then lets the ranks fail loudly
+    themselves)."""
     import glob
     if not os.path.isdir("/sys/class/kfd"):
         return 0                                   # no KFD driver: no AMD GPU in this machine / container
     paths = glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")
-    if not paths:
-        return None
-    n = 0
+    n, readable = 0, 0
     for p in paths:
         try:
-            for ln in open(p):
+            with open(p) as f:
+                lines = f.readlines()
+        except OSError:
+            continue
+        readable += 1
+        try:
+            for ln in lines:
                 k, _, v = ln.partition(" ")
                 if k == "simd_count" and int(v) > 0:
                     n += 1
-        except (OSError, ValueError):
+        except ValueError:
             return None
+    if not readable:
+        return None
     for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         lst = os.environ.get(var)
         if lst is not None:
