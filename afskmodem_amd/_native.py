@@ -91,6 +91,19 @@ SIGNATURES = {
 }
 
 
+# The sequence-parallel entries (afsk_split_plan_* / afsk_demod_batch_split), bound by lib() like SIGNATURES but kept
+# in a table of their own: SIGNATURES is also resolved against builds that do not contain them.
+SPLIT_SIGNATURES = {
+    "afsk_split_plan_create": (C.c_int, [_i32p, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "afsk_split_plan_info": (C.c_int, [C.c_void_p, _i32p, _i32p, _i64p]),
+    "afsk_split_plan_destroy": (C.c_int, [C.c_void_p]),
+    "afsk_split_scratch_bytes": (C.c_int, [_i32p, _i32p, C.c_int32, C.c_int32, _i64p, _i32p]),
+    "afsk_demod_batch_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+}
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -100,7 +113,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with afskmodem_amd/csrc/build.sh "
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

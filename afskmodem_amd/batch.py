@@ -400,13 +400,16 @@ def _drain_parked_plans() -> None:
         return
     with _PARKED_LOCK:
         todo, _PARKED_PLANS[:] = list(_PARKED_PLANS), []
-    for h, dev in todo:
+    for h, dev, *kind in todo:
         try:
             torch.cuda.synchronize(dev)
-            _native.lib().afsk_group_plan_destroy(h)
+            if kind:
+                _native.lib().afsk_split_plan_destroy(h)
+            else:
+                _native.lib().afsk_group_plan_destroy(h)
         except Exception:  # noqa: BLE001
             with _PARKED_LOCK:
-                _PARKED_PLANS.append((h, dev))
+                _PARKED_PLANS.append((h, dev, *kind))
 
 
 def release_parked_plans() -> int:
@@ -539,6 +542,162 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
                 out.status.data_ptr(), _stream_ptr(stream, dev)))
     # keep the bit_frames tensor alive until the launch has been enqueued on the stream
     out._bf_keepalive = bf  # type: ignore[attr-defined]
+    return out
+
+
+def _split_host_arrays(stream_len_host, bit_frames, segment_symbols):
+    """The host-side arguments of a split plan as contiguous int32 arrays, checked before any device is touched."""
+    lens = np.ascontiguousarray(np.asarray(stream_len_host, dtype=np.int64).reshape(-1))
+    n = int(lens.size)
+    if n and (int(lens.min()) < 0 or int(lens.max()) > _native.MAX_STREAM_LEN):
+        raise ValueError(f"stream lengths must lie in 0 ... {_native.MAX_STREAM_LEN}")
+    bf = np.asarray(bit_frames)
+    if bf.size not in (1, n) and not (n == 0 and bf.size == 0):
+        raise ValueError(f"bit_frames holds {bf.size} values for {n} streams (1 or {n} expected)")
+    bf = np.ascontiguousarray(np.broadcast_to(bf.reshape(-1) if bf.ndim else bf, (n,)).astype(np.int32))
+    if n:
+        validate_bit_frames(bf)
+    segment_symbols = int(segment_symbols)
+    if segment_symbols < 0 or segment_symbols % 64:
+        raise ValueError("segment_symbols must be a multiple of 64 (0 = the default)")
+    return lens.astype(np.int32), bf, segment_symbols
+
+
+def split_scratch_bytes(stream_len_host, bit_frames, segment_symbols: int = 0) -> tuple[int, int]:
+    """(scratch bytes, segments) a ``SplitPlan`` for these host-side lengths would need (``afsk_split_scratch_bytes``:
+    host-only, no device)."""
+    lens, bf, seg = _split_host_arrays(stream_len_host, bit_frames, segment_symbols)
+    i32 = C.POINTER(C.c_int32)
+    nbytes, nseg = C.c_int64(), C.c_int32()
+    _native.check(_native.lib().afsk_split_scratch_bytes(lens.ctypes.data_as(i32), bf.ctypes.data_as(i32), int(lens.size),
+                                                         seg, C.byref(nbytes), C.byref(nseg)))
+    return int(nbytes.value), int(nseg.value)
+
+
+class SplitPlan:
+    """Sequence-parallel plan (``afsk_split_plan_create``) for a batch of few, long streams: every stream is cut into
+    segments of ``segment_symbols`` symbols (a multiple of 64; 0 = the default) that separate wavefronts demodulate, so
+    that one long recording fills the device.  ``stream_len_host`` / ``bit_frames``: the HOST-side lengths and rates
+    (an int or one value per stream; rates may be mixed).  Owns the plan's segment table and the scratch tensor a launch
+    needs; same lifetime and close rules as ``GroupPlan`` (it belongs to the device that was current when it was built;
+    ``close()`` only after the launches that use it have completed).  Decode with ``demod_batch_split``."""
+
+    def __init__(self, stream_len_host, bit_frames, device=None, segment_symbols: int = 0):
+        torch = _torch()
+        lens, bf, seg = _split_host_arrays(stream_len_host, bit_frames, segment_symbols)
+        _native.require_device()
+        _drain_parked_plans()
+        self.stream_len = lens
+        self.bit_frames = bf
+        self.n = int(lens.size)
+        self.segment_symbols = seg
+        self.device = _default_device(device)
+        self._h = C.c_void_p()
+        i32 = C.POINTER(C.c_int32)
+        lib = _native.lib()
+        with torch.cuda.device(self.device):
+            _native.check(lib.afsk_split_plan_create(lens.ctypes.data_as(i32), bf.ctypes.data_as(i32), self.n, seg,
+                                                     C.byref(self._h)))
+            nseg, nbytes = C.c_int32(), C.c_int64()
+            _native.check(lib.afsk_split_plan_info(self._h, None, C.byref(nseg), C.byref(nbytes)))
+            self.n_segments = int(nseg.value)
+            self.scratch_bytes = int(nbytes.value)
+            self.scratch = torch.empty(max(self.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("the plan has been closed")
+        return self._h
+
+    def close(self) -> None:
+        """Free the plan (after the launches that use it have completed)."""
+        if self._h:
+            _native.lib().afsk_split_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        # as GroupPlan.__del__: launches may still be queued, so free behind a device synchronise, or park the handle
+        h = getattr(self, "_h", None)
+        if not h:
+            return
+        self._h = None
+        try:
+            torch = _torch()
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capturing")
+            torch.cuda.synchronize(self.device)
+            _native.lib().afsk_split_plan_destroy(h)
+        except Exception:  # noqa: BLE001
+            try:
+                with _PARKED_LOCK:
+                    _PARKED_PLANS.append((h, self.device, "split"))
+            except Exception:  # noqa: BLE001
+                pass
+
+
+def demod_batch_split(samples, stream_offset, stream_len, plan: SplitPlan, amp_end_threshold: int = 14000,
+                      out: DemodResult | None = None, out_stride: int | None = None, stream=None,
+                      diagnostics: bool = False, margin_stride: int | None = None) -> DemodResult:
+    """``demod_batch`` through the sequence-parallel path (``afsk_demod_batch_split``): the same outputs, bit for bit,
+    for a batch of few, long streams that one wavefront per stream cannot spread over the device.  ``plan`` is a
+    ``SplitPlan`` built from this batch's host-side lengths (a device ``stream_len`` above them gives that stream
+    status ``ST_BAD_LENGTH``) and rates.  Other arguments as ``demod_batch``; asynchronous on ``stream``.  One launch
+    at a time per plan: the plan's scratch is reused."""
+    torch = _torch()
+    if not isinstance(plan, SplitPlan):
+        raise TypeError("plan must be a SplitPlan")
+    if not (isinstance(samples, torch.Tensor) and samples.dtype == torch.int16):
+        raise TypeError("samples must be an int16 CUDA tensor (HBM resident)")
+    if not (isinstance(stream_offset, torch.Tensor) and isinstance(stream_len, torch.Tensor)):
+        raise TypeError("stream_offset / stream_len must be CUDA tensors")
+    if stream_offset.dtype != torch.int64 or stream_len.dtype != torch.int32:
+        raise TypeError("stream_offset must be int64 and stream_len int32")
+    n = int(stream_offset.numel())
+    if plan.n != n or int(stream_len.numel()) != n:
+        raise ValueError(f"the plan covers {plan.n} streams, the batch {n}")
+    if out is None and out_stride is None:
+        raise ValueError("pass out= or out_stride=")
+    if diagnostics and (out is None or out.margins is None) and margin_stride is None:
+        raise ValueError("diagnostics=True needs margin_stride= (symbols per margins row)")
+    _native.require_device()
+    if not samples.is_cuda:
+        raise TypeError("samples must be an int16 CUDA tensor (HBM resident)")
+    if not samples.is_contiguous():
+        raise ValueError("samples must be contiguous")
+    if not (stream_offset.is_cuda and stream_len.is_cuda):
+        raise TypeError("stream_offset / stream_len must be CUDA tensors")
+    dev = samples.device
+    _same_device(dev, stream_offset=stream_offset, stream_len=stream_len)
+    if not (stream_offset.is_contiguous() and stream_len.is_contiguous()):
+        raise ValueError("stream_offset / stream_len must be contiguous (the kernel reads them as plain arrays)")
+    if plan.device != dev:
+        raise ValueError(f"the plan was built on {plan.device}, the batch lives on {dev}")
+    fresh = False
+    if out is None:
+        out = alloc_result(n, int(out_stride), dev)
+        fresh = True
+    stride = int(out.bytes.shape[1])
+    corrected_ptr = margins_ptr = None
+    mstride = 0
+    if diagnostics:
+        if out.corrected is None:
+            out.corrected = torch.zeros(n, dtype=torch.int32, device=dev)
+            fresh = True
+        if out.margins is None:
+            out.margins = torch.zeros((n, int(margin_stride)), dtype=torch.int32, device=dev)
+            fresh = True
+        corrected_ptr, margins_ptr, mstride = out.corrected.data_ptr(), out.margins.data_ptr(), int(out.margins.shape[1])
+    _same_device(dev, out_bytes=out.bytes, out_nbytes=out.nbytes, out_status=out.status)
+    with torch.cuda.device(dev):
+        if fresh:
+            _order_after_current(stream, dev)
+        _native.check(_native.lib().afsk_demod_batch_split(
+            plan.handle, samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(),
+            threshold_lt(amp_end_threshold), plan.scratch.data_ptr(), out.bytes.data_ptr(), stride,
+            out.nbytes.data_ptr(), out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
+            out.status.data_ptr(), corrected_ptr, margins_ptr, mstride, _stream_ptr(stream, dev)))
+    out._plan_keepalive = plan  # type: ignore[attr-defined]   (the plan's segment table outlives the launch)
     return out
 
 

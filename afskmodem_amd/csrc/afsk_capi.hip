@@ -754,6 +754,13 @@ int no_throw(F&& body) {
 
 }  // namespace
 
+namespace afsk {
+// the last-error slot of this library for entries implemented in other translation units (afsk_split.hip)
+int capi_fail(int code, const char* msg) { return fail(code, msg); }
+int capi_hip_fail(hipError_t e, const char* what) { return hip_fail(e, what); }
+int capi_require_device() { return require_device(); }
+}  // namespace afsk
+
 extern "C" {
 
 int afsk_version(void) { return AFSK_ABI_VERSION; }

@@ -378,21 +378,32 @@ class Receiver:
         return self.__finish(np.asarray(frames, dtype=np.int16), string)
 
     # -- batched forms (device-resident; see afskmodem_amd.batch)
-    def decode_batch(self, streams, string: bool = False):
-        """Decode many in-memory streams (list of int16 arrays, ragged allowed) in one launch."""
+    def decode_batch(self, streams, string: bool = False, split: bool = False):
+        """Decode many in-memory streams (list of int16 arrays, ragged allowed) in one launch.
+        ``split=True``: through the sequence-parallel path (``batch.SplitPlan`` / ``batch.demod_batch_split``), which
+        spreads each stream over many wavefronts -- for a few long streams; same results."""
         from . import batch
         arrays = [np.ascontiguousarray(s, dtype=np.int16) for s in streams]
         for a in arrays:
             self.check_decodable(len(a))
-        res = batch.demod_host_arrays(arrays, self.__bit_frames, self.__amp_end_threshold)
+        if split:
+            import torch
+            if not arrays:
+                return []
+            samples, off, ln, max_len = batch.upload_streams(arrays)
+            res = self.__demod_split(samples, off, ln, max_len)
+            torch.cuda.synchronize()
+        else:
+            res = batch.demod_host_arrays(arrays, self.__bit_frames, self.__amp_end_threshold)
         out = []
         for data in res.payloads():
             out.append(data.decode("utf-8") if (string and data != b"") else data)
         return out
 
-    def load_batch(self, filenames, string: bool = False):
+    def load_batch(self, filenames, string: bool = False, split: bool = False):
         """``load`` for many files: parallel .wav ingest into one device buffer
-        (``batch.load_wav_batch``), one demodulation launch."""
+        (``batch.load_wav_batch``), one demodulation launch.  ``split=True``: the sequence-parallel path
+        (``batch.demod_batch_split``) -- for a few long recordings; same results."""
         import torch
         from . import batch
         names = list(filenames)
@@ -400,12 +411,21 @@ class Receiver:
             return []
         samples, off, ln, max_len = batch.load_wav_batch(names)
         self.check_decodable(max_len)
-        stride = batch.out_stride_for(max_len, self.__bit_frames)
-        # (files of different lengths: the host-side lengths let the launch take the longest streams first)
-        res = batch.demod_batch(samples, off, ln, self.__bit_frames, self.__amp_end_threshold,
-                                out_stride=stride, stream_len_host=ln.cpu().numpy())
+        if split:
+            res = self.__demod_split(samples, off, ln, max_len)
+        else:
+            stride = batch.out_stride_for(max_len, self.__bit_frames)
+            # (files of different lengths: the host-side lengths let the launch take the longest streams first)
+            res = batch.demod_batch(samples, off, ln, self.__bit_frames, self.__amp_end_threshold,
+                                    out_stride=stride, stream_len_host=ln.cpu().numpy())
         torch.cuda.synchronize()
         return [d.decode("utf-8") if (string and d != b"") else d for d in res.payloads()]
+
+    def __demod_split(self, samples, off, ln, max_len):
+        from . import batch
+        plan = batch.SplitPlan(ln.cpu().numpy(), self.__bit_frames, device=samples.device)
+        stride = batch.out_stride_for(max_len, self.__bit_frames)
+        return batch.demod_batch_split(samples, off, ln, plan, self.__amp_end_threshold, out_stride=stride)
 
     def decode_captures(self, captures, max_bursts: int = 16, string: bool = False):
         """What repeated ``receive()`` calls would return if each capture (a long int16

@@ -195,6 +195,46 @@ int afsk_demod_batch_grouped(const afsk_group_plan *plan, const int16_t *samples
                              int32_t *out_margins, int32_t margin_stride, void *hip_stream);
 
 /*
+ * Sequence-parallel demodulation (an addition: ABI version unchanged) for batches of FEW, LONG streams -- one long
+ * recording, a large payload, the live gate's bursts -- where one wavefront per stream cannot fill the device.  The
+ * work of one stream is split over many wavefronts: clock recovery per stream, then per-symbol decisions and squelch
+ * flags by SEGMENTS of segment_symbols symbols (any number of wavefronts per stream), then terminator scan, squelch
+ * stop, Hamming decode and byte pack per stream -- three kernel launches in order on hip_stream (a captured graph of
+ * them is a linear chain).  Outputs are bit for bit what afsk_demod_batch_ex writes for the same input, including
+ * clock_idx / term_frame / nbits of NO_DATA, TOO_SHORT and BAD_LENGTH streams; row bytes past nbytes are untouched.
+ * Only 1200 baud (bit_frames 40) has a tuned segment kernel; every other valid bit_frames is decoded correctly.
+ *
+ *  afsk_split_plan_create   stream_len_host / bit_frames_host: HOST arrays [n] (several rates may be mixed; invalid
+ *                           bit_frames: AFSK_E_INVALID_BAUD; a length outside 0 ... AFSK_MAX_STREAM_LEN:
+ *                           AFSK_E_INVALID_ARG).  segment_symbols: a multiple of 64, 0 = the default (1024).
+ *                           The plan (segment table, per-stream scratch offsets) lives on the current device;
+ *                           it is sized with ceil(len / bit_frames) symbols per stream (synchronous upload).
+ *  afsk_split_plan_info     n_streams, number of segments, scratch bytes a launch needs; any pointer may be NULL
+ *  afsk_split_scratch_bytes host-only (no device needed): what afsk_split_plan_create would report for these arguments
+ *  afsk_demod_batch_split   every array as afsk_demod_batch_ex (n_streams is the plan's); d_scratch: caller-owned
+ *                           device memory of the plan's scratch bytes, contents need not be initialised, one launch
+ *                           at a time per scratch buffer.  A device stream_len[s] above the length the plan was built
+ *                           for gives that stream AFSK_ST_BAD_LENGTH (so does the usual range rule); shorter lengths
+ *                           are fine.  bit_frames come from the plan.
+ *  afsk_split_plan_destroy  after the launches that use the plan have completed (NULL is fine)
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, SPLIT_SIGNATURES, apart from
+ * the SIGNATURES table that mirrors the `int afsk_*(` declarations above one to one.)
+ */
+typedef struct afsk_split_plan afsk_split_plan;
+extern int afsk_split_plan_create(const int32_t *stream_len_host, const int32_t *bit_frames_host, int32_t n_streams,
+                           int32_t segment_symbols, afsk_split_plan **out_plan);
+extern int afsk_split_plan_info(const afsk_split_plan *plan, int32_t *out_n_streams, int32_t *out_n_segments,
+                         int64_t *out_scratch_bytes);
+extern int afsk_split_plan_destroy(afsk_split_plan *plan);
+extern int afsk_split_scratch_bytes(const int32_t *stream_len_host, const int32_t *bit_frames_host, int32_t n_streams,
+                             int32_t segment_symbols, int64_t *out_scratch_bytes, int32_t *out_n_segments);
+extern int afsk_demod_batch_split(const afsk_split_plan *plan, const int16_t *samples, const int64_t *stream_offset,
+                           const int32_t *stream_len, int32_t amp_end_threshold, void *d_scratch,
+                           uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes, int32_t *out_nbits,
+                           int32_t *out_clock_idx, int32_t *out_term_frame, int32_t *out_status,
+                           int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride, void *hip_stream);
+
+/*
  * Same operation on HOST buffers: allocates device scratch, copies in, runs the
  * HIP kernel, copies out, synchronises.  This is the PCIe-inclusive convenience
  * path a single Receiver.load() uses; it is not the benchmarked entry.
