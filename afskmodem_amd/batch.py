@@ -310,36 +310,14 @@ def _cached_plan(bit_frames, n: int, dev, stream_len_host=None) -> "GroupPlan":
     return fresh
 
 
-class GroupPlan:
-    """Rate-grouped dispatch plan of a mixed-baud batch whose ``bit_frames`` the host can see
-    (``afsk_group_plan_create``): the streams bucketed by rate, decoded by ONE launch that walks them bucket
-    by bucket (neighbouring wavefronts run the same rate's code), outputs at the original stream numbers.
-    Build it once per batch layout and pass it to ``demod_batch(..., plan=...)``; it belongs to the device
-    that was current when it was built.
+class _NativePlan:
+    """What ``GroupPlan`` and ``SplitPlan`` share: the native handle, the device the plan belongs to, and its release
+    through the native destroy function named by ``_destroy``."""
+    _destroy: str
 
-    ``stream_len`` (r6, ``afsk_group_plan_create_ragged``): the HOST-side lengths of the streams.  One wavefront decodes
-    one stream whatever its length, and a workgroup of four holds its share of a CU until its longest stream ends: when
-    the lengths differ (shortest below 3/4 of the longest) the walk takes the longest streams first inside every window
-    of 4096 streams and every rate -- also for a single rate.  Speed only: the outputs are the same."""
-
-    def __init__(self, bit_frames, device=None, stream_len=None):
-        torch = _torch()
-        _native.require_device()
-        _drain_parked_plans()
-        self.bit_frames = np.ascontiguousarray(np.asarray(bit_frames, dtype=np.int32).reshape(-1))
-        self.n = int(self.bit_frames.size)
-        self.stream_len = None
-        if stream_len is not None:
-            self.stream_len = np.ascontiguousarray(np.asarray(stream_len, dtype=np.int32).reshape(-1))
-            if self.stream_len.size != self.n:
-                raise ValueError(f"stream_len holds {self.stream_len.size} values for {self.n} streams")
+    def __init__(self, device):
         self.device = _default_device(device)
         self._h = C.c_void_p()
-        i32 = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().afsk_group_plan_create_ragged(
-                self.bit_frames.ctypes.data_as(i32),
-                None if self.stream_len is None else self.stream_len.ctypes.data_as(i32), self.n, C.byref(self._h)))
 
     @property
     def handle(self):
@@ -347,23 +325,14 @@ class GroupPlan:
             raise ValueError("the plan has been closed")
         return self._h
 
-    def groups(self) -> list[tuple[int, int]]:
-        """[(bit_frames, streams)] per bucket, in launch order (largest first; bit_frames 0 = refused streams)."""
-        ng, nn = C.c_int32(), C.c_int32()
-        lib = _native.lib()
-        _native.check(lib.afsk_group_plan_info(self.handle, C.byref(nn), C.byref(ng), None, None, 0))
-        bf, cnt = (C.c_int32 * max(ng.value, 1))(), (C.c_int32 * max(ng.value, 1))()
-        _native.check(lib.afsk_group_plan_info(self.handle, None, None, bf, cnt, ng.value))
-        return [(int(bf[k]), int(cnt[k])) for k in range(ng.value)]
-
     def close(self) -> None:
         """Free the plan (after the launches that use it have completed)."""
         if self._h:
-            _native.lib().afsk_group_plan_destroy(self._h)
+            getattr(_native.lib(), self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
-        # Launches that use the plan's device index list may still be queued: free it behind a device synchronise.
+        # Launches that use the plan's device tables may still be queued: free them behind a device synchronise.
         # Not inside a HIP stream capture (the last DemodResult of a cached plan may be dropped there, e.g. by
         # rebinding ``res = demod_batch(...)`` while capturing): a synchronise would invalidate the capture, so the
         # handle is parked and freed by the next plan construction / explicit ``release_parked_plans()`` outside one.
@@ -376,16 +345,58 @@ class GroupPlan:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("capturing")
             torch.cuda.synchronize(self.device)
-            _native.lib().afsk_group_plan_destroy(h)
+            getattr(_native.lib(), self._destroy)(h)
         except Exception:  # noqa: BLE001  (capturing, a failed synchronise, interpreter shutdown): never drop the handle
             try:
                 with _PARKED_LOCK:
-                    _PARKED_PLANS.append((h, self.device))
+                    _PARKED_PLANS.append((h, self.device, self._destroy))
             except Exception:  # noqa: BLE001
                 pass
 
 
-_PARKED_PLANS: list = []          # (handle, device) of plans whose owner died where no synchronise was possible
+class GroupPlan(_NativePlan):
+    """Rate-grouped dispatch plan of a mixed-baud batch whose ``bit_frames`` the host can see
+    (``afsk_group_plan_create``): the streams bucketed by rate, decoded by ONE launch that walks them bucket
+    by bucket (neighbouring wavefronts run the same rate's code), outputs at the original stream numbers.
+    Build it once per batch layout and pass it to ``demod_batch(..., plan=...)``; it belongs to the device
+    that was current when it was built.
+
+    ``stream_len`` (r6, ``afsk_group_plan_create_ragged``): the HOST-side lengths of the streams.  One wavefront decodes
+    one stream whatever its length, and a workgroup of four holds its share of a CU until its longest stream ends: when
+    the lengths differ (shortest below 3/4 of the longest) the walk takes the longest streams first inside every window
+    of 8192 streams (twice the window of a rate-only plan; ``AFSK_GROUP_WINDOW``, when set, is both) and every rate --
+    also for a single rate.  Speed only: the outputs are the same."""
+    _destroy = "afsk_group_plan_destroy"
+
+    def __init__(self, bit_frames, device=None, stream_len=None):
+        torch = _torch()
+        _native.require_device()
+        _drain_parked_plans()
+        self.bit_frames = np.ascontiguousarray(np.asarray(bit_frames, dtype=np.int32).reshape(-1))
+        self.n = int(self.bit_frames.size)
+        self.stream_len = None
+        if stream_len is not None:
+            self.stream_len = np.ascontiguousarray(np.asarray(stream_len, dtype=np.int32).reshape(-1))
+            if self.stream_len.size != self.n:
+                raise ValueError(f"stream_len holds {self.stream_len.size} values for {self.n} streams")
+        super().__init__(device)
+        i32 = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().afsk_group_plan_create_ragged(
+                self.bit_frames.ctypes.data_as(i32),
+                None if self.stream_len is None else self.stream_len.ctypes.data_as(i32), self.n, C.byref(self._h)))
+
+    def groups(self) -> list[tuple[int, int]]:
+        """[(bit_frames, streams)] per bucket, in launch order (largest first; bit_frames 0 = refused streams)."""
+        ng, nn = C.c_int32(), C.c_int32()
+        lib = _native.lib()
+        _native.check(lib.afsk_group_plan_info(self.handle, C.byref(nn), C.byref(ng), None, None, 0))
+        bf, cnt = (C.c_int32 * max(ng.value, 1))(), (C.c_int32 * max(ng.value, 1))()
+        _native.check(lib.afsk_group_plan_info(self.handle, None, None, bf, cnt, ng.value))
+        return [(int(bf[k]), int(cnt[k])) for k in range(ng.value)]
+
+
+_PARKED_PLANS: list = []          # (handle, device, destroy function name) of plans whose owner died where no synchronise was possible
 _PARKED_LOCK = threading.Lock()
 
 
@@ -400,22 +411,58 @@ def _drain_parked_plans() -> None:
         return
     with _PARKED_LOCK:
         todo, _PARKED_PLANS[:] = list(_PARKED_PLANS), []
-    for h, dev, *kind in todo:
+    for h, dev, destroy in todo:
         try:
             torch.cuda.synchronize(dev)
-            if kind:
-                _native.lib().afsk_split_plan_destroy(h)
-            else:
-                _native.lib().afsk_group_plan_destroy(h)
+            getattr(_native.lib(), destroy)(h)
         except Exception:  # noqa: BLE001
             with _PARKED_LOCK:
-                _PARKED_PLANS.append((h, dev, *kind))
+                _PARKED_PLANS.append((h, dev, destroy))
 
 
 def release_parked_plans() -> int:
     """Free the plans whose last reference went away inside a stream capture; returns how many are still parked."""
     _drain_parked_plans()
     return len(_PARKED_PLANS)
+
+
+def _check_index_tensors(dev, stream_offset, stream_len) -> None:
+    """stream_offset / stream_len of a device launch: int64 / int32 CUDA tensors on ``dev``, contiguous."""
+    torch = _torch()
+    if stream_offset.dtype != torch.int64 or stream_len.dtype != torch.int32:
+        raise TypeError("stream_offset must be int64 and stream_len int32")
+    if not (stream_offset.is_cuda and stream_len.is_cuda):
+        raise TypeError("stream_offset / stream_len must be CUDA tensors")
+    _same_device(dev, stream_offset=stream_offset, stream_len=stream_len)
+    if not (stream_offset.is_contiguous() and stream_len.is_contiguous()):
+        raise ValueError("stream_offset / stream_len must be contiguous (the kernel reads them as plain arrays)")
+
+
+def _prepare_outputs(out, out_stride, n: int, dev, diagnostics: bool, margin_stride):
+    """``out`` (allocated when None) with the soft outputs ``diagnostics`` asks for.  Returns (out, fresh, args):
+    ``fresh`` = tensors were created (zero-filled) here; ``args`` = the output block of the device demod entries --
+    bytes, stride, the five int32 arrays, corrected, margins, margin_stride."""
+    torch = _torch()
+    fresh = False
+    if out is None:
+        if out_stride is None:
+            raise ValueError("pass out= or out_stride=")
+        out = alloc_result(n, int(out_stride), dev)
+        fresh = True
+    soft = (None, None, 0)
+    if diagnostics:
+        if out.corrected is None:
+            out.corrected = torch.zeros(n, dtype=torch.int32, device=dev)
+            fresh = True
+        if out.margins is None:
+            if margin_stride is None:
+                raise ValueError("diagnostics=True needs margin_stride= (symbols per margins row)")
+            out.margins = torch.zeros((n, int(margin_stride)), dtype=torch.int32, device=dev)
+            fresh = True
+        soft = (out.corrected.data_ptr(), out.margins.data_ptr(), int(out.margins.shape[1]))
+    _same_device(dev, out_bytes=out.bytes, out_nbytes=out.nbytes, out_status=out.status)
+    return out, fresh, (out.bytes.data_ptr(), int(out.bytes.shape[1]), out.nbytes.data_ptr(), out.nbits.data_ptr(),
+                        out.clock_idx.data_ptr(), out.term_frame.data_ptr(), out.status.data_ptr(), *soft)
 
 
 def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshold: int = 14000,
@@ -438,7 +485,7 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
                    geometry) when the host can see that bit_frames is one value;
                    ``afsk_demod_batch_grouped`` (one launch over the rate-sorted streams) when it can
                    see several (a host sequence / array, or ``plan=``); the per-stream
-                   ``afsk_demod_batch`` / ``_ex`` for a device tensor.  "uniform" / "grouped" / "mixed"
+                   ``afsk_demod_batch_ex`` for a device tensor.  "uniform" / "grouped" / "mixed"
                    force one.  The uniform entry raises AFSK_E_INVALID_BAUD for an invalid value
                    (``validate=False``); the grouped and mixed entries write status 3 for such streams.
     plan           a ``GroupPlan`` built from this batch's host-side bit_frames: reused across calls
@@ -463,13 +510,7 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
         raise ValueError("bit_frames=None needs plan= (the plan holds the batch's bit_frames)")
     if validate and bit_frames is not None and not isinstance(bit_frames, torch.Tensor):
         validate_bit_frames(bit_frames)
-    if stream_offset.dtype != torch.int64 or stream_len.dtype != torch.int32:
-        raise TypeError("stream_offset must be int64 and stream_len int32")
-    if not (stream_offset.is_cuda and stream_len.is_cuda):
-        raise TypeError("stream_offset / stream_len must be CUDA tensors")
-    _same_device(dev, stream_offset=stream_offset, stream_len=stream_len)
-    if not (stream_offset.is_contiguous() and stream_len.is_contiguous()):
-        raise ValueError("stream_offset / stream_len must be contiguous (the kernel reads them as plain arrays)")
+    _check_index_tensors(dev, stream_offset, stream_len)
     host_bf = isinstance(bit_frames, (int, np.integer, list, tuple, np.ndarray))
     if plan is not None:
         if entry not in ("auto", "grouped"):
@@ -484,26 +525,8 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
     if entry == "grouped" and plan is None and not host_bf:
         raise ValueError("entry='grouped' needs host-side bit_frames (or plan=): a device tensor is never inspected")
     grouped = entry == "grouped" or ragged or (entry == "auto" and ubf is None and host_bf)
-    fresh = False                      # tensors created (zero-filled / uploaded) inside this call
-    if out is None:
-        if out_stride is None:
-            raise ValueError("pass out= or out_stride=")
-        out = alloc_result(n, int(out_stride), dev)
-        fresh = True
-    stride = int(out.bytes.shape[1])
-    corrected_ptr = margins_ptr = None
-    mstride = 0
-    if diagnostics:
-        if out.corrected is None:
-            out.corrected = torch.zeros(n, dtype=torch.int32, device=dev)
-            fresh = True
-        if out.margins is None:
-            if margin_stride is None:
-                raise ValueError("diagnostics=True needs margin_stride= (symbols per margins row)")
-            out.margins = torch.zeros((n, int(margin_stride)), dtype=torch.int32, device=dev)
-            fresh = True
-        corrected_ptr, margins_ptr, mstride = out.corrected.data_ptr(), out.margins.data_ptr(), int(out.margins.shape[1])
-    _same_device(dev, out_bytes=out.bytes, out_nbytes=out.nbytes, out_status=out.status)
+    out, fresh, outs = _prepare_outputs(out, out_stride, n, dev, diagnostics, margin_stride)
+    amp = threshold_lt(amp_end_threshold)
     lib = _native.lib()
     # the device entries launch on the CURRENT HIP device: make that the one the data lives on
     with torch.cuda.device(dev):
@@ -511,35 +534,22 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
             _order_after_current(stream, dev)
         if ubf is not None:
             _native.check(lib.afsk_demod_batch_uniform(
-                samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), ubf,
-                threshold_lt(amp_end_threshold), n, out.bytes.data_ptr(), stride, out.nbytes.data_ptr(),
-                out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
-                out.status.data_ptr(), corrected_ptr, margins_ptr, mstride, _stream_ptr(stream, dev)))
+                samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), ubf, amp, n, *outs,
+                _stream_ptr(stream, dev)))
             return out
         if grouped:
             if plan is None:
                 plan = _cached_plan(bit_frames, n, dev, stream_len_host if ragged else None)
             _native.check(lib.afsk_demod_batch_grouped(
-                plan.handle, samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(),
-                threshold_lt(amp_end_threshold), out.bytes.data_ptr(), stride, out.nbytes.data_ptr(),
-                out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
-                out.status.data_ptr(), corrected_ptr, margins_ptr, mstride, _stream_ptr(stream, dev)))
+                plan.handle, samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), amp, *outs,
+                _stream_ptr(stream, dev)))
             out._plan_keepalive = plan  # type: ignore[attr-defined]   (the plan's device index list outlives the launch)
             return out
         bf = _as_device_i32(bit_frames, n, dev)
         _order_after_current(stream, dev)
-        if diagnostics:
-            _native.check(lib.afsk_demod_batch_ex(
-                samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), bf.data_ptr(),
-                threshold_lt(amp_end_threshold), n, out.bytes.data_ptr(), stride, out.nbytes.data_ptr(),
-                out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
-                out.status.data_ptr(), corrected_ptr, margins_ptr, mstride, _stream_ptr(stream, dev)))
-        else:
-            _native.check(lib.afsk_demod_batch(
-                samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), bf.data_ptr(),
-                threshold_lt(amp_end_threshold), n, out.bytes.data_ptr(), stride, out.nbytes.data_ptr(),
-                out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
-                out.status.data_ptr(), _stream_ptr(stream, dev)))
+        _native.check(lib.afsk_demod_batch_ex(
+            samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), bf.data_ptr(), amp, n, *outs,
+            _stream_ptr(stream, dev)))
     # keep the bit_frames tensor alive until the launch has been enqueued on the stream
     out._bf_keepalive = bf  # type: ignore[attr-defined]
     return out
@@ -574,13 +584,14 @@ def split_scratch_bytes(stream_len_host, bit_frames, segment_symbols: int = 0) -
     return int(nbytes.value), int(nseg.value)
 
 
-class SplitPlan:
+class SplitPlan(_NativePlan):
     """Sequence-parallel plan (``afsk_split_plan_create``) for a batch of few, long streams: every stream is cut into
     segments of ``segment_symbols`` symbols (a multiple of 64; 0 = the default) that separate wavefronts demodulate, so
     that one long recording fills the device.  ``stream_len_host`` / ``bit_frames``: the HOST-side lengths and rates
     (an int or one value per stream; rates may be mixed).  Owns the plan's segment table and the scratch tensor a launch
     needs; same lifetime and close rules as ``GroupPlan`` (it belongs to the device that was current when it was built;
     ``close()`` only after the launches that use it have completed).  Decode with ``demod_batch_split``."""
+    _destroy = "afsk_split_plan_destroy"
 
     def __init__(self, stream_len_host, bit_frames, device=None, segment_symbols: int = 0):
         torch = _torch()
@@ -591,8 +602,7 @@ class SplitPlan:
         self.bit_frames = bf
         self.n = int(lens.size)
         self.segment_symbols = seg
-        self.device = _default_device(device)
-        self._h = C.c_void_p()
+        super().__init__(device)
         i32 = C.POINTER(C.c_int32)
         lib = _native.lib()
         with torch.cuda.device(self.device):
@@ -603,37 +613,6 @@ class SplitPlan:
             self.n_segments = int(nseg.value)
             self.scratch_bytes = int(nbytes.value)
             self.scratch = torch.empty(max(self.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
-
-    @property
-    def handle(self):
-        if not self._h:
-            raise ValueError("the plan has been closed")
-        return self._h
-
-    def close(self) -> None:
-        """Free the plan (after the launches that use it have completed)."""
-        if self._h:
-            _native.lib().afsk_split_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        # as GroupPlan.__del__: launches may still be queued, so free behind a device synchronise, or park the handle
-        h = getattr(self, "_h", None)
-        if not h:
-            return
-        self._h = None
-        try:
-            torch = _torch()
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("capturing")
-            torch.cuda.synchronize(self.device)
-            _native.lib().afsk_split_plan_destroy(h)
-        except Exception:  # noqa: BLE001
-            try:
-                with _PARKED_LOCK:
-                    _PARKED_PLANS.append((h, self.device, "split"))
-            except Exception:  # noqa: BLE001
-                pass
 
 
 def demod_batch_split(samples, stream_offset, stream_len, plan: SplitPlan, amp_end_threshold: int = 14000,
@@ -665,38 +644,17 @@ def demod_batch_split(samples, stream_offset, stream_len, plan: SplitPlan, amp_e
         raise TypeError("samples must be an int16 CUDA tensor (HBM resident)")
     if not samples.is_contiguous():
         raise ValueError("samples must be contiguous")
-    if not (stream_offset.is_cuda and stream_len.is_cuda):
-        raise TypeError("stream_offset / stream_len must be CUDA tensors")
     dev = samples.device
-    _same_device(dev, stream_offset=stream_offset, stream_len=stream_len)
-    if not (stream_offset.is_contiguous() and stream_len.is_contiguous()):
-        raise ValueError("stream_offset / stream_len must be contiguous (the kernel reads them as plain arrays)")
+    _check_index_tensors(dev, stream_offset, stream_len)
     if plan.device != dev:
         raise ValueError(f"the plan was built on {plan.device}, the batch lives on {dev}")
-    fresh = False
-    if out is None:
-        out = alloc_result(n, int(out_stride), dev)
-        fresh = True
-    stride = int(out.bytes.shape[1])
-    corrected_ptr = margins_ptr = None
-    mstride = 0
-    if diagnostics:
-        if out.corrected is None:
-            out.corrected = torch.zeros(n, dtype=torch.int32, device=dev)
-            fresh = True
-        if out.margins is None:
-            out.margins = torch.zeros((n, int(margin_stride)), dtype=torch.int32, device=dev)
-            fresh = True
-        corrected_ptr, margins_ptr, mstride = out.corrected.data_ptr(), out.margins.data_ptr(), int(out.margins.shape[1])
-    _same_device(dev, out_bytes=out.bytes, out_nbytes=out.nbytes, out_status=out.status)
+    out, fresh, outs = _prepare_outputs(out, out_stride, n, dev, diagnostics, margin_stride)
     with torch.cuda.device(dev):
         if fresh:
             _order_after_current(stream, dev)
         _native.check(_native.lib().afsk_demod_batch_split(
             plan.handle, samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(),
-            threshold_lt(amp_end_threshold), plan.scratch.data_ptr(), out.bytes.data_ptr(), stride,
-            out.nbytes.data_ptr(), out.nbits.data_ptr(), out.clock_idx.data_ptr(), out.term_frame.data_ptr(),
-            out.status.data_ptr(), corrected_ptr, margins_ptr, mstride, _stream_ptr(stream, dev)))
+            threshold_lt(amp_end_threshold), plan.scratch.data_ptr(), *outs, _stream_ptr(stream, dev)))
     out._plan_keepalive = plan  # type: ignore[attr-defined]   (the plan's segment table outlives the launch)
     return out
 

@@ -28,11 +28,14 @@
 #include <vector>
 
 #include "../../include/afsk_amd.h"
+#include "afsk_capi_internal.h"
 #include "afsk_kernels.h"
 
 namespace {
-
 thread_local std::string g_last_error;
+}  // namespace
+
+namespace afsk {
 
 int fail(int code, const std::string& msg) {
     g_last_error = msg;
@@ -53,6 +56,24 @@ int require_device() {
     return AFSK_OK;
 }
 
+int plan_on_current_device(int plan_device) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != plan_device)
+        return fail(AFSK_E_INVALID_ARG, "the plan was created on another device than the current one");
+    return AFSK_OK;
+}
+
+}  // namespace afsk
+
+using afsk::bf_valid;
+using afsk::DemodOutputs;
+using afsk::fail;
+using afsk::fail_bit_frames;
+using afsk::hip_fail;
+using afsk::no_throw;
+using afsk::require_device;
+
+namespace {
 
 // ---- NUMA: keep the host side of the PCIe traffic on the socket the GPU hangs off ---------------------------
 // The GPU boxes are two-socket hosts (2 x 64 cores, 4 GPUs per socket).  A staging buffer pinned on the other
@@ -609,7 +630,6 @@ struct GroupPlan {
         if (own_index && d_index) (void)hipFree(d_index);
     }
 
-    static bool valid_bf(int32_t bf) { return bf >= 4 && (bf & 3) == 0 && 2 * bf < AFSK_SYNC_WINDOW; }
     bool sorted() const { return by_length || groups.size() >= sort_from(); }
     static size_t sort_from() {                  // AFSK_GROUP_SORT_FROM overrides (A/B runs)
         const char* e = std::getenv("AFSK_GROUP_SORT_FROM");
@@ -636,7 +656,7 @@ struct GroupPlan {
         n = n_streams;
         by_length = lengths_ragged(h_len, n_streams) && !std::getenv("AFSK_GROUP_NO_LENGTH_SORT");
         std::vector<int32_t> count(AFSK_SYNC_WINDOW / 2 + 1, 0);    // slot 0 = every invalid value
-        auto slot = [](int32_t bf) { return valid_bf(bf) ? bf : 0; };
+        auto slot = [](int32_t bf) { return bf_valid(bf) ? bf : 0; };
         for (int32_t s = 0; s < n; s++) count[(size_t)slot(h_bf[s])]++;
         std::vector<int32_t> order;
         for (int32_t bf = 4; bf < (int32_t)count.size(); bf += 4)
@@ -737,29 +757,94 @@ struct GroupPlan {
         if (e_ != hipSuccess) { rc = hip_fail(e_, what); goto done; } \
     } while (0)
 
-// The host-buffer entries allocate (std::vector, std::thread): nothing may be thrown across the
-// C boundary, so the bodies live in *_impl and the exported functions catch everything.
-template <class F>
-int no_throw(F&& body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(AFSK_E_HOST, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(AFSK_E_HOST, std::string("host-side failure: ") + e.what());
-    } catch (...) {
-        return fail(AFSK_E_HOST, "host-side failure");
+// The host entries see the bit_frames array (checked valid, the device present): one value for all streams ->
+// the uniform kernel; several -> the grouped dispatch (index list + bit_frames live in `index_storage`, 2 n int32 of
+// the caller's device scratch; `keep` owns the plan's host side until the caller has synchronised).
+int demod_device_auto(const int32_t* h_bit_frames, const int32_t* h_stream_len, const int16_t* samples,
+                      const int64_t* stream_offset, const int32_t* stream_len, int32_t amp_end_threshold,
+                      int32_t n_streams, const DemodOutputs& o, hipStream_t stream, int32_t* index_storage,
+                      std::unique_ptr<GroupPlan>& keep) {
+    afsk::DemodArgs a = o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold, n_streams);
+    bool same = true;
+    for (int32_t s = 1; s < n_streams && same; s++) same = h_bit_frames[s] == h_bit_frames[0];
+    // (one rate but ragged lengths: the plan, whose walk takes the longest streams first -- GroupPlan::bucket)
+    if (same && !GroupPlan::lengths_ragged(h_stream_len, n_streams)) {
+        a.uniform_bit_frames = h_bit_frames[0];
+        hipError_t e = afsk::launch_demod_uniform(a, stream);
+        return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_uniform_kernel");
     }
+    keep.reset(new GroupPlan());
+    keep->bucket(h_bit_frames, n_streams, h_stream_len);
+    hipError_t e = keep->materialise(index_storage, stream);
+    if (e != hipSuccess) return hip_fail(e, "grouped dispatch (index list)");
+    e = keep->launch(a, stream);
+    return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_kernel (grouped)");
+}
+
+// The part of the host-buffer entries that follows their argument checks.  Device scratch: samples | meta = offsets,
+// len, bf | the index list and bit_frames of a grouped dispatch | out = 5 x int32 [n], bytes [n, stride].
+// upload(lease, d_samples, stream) puts the total_samples samples at the start of it, where dev_offset[] points;
+// then one H2D of the meta block, the launch, one D2H of all outputs and the scatter into `o` (host arrays).
+// `block`: wait for the shared scratch cache (which owns the staging windows) instead of allocating privately.
+template <class Upload>
+int run_host_entry(int64_t total_samples, const int64_t* dev_offset, const int32_t* stream_len,
+                   const int32_t* bit_frames, int32_t amp_end_threshold, int32_t n_streams,
+                   const DemodOutputs& o, bool block, Upload&& upload) {
+    if (int rc0 = require_device()) return rc0;
+
+    int rc = AFSK_OK;
+    const size_t n = (size_t)n_streams;
+    const size_t sample_bytes = (size_t)(total_samples > 0 ? total_samples : 1) * 2;
+    const size_t bytes_out = n * (size_t)o.stride;
+    const size_t o_meta = (sample_bytes + 255) & ~(size_t)255;
+    const size_t meta_bytes = n * 16;
+    const size_t o_out = o_meta + meta_bytes + n * 8;      // + the index list and bit_frames of a grouped dispatch
+    const size_t out_bytes_total = n * 20 + bytes_out;
+    hipStream_t stream = nullptr;
+    {
+        hipError_t e = g_thread_stream.get(&stream);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithFlags (host-entry stream)");
+    }
+    ScratchLease lease;
+    std::unique_ptr<GroupPlan> plan;      // mixed rates: the host copy of the index list, alive until the final synchronise
+    char* d_all = nullptr;
+    // host staging: one H2D for the three index arrays, one D2H for all six outputs
+    std::vector<char> h_meta(meta_bytes), h_out(out_bytes_total);
+    std::memcpy(h_meta.data(), dev_offset, n * 8);
+    std::memcpy(h_meta.data() + n * 8, stream_len, n * 4);
+    std::memcpy(h_meta.data() + n * 12, bit_frames, n * 4);
+    {
+        hipError_t e = lease.acquire(o_out + out_bytes_total, &d_all, block);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc (host-entry scratch)");
+    }
+    if ((rc = upload(lease, d_all, stream)) != AFSK_OK) goto done;
+    AFSK_HIP(hipMemcpyAsync(d_all + o_meta, h_meta.data(), meta_bytes, hipMemcpyHostToDevice, stream),
+             "H2D stream index");
+    {
+        int32_t* i32 = (int32_t*)(d_all + o_out);
+        const DemodOutputs d_out{(uint8_t*)(d_all + o_out + n * 20), o.stride, i32, i32 + n, i32 + 2 * n, i32 + 3 * n,
+                                 i32 + 4 * n, nullptr, nullptr, 0};
+        rc = demod_device_auto(bit_frames, stream_len, (const int16_t*)d_all, (const int64_t*)(d_all + o_meta),
+                               (const int32_t*)(d_all + o_meta + n * 8), amp_end_threshold, n_streams, d_out, stream,
+                               (int32_t*)(d_all + o_meta + n * 16), plan);
+        if (rc != AFSK_OK) goto done;
+    }
+    AFSK_HIP(hipMemcpyAsync(h_out.data(), d_all + o_out, out_bytes_total, hipMemcpyDeviceToHost, stream),
+             "D2H results");
+    AFSK_HIP(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    std::memcpy(o.nbytes, h_out.data(), n * 4);
+    std::memcpy(o.nbits, h_out.data() + n * 4, n * 4);
+    std::memcpy(o.clock_idx, h_out.data() + n * 8, n * 4);
+    std::memcpy(o.term_frame, h_out.data() + n * 12, n * 4);
+    std::memcpy(o.status, h_out.data() + n * 16, n * 4);
+    if (bytes_out > 0) std::memcpy(o.bytes, h_out.data() + n * 20, bytes_out);
+done:
+    // nothing may still use the scratch, the staging windows or the host vectors when they are released
+    if (rc != AFSK_OK) (void)hipStreamSynchronize(stream);
+    return rc;   // the lease returns (or frees) the device scratch
 }
 
 }  // namespace
-
-namespace afsk {
-// the last-error slot of this library for entries implemented in other translation units (afsk_split.hip)
-int capi_fail(int code, const char* msg) { return fail(code, msg); }
-int capi_hip_fail(hipError_t e, const char* what) { return hip_fail(e, what); }
-int capi_require_device() { return require_device(); }
-}  // namespace afsk
 
 extern "C" {
 
@@ -807,22 +892,15 @@ int afsk_demod_batch_ex(const int16_t* samples, const int64_t* stream_offset,
                         int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status,
                         int32_t* out_corrected, int32_t* out_margins, int32_t margin_stride,
                         void* hip_stream) {
-    if (n_streams < 0 || out_stride < 0 || margin_stride < 0)
-        return fail(AFSK_E_INVALID_ARG, "negative size");
+    const DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                         out_corrected, out_margins, margin_stride};
+    if (n_streams < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_streams == 0) return AFSK_OK;
-    if (!samples || !stream_offset || !stream_len || !bit_frames || !out_nbytes || !out_nbits ||
-        !out_clock_idx || !out_term_frame || !out_status || (!out_bytes && out_stride > 0))
+    if (!samples || !stream_offset || !stream_len || !bit_frames || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
-    afsk::DemodArgs a;
-    a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
-    a.bit_frames = bit_frames; a.amp_end = amp_end_threshold; a.n_streams = n_streams;
-    a.out_bytes = out_bytes; a.out_stride = out_stride; a.out_nbytes = out_nbytes;
-    a.out_nbits = out_nbits; a.out_clock_idx = out_clock_idx; a.out_term_frame = out_term_frame;
-    a.out_status = out_status;
-    a.out_corrected = out_corrected;
-    a.out_margins = margin_stride > 0 ? out_margins : nullptr;
-    a.margin_stride = margin_stride;
+    afsk::DemodArgs a = o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold, n_streams);
+    a.bit_frames = bit_frames;
     hipError_t e = afsk::launch_demod(a, (hipStream_t)hip_stream);
     return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_kernel");
 }
@@ -834,25 +912,16 @@ int afsk_demod_batch_uniform(const int16_t* samples, const int64_t* stream_offse
                              int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status,
                              int32_t* out_corrected, int32_t* out_margins, int32_t margin_stride,
                              void* hip_stream) {
-    if (n_streams < 0 || out_stride < 0 || margin_stride < 0)
-        return fail(AFSK_E_INVALID_ARG, "negative size");
-    if (bit_frames < 4 || (bit_frames & 3) || 2 * bit_frames >= AFSK_SYNC_WINDOW)
-        return fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 with 2*bf < 4096");
+    const DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                         out_corrected, out_margins, margin_stride};
+    if (n_streams < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
+    if (!bf_valid(bit_frames)) return fail_bit_frames();
     if (n_streams == 0) return AFSK_OK;
-    if (!samples || !stream_offset || !stream_len || !out_nbytes || !out_nbits ||
-        !out_clock_idx || !out_term_frame || !out_status || (!out_bytes && out_stride > 0))
+    if (!samples || !stream_offset || !stream_len || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
-    afsk::DemodArgs a;
-    a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
-    a.bit_frames = nullptr; a.uniform_bit_frames = bit_frames;
-    a.amp_end = amp_end_threshold; a.n_streams = n_streams;
-    a.out_bytes = out_bytes; a.out_stride = out_stride; a.out_nbytes = out_nbytes;
-    a.out_nbits = out_nbits; a.out_clock_idx = out_clock_idx; a.out_term_frame = out_term_frame;
-    a.out_status = out_status;
-    a.out_corrected = out_corrected;
-    a.out_margins = margin_stride > 0 ? out_margins : nullptr;
-    a.margin_stride = margin_stride;
+    afsk::DemodArgs a = o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold, n_streams);
+    a.uniform_bit_frames = bit_frames;
     hipError_t e = afsk::launch_demod_uniform(a, (hipStream_t)hip_stream);
     return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_uniform_kernel");
 }
@@ -903,58 +972,17 @@ int afsk_demod_batch_grouped(const afsk_group_plan* plan, const int16_t* samples
                              int32_t* out_nbytes, int32_t* out_nbits, int32_t* out_clock_idx,
                              int32_t* out_term_frame, int32_t* out_status, int32_t* out_corrected,
                              int32_t* out_margins, int32_t margin_stride, void* hip_stream) {
+    const DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                         out_corrected, out_margins, margin_stride};
     if (!plan) return fail(AFSK_E_INVALID_ARG, "null plan");
-    if (out_stride < 0 || margin_stride < 0) return fail(AFSK_E_INVALID_ARG, "negative size");
+    if (o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
     if (plan->p.n == 0) return AFSK_OK;
-    if (!samples || !stream_offset || !stream_len || !out_nbytes || !out_nbits ||
-        !out_clock_idx || !out_term_frame || !out_status || (!out_bytes && out_stride > 0))
+    if (!samples || !stream_offset || !stream_len || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != plan->p.device)
-        return fail(AFSK_E_INVALID_ARG, "the plan was created on another device than the current one");
-    afsk::DemodArgs a;
-    a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
-    a.amp_end = amp_end_threshold;
-    a.out_bytes = out_bytes; a.out_stride = out_stride; a.out_nbytes = out_nbytes;
-    a.out_nbits = out_nbits; a.out_clock_idx = out_clock_idx; a.out_term_frame = out_term_frame;
-    a.out_status = out_status;
-    a.out_corrected = out_corrected;
-    a.out_margins = margin_stride > 0 ? out_margins : nullptr;
-    a.margin_stride = margin_stride;
-    hipError_t e = plan->p.launch(a, (hipStream_t)hip_stream);
-    return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_kernel (grouped)");
-}
-
-// The host entries see the bit_frames array: one value for all streams -> the uniform kernel;
-// several -> the grouped dispatch (index list + bit_frames live in `index_storage`, 2 n int32 of the
-// caller's device scratch; `keep` owns the side streams until the caller has synchronised).
-static int demod_device_auto(const int32_t* h_bit_frames, const int32_t* h_stream_len, const int16_t* samples, const int64_t* stream_offset,
-                             const int32_t* stream_len, const int32_t* d_bit_frames, int32_t amp_end_threshold,
-                             int32_t n_streams, uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes,
-                             int32_t* out_nbits, int32_t* out_clock_idx, int32_t* out_term_frame,
-                             int32_t* out_status, hipStream_t stream, int32_t* index_storage,
-                             std::unique_ptr<GroupPlan>& keep) {
-    (void)d_bit_frames;
-    bool same = true;
-    for (int32_t s = 1; s < n_streams && same; s++) same = h_bit_frames[s] == h_bit_frames[0];
-    // (one rate but ragged lengths: the plan, whose walk takes the longest streams first -- GroupPlan::bucket)
-    if (same && !GroupPlan::lengths_ragged(h_stream_len, n_streams))
-        return afsk_demod_batch_uniform(samples, stream_offset, stream_len, h_bit_frames[0], amp_end_threshold,
-                                        n_streams, out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx,
-                                        out_term_frame, out_status, nullptr, nullptr, 0, stream);
-    if (int rc = require_device()) return rc;
-    keep.reset(new GroupPlan());
-    keep->bucket(h_bit_frames, n_streams, h_stream_len);
-    hipError_t e = keep->materialise(index_storage, stream);
-    if (e != hipSuccess) return hip_fail(e, "grouped dispatch (index list)");
-    afsk::DemodArgs a;
-    a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
-    a.amp_end = amp_end_threshold;
-    a.out_bytes = out_bytes; a.out_stride = out_stride; a.out_nbytes = out_nbytes;
-    a.out_nbits = out_nbits; a.out_clock_idx = out_clock_idx; a.out_term_frame = out_term_frame;
-    a.out_status = out_status;
-    e = keep->launch(a, stream);
+    if (int rc = afsk::plan_on_current_device(plan->p.device)) return rc;
+    hipError_t e = plan->p.launch(o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold,
+                                                          plan->p.n), (hipStream_t)hip_stream);
     return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_kernel (grouped)");
 }
 
@@ -964,78 +992,26 @@ static int demod_batch_host_impl(const int16_t* samples, int64_t total_samples,
                                  int32_t n_streams, uint8_t* out_bytes, int32_t out_stride,
                                  int32_t* out_nbytes, int32_t* out_nbits, int32_t* out_clock_idx,
                                  int32_t* out_term_frame, int32_t* out_status) {
-    if (n_streams < 0 || out_stride < 0 || total_samples < 0)
+    const DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                         nullptr, nullptr, 0};
+    if (n_streams < 0 || o.negative() || total_samples < 0)
         return fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_streams == 0) return AFSK_OK;
-    if (!stream_offset || !stream_len || !bit_frames || !out_nbytes || !out_nbits ||
-        !out_clock_idx || !out_term_frame || !out_status || (!out_bytes && out_stride > 0) ||
-        (!samples && total_samples > 0))
+    if (!stream_offset || !stream_len || !bit_frames || o.missing() || (!samples && total_samples > 0))
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     for (int32_t s = 0; s < n_streams; s++) {
-        const int bf = bit_frames[s];
-        if (bf < 4 || (bf & 3) || 2 * bf >= AFSK_SYNC_WINDOW)
-            return fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 with 2*bf < 4096");
+        if (!bf_valid(bit_frames[s])) return fail_bit_frames();
         if (stream_len[s] < 0 || stream_len[s] > AFSK_MAX_STREAM_LEN || stream_offset[s] < 0 ||
             stream_offset[s] + stream_len[s] > total_samples)
             return fail(AFSK_E_INVALID_ARG, "stream outside the sample buffer (or longer than AFSK_MAX_STREAM_LEN)");
     }
-    if (int rc0 = require_device()) return rc0;
-
-    int rc = AFSK_OK;
-    const size_t n = (size_t)n_streams;
-    const size_t sample_bytes = (size_t)(total_samples > 0 ? total_samples : 1) * 2;
-    const size_t bytes_out = n * (size_t)out_stride;
-    // device layout: samples | meta = offsets, len, bf | out = 5 x int32 [n], bytes [n, stride]
-    const size_t o_meta = (sample_bytes + 255) & ~(size_t)255;
-    const size_t meta_bytes = n * 16;
-    const size_t o_out = o_meta + meta_bytes + n * 8;      // + the index list and bit_frames of a grouped dispatch
-    const size_t out_bytes_total = n * 20 + bytes_out;
-    const size_t total = o_out + out_bytes_total;
-    hipStream_t stream = nullptr;
-    {
-        hipError_t e = g_thread_stream.get(&stream);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithFlags (host-entry stream)");
-    }
-    ScratchLease lease;
-    std::unique_ptr<GroupPlan> plan;      // mixed rates: the host copy of the index list, alive until the final synchronise
-    char* d_all = nullptr;
-    // host staging: one H2D for the three index arrays, one D2H for all six outputs
-    std::vector<char> h_meta(meta_bytes), h_out(out_bytes_total);
-    std::memcpy(h_meta.data(), stream_offset, n * 8);
-    std::memcpy(h_meta.data() + n * 8, stream_len, n * 4);
-    std::memcpy(h_meta.data() + n * 12, bit_frames, n * 4);
-    {
-        hipError_t e = lease.acquire(total, &d_all);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc (host-entry scratch)");
-    }
-    if (total_samples > 0)
-        AFSK_HIP(hipMemcpyAsync(d_all, samples, (size_t)total_samples * 2, hipMemcpyHostToDevice, stream),
-                 "H2D samples");
-    AFSK_HIP(hipMemcpyAsync(d_all + o_meta, h_meta.data(), meta_bytes, hipMemcpyHostToDevice, stream),
-             "H2D stream index");
-    {
-        int32_t* i32 = (int32_t*)(d_all + o_out);
-        rc = demod_device_auto(bit_frames, stream_len, (const int16_t*)d_all, (const int64_t*)(d_all + o_meta),
-                               (const int32_t*)(d_all + o_meta + n * 8),
-                               (const int32_t*)(d_all + o_meta + n * 12), amp_end_threshold, n_streams,
-                               (uint8_t*)(d_all + o_out + n * 20), out_stride, i32, i32 + n, i32 + 2 * n,
-                               i32 + 3 * n, i32 + 4 * n, stream,
-                               (int32_t*)(d_all + o_meta + n * 16), plan);
-        if (rc != AFSK_OK) goto done;
-    }
-    AFSK_HIP(hipMemcpyAsync(h_out.data(), d_all + o_out, out_bytes_total, hipMemcpyDeviceToHost, stream),
-             "D2H results");
-    AFSK_HIP(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    std::memcpy(out_nbytes, h_out.data(), n * 4);
-    std::memcpy(out_nbits, h_out.data() + n * 4, n * 4);
-    std::memcpy(out_clock_idx, h_out.data() + n * 8, n * 4);
-    std::memcpy(out_term_frame, h_out.data() + n * 12, n * 4);
-    std::memcpy(out_status, h_out.data() + n * 16, n * 4);
-    if (bytes_out > 0) std::memcpy(out_bytes, h_out.data() + n * 20, bytes_out);
-done:
-    // nothing may still use the scratch or the staging vectors when they are released
-    if (rc != AFSK_OK) (void)hipStreamSynchronize(stream);
-    return rc;   // the lease returns (or frees) the device scratch
+    // the caller's buffer is the device layout already: one copy
+    return run_host_entry(total_samples, stream_offset, stream_len, bit_frames, amp_end_threshold, n_streams, o,
+                          /*block=*/false, [&](ScratchLease&, char* d_samples, hipStream_t stream) {
+        if (total_samples == 0) return AFSK_OK;
+        hipError_t e = hipMemcpyAsync(d_samples, samples, (size_t)total_samples * 2, hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? AFSK_OK : hip_fail(e, "H2D samples");
+    });
 }
 
 int afsk_demod_batch_host(const int16_t* samples, int64_t total_samples,
@@ -1074,57 +1050,31 @@ static int demod_streams_host_impl(const int16_t* const* streams, const int32_t*
                                    int32_t n_streams, uint8_t* out_bytes, int32_t out_stride,
                                    int32_t* out_nbytes, int32_t* out_nbits, int32_t* out_clock_idx,
                                    int32_t* out_term_frame, int32_t* out_status) {
-    if (n_streams < 0 || out_stride < 0) return fail(AFSK_E_INVALID_ARG, "negative size");
+    const DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                         nullptr, nullptr, 0};
+    if (n_streams < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_streams == 0) return AFSK_OK;
-    if (!streams || !stream_len || !bit_frames || !out_nbytes || !out_nbits || !out_clock_idx ||
-        !out_term_frame || !out_status || (!out_bytes && out_stride > 0))
+    if (!streams || !stream_len || !bit_frames || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     const size_t n = (size_t)n_streams;
     // device layout: every stream starts on a 16-byte boundary
-    std::vector<char> h_meta(n * 16);
-    int64_t* h_off = (int64_t*)h_meta.data();
+    std::vector<int64_t> h_off(n);
     int64_t total_samples = 0;
     for (size_t s = 0; s < n; s++) {
-        const int bf = bit_frames[s];
-        if (bf < 4 || (bf & 3) || 2 * bf >= AFSK_SYNC_WINDOW)
-            return fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 with 2*bf < 4096");
+        if (!bf_valid(bit_frames[s])) return fail_bit_frames();
         if (stream_len[s] < 0 || stream_len[s] > AFSK_MAX_STREAM_LEN || (stream_len[s] > 0 && !streams[s]))
             return fail(AFSK_E_INVALID_ARG, "bad stream length or null stream pointer");
         h_off[s] = total_samples;
         total_samples += ((int64_t)stream_len[s] + 7) & ~(int64_t)7;
     }
-    std::memcpy(h_meta.data() + n * 8, stream_len, n * 4);
-    std::memcpy(h_meta.data() + n * 12, bit_frames, n * 4);
-    if (int rc0 = require_device()) return rc0;
-
-    int rc = AFSK_OK;
-    const size_t sample_bytes = (size_t)(total_samples > 0 ? total_samples : 1) * 2;
-    const size_t bytes_out = n * (size_t)out_stride;
-    const size_t o_meta = (sample_bytes + 255) & ~(size_t)255;
-    const size_t o_out = o_meta + n * 16 + n * 8;          // + the index list and bit_frames of a grouped dispatch
-    const size_t out_bytes_total = n * 20 + bytes_out;
-    hipStream_t stream = nullptr;
-    {
-        hipError_t e = g_thread_stream.get(&stream);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithFlags (host-entry stream)");
-    }
-    {
+    return run_host_entry(total_samples, h_off.data(), stream_len, bit_frames, amp_end_threshold, n_streams, o,
+                          /*block=*/true, [&](ScratchLease& lease, char* d_samples, hipStream_t stream) {
         cpu_set_t cpus;                                   // the packing threads belong on the device's socket
         if (device_node_cpus(&cpus)) io_pool().confine_to(cpus);
-    }
-    ScratchLease lease;
-    std::unique_ptr<GroupPlan> plan;      // mixed rates: the host copy of the index list, alive until the final synchronise
-    char* d_all = nullptr;
-    char* stage[2];
-    hipEvent_t stage_free[2];
-    std::vector<char> h_out(out_bytes_total);
-    {
-        hipError_t e = lease.acquire(o_out + out_bytes_total, &d_all, /*block=*/true);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc (host-entry scratch)");
-        e = lease.staging(&stage[0], &stage[1], &stage_free[0], &stage_free[1]);
+        char* stage[2];
+        hipEvent_t stage_free[2];
+        hipError_t e = lease.staging(&stage[0], &stage[1], &stage_free[0], &stage_free[1]);
         if (e != hipSuccess) return hip_fail(e, "hipHostMalloc (staging)");
-    }
-    {
         // windows of the device sample range; pieces of streams are packed into a pinned window
         // by the copy threads while the previous window is on the wire
         const size_t all = (size_t)total_samples * 2;
@@ -1135,7 +1085,8 @@ static int demod_streams_host_impl(const int16_t* const* streams, const int32_t*
         for (size_t w0 = 0, k = 0; w0 < all; w0 += win, k++) {
             const size_t w1 = std::min(all, w0 + win);
             char* st = stage[k & 1];
-            if (k >= 2) AFSK_HIP(hipEventSynchronize(stage_free[k & 1]), "hipEventSynchronize");
+            if (k >= 2 && (e = hipEventSynchronize(stage_free[k & 1])) != hipSuccess)
+                return hip_fail(e, "hipEventSynchronize");
             jobs.clear();
             size_t moved = 0;
             for (size_t s = s_cur; s < n; s++) {
@@ -1147,34 +1098,12 @@ static int demod_streams_host_impl(const int16_t* const* streams, const int32_t*
                 moved += hi - lo;
             }
             parallel_copy(jobs, moved);
-            AFSK_HIP(hipMemcpyAsync(d_all + w0, st, w1 - w0, hipMemcpyHostToDevice, stream), "H2D samples");
-            AFSK_HIP(hipEventRecord(stage_free[k & 1], stream), "hipEventRecord");
+            if ((e = hipMemcpyAsync(d_samples + w0, st, w1 - w0, hipMemcpyHostToDevice, stream)) != hipSuccess)
+                return hip_fail(e, "H2D samples");
+            if ((e = hipEventRecord(stage_free[k & 1], stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
         }
-    }
-    AFSK_HIP(hipMemcpyAsync(d_all + o_meta, h_meta.data(), n * 16, hipMemcpyHostToDevice, stream),
-             "H2D stream index");
-    {
-        int32_t* i32 = (int32_t*)(d_all + o_out);
-        rc = demod_device_auto(bit_frames, stream_len, (const int16_t*)d_all, (const int64_t*)(d_all + o_meta),
-                               (const int32_t*)(d_all + o_meta + n * 8),
-                               (const int32_t*)(d_all + o_meta + n * 12), amp_end_threshold, n_streams,
-                               (uint8_t*)(d_all + o_out + n * 20), out_stride, i32, i32 + n, i32 + 2 * n,
-                               i32 + 3 * n, i32 + 4 * n, stream,
-                               (int32_t*)(d_all + o_meta + n * 16), plan);
-        if (rc != AFSK_OK) goto done;
-    }
-    AFSK_HIP(hipMemcpyAsync(h_out.data(), d_all + o_out, out_bytes_total, hipMemcpyDeviceToHost, stream),
-             "D2H results");
-    AFSK_HIP(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    std::memcpy(out_nbytes, h_out.data(), n * 4);
-    std::memcpy(out_nbits, h_out.data() + n * 4, n * 4);
-    std::memcpy(out_clock_idx, h_out.data() + n * 8, n * 4);
-    std::memcpy(out_term_frame, h_out.data() + n * 12, n * 4);
-    std::memcpy(out_status, h_out.data() + n * 16, n * 4);
-    if (bytes_out > 0) std::memcpy(out_bytes, h_out.data() + n * 20, bytes_out);
-done:
-    if (rc != AFSK_OK) (void)hipStreamSynchronize(stream);   // nothing may still read the staging windows
-    return rc;
+        return AFSK_OK;
+    });
 }
 
 int afsk_demod_streams_host(const int16_t* const* streams, const int32_t* stream_len,

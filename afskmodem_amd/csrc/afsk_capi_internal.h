@@ -1,0 +1,79 @@
+// afsk_capi_internal.h -- host-side pieces the C-ABI translation units share (afsk_capi.hip, afsk_split.hip):
+// the library's last-error slot, the exception barrier of the exported entries, and the argument checks and
+// output fields every demod entry has in common.  Host code only; not part of the installed interface.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <exception>
+#include <new>
+#include <string>
+
+#include "../../include/afsk_amd.h"
+
+namespace afsk {
+
+// store msg in the calling thread's afsk_last_error slot, return code
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
+// AFSK_E_NO_DEVICE unless a HIP device is visible
+int require_device();
+// AFSK_E_INVALID_ARG unless the current device is the one a plan was created on
+int plan_on_current_device(int plan_device);
+
+// Entries that allocate on the host (std::vector, std::thread): nothing may be thrown across the C boundary.
+template <class F>
+int no_throw(F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(AFSK_E_HOST, "out of host memory");
+    } catch (const std::exception& e) {
+        return fail(AFSK_E_HOST, std::string("host-side failure: ") + e.what());
+    } catch (...) {
+        return fail(AFSK_E_HOST, "host-side failure");
+    }
+}
+
+// The host side's bit_frames rule (a multiple of 4 with 2*bf < AFSK_SYNC_WINDOW) and its error.
+inline bool bf_valid(int32_t bf) { return bf >= 4 && (bf & 3) == 0 && 2 * bf < AFSK_SYNC_WINDOW; }
+inline int fail_bit_frames() {
+    return fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 with 2*bf < 4096");
+}
+
+// The output block of a demod entry: the five int32 arrays, the byte rows and the optional soft outputs.
+struct DemodOutputs {
+    uint8_t* bytes;
+    int32_t stride;
+    int32_t* nbytes;
+    int32_t* nbits;
+    int32_t* clock_idx;
+    int32_t* term_frame;
+    int32_t* status;
+    int32_t* corrected;
+    int32_t* margins;
+    int32_t margin_stride;
+
+    bool negative() const { return stride < 0 || margin_stride < 0; }
+    bool missing() const {
+        return !nbytes || !nbits || !clock_idx || !term_frame || !status || (!bytes && stride > 0);
+    }
+    // launch arguments (DemodArgs or SplitArgs) with the inputs every entry has and these outputs;
+    // the margins only with a positive margin_stride
+    template <class Args>
+    Args args(const int16_t* samples, const int64_t* stream_offset, const int32_t* stream_len, int32_t amp_end,
+              int32_t n_streams) const {
+        Args a{};
+        a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
+        a.amp_end = amp_end; a.n_streams = n_streams;
+        a.out_bytes = bytes; a.out_stride = stride; a.out_nbytes = nbytes; a.out_nbits = nbits;
+        a.out_clock_idx = clock_idx; a.out_term_frame = term_frame; a.out_status = status;
+        a.out_corrected = corrected;
+        a.out_margins = margin_stride > 0 ? margins : nullptr;
+        a.margin_stride = margin_stride;
+        return a;
+    }
+};
+
+}  // namespace afsk

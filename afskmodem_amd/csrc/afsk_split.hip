@@ -35,14 +35,10 @@
 #include <vector>
 
 #include "../../include/afsk_amd.h"
+#include "afsk_capi_internal.h"
 #include "afsk_demod_impl.h"
 
 namespace afsk {
-
-// the last-error slot of the library (afsk_capi.hip)
-int capi_fail(int code, const char* msg);
-int capi_hip_fail(hipError_t e, const char* what);
-int capi_require_device();
 
 constexpr int kSplitDefaultSymbols = 1024;          // 16 bitmap words, 80 KiB of samples at 1200 baud
 constexpr int kSplitSlots = 4;                      // pass buffers per wave (3 passes in flight)
@@ -366,15 +362,14 @@ struct SplitLayout {
 
 static int split_layout(const int32_t* len, const int32_t* bf, int32_t n, int32_t segment_symbols, SplitLayout& L,
                         std::vector<int64_t>* word_off, std::vector<int32_t>* seg_stream, std::vector<int32_t>* seg_k0) {
-    if (n < 0 || segment_symbols < 0) return capi_fail(AFSK_E_INVALID_ARG, "negative size");
-    if (n > 0 && (!len || !bf)) return capi_fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (segment_symbols % 64) return capi_fail(AFSK_E_INVALID_ARG, "segment_symbols must be a multiple of 64 (0 = default)");
+    if (n < 0 || segment_symbols < 0) return fail(AFSK_E_INVALID_ARG, "negative size");
+    if (n > 0 && (!len || !bf)) return fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (segment_symbols % 64) return fail(AFSK_E_INVALID_ARG, "segment_symbols must be a multiple of 64 (0 = default)");
     L.seg_symbols = segment_symbols ? segment_symbols : kSplitDefaultSymbols;
     for (int32_t s = 0; s < n; s++) {
-        if (bf[s] < 4 || (bf[s] & 3) || 2 * bf[s] >= AFSK_SYNC_WINDOW)
-            return capi_fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 with 2*bf < 4096");
+        if (!bf_valid(bf[s])) return fail_bit_frames();
         if (len[s] < 0 || len[s] > AFSK_MAX_STREAM_LEN)
-            return capi_fail(AFSK_E_INVALID_ARG, "stream_len outside 0 ... AFSK_MAX_STREAM_LEN");
+            return fail(AFSK_E_INVALID_ARG, "stream_len outside 0 ... AFSK_MAX_STREAM_LEN");
     }
     // segments of the 1200-baud streams first (their own stage-B kernel), then the rest, each in stream order
     if (word_off) word_off->assign((size_t)n, 0);
@@ -394,7 +389,7 @@ static int split_layout(const int32_t* len, const int32_t* bf, int32_t n, int32_
         L.total_words += (nsym + 63) / 64;
     }
     if (L.n_segments > std::numeric_limits<int32_t>::max())
-        return capi_fail(AFSK_E_INVALID_ARG, "more than 2^31 - 1 segments: use a larger segment_symbols");
+        return fail(AFSK_E_INVALID_ARG, "more than 2^31 - 1 segments: use a larger segment_symbols");
     L.ci_bytes = ((4 * (int64_t)n + 255) / 256) * 256;
     L.scratch_bytes = L.ci_bytes + 16 * L.total_words;
     return AFSK_OK;
@@ -430,18 +425,18 @@ int afsk_split_scratch_bytes(const int32_t* stream_len_host, const int32_t* bit_
 
 int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_frames_host, int32_t n_streams,
                            int32_t segment_symbols, afsk_split_plan** out_plan) {
-    if (!out_plan) return afsk::capi_fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (!out_plan) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     *out_plan = nullptr;
-    try {
+    return afsk::no_throw([&] {
         std::vector<int64_t> word_off;
         std::vector<int32_t> seg_stream, seg_k0;
         std::unique_ptr<afsk_split_plan> pl(new afsk_split_plan());
         if (int rc = afsk::split_layout(stream_len_host, bit_frames_host, n_streams, segment_symbols, pl->L, &word_off,
                                         &seg_stream, &seg_k0))
             return rc;
-        if (int rc = afsk::capi_require_device()) return rc;
+        if (int rc = afsk::require_device()) return rc;
         hipError_t e = hipGetDevice(&pl->device);
-        if (e != hipSuccess) return afsk::capi_hip_fail(e, "afsk_split_plan_create (hipGetDevice)");
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_split_plan_create (hipGetDevice)");
         pl->n = n_streams;
         int32_t n40 = 0;
         for (size_t g = 0; g < seg_stream.size(); g++) n40 += bit_frames_host[seg_stream[g]] == 40;
@@ -461,9 +456,9 @@ int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_fr
             std::memcpy(h.data() + o_k0, seg_k0.data(), 4 * ns);
         }
         e = hipMalloc(&pl->d, bytes);
-        if (e != hipSuccess) { pl->d = nullptr; return afsk::capi_hip_fail(e, "afsk_split_plan_create (hipMalloc)"); }
+        if (e != hipSuccess) { pl->d = nullptr; return afsk::hip_fail(e, "afsk_split_plan_create (hipMalloc)"); }
         e = hipMemcpy(pl->d, h.data(), bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return afsk::capi_hip_fail(e, "afsk_split_plan_create (upload)");
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_split_plan_create (upload)");
         uint8_t* d = static_cast<uint8_t*>(pl->d);
         pl->bf = reinterpret_cast<int32_t*>(d);
         pl->plen = reinterpret_cast<int32_t*>(d + o_plen);
@@ -472,16 +467,12 @@ int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_fr
         pl->seg_k0 = reinterpret_cast<int32_t*>(d + o_k0);
         *out_plan = pl.release();
         return AFSK_OK;
-    } catch (const std::bad_alloc&) {
-        return afsk::capi_fail(AFSK_E_HOST, "out of host memory");
-    } catch (...) {
-        return afsk::capi_fail(AFSK_E_HOST, "host-side failure");
-    }
+    });
 }
 
 int afsk_split_plan_info(const afsk_split_plan* plan, int32_t* out_n_streams, int32_t* out_n_segments,
                          int64_t* out_scratch_bytes) {
-    if (!plan) return afsk::capi_fail(AFSK_E_INVALID_ARG, "null plan");
+    if (!plan) return afsk::fail(AFSK_E_INVALID_ARG, "null plan");
     if (out_n_streams) *out_n_streams = plan->n;
     if (out_n_segments) *out_n_segments = (int32_t)plan->L.n_segments;
     if (out_scratch_bytes) *out_scratch_bytes = plan->L.scratch_bytes;
@@ -498,51 +489,41 @@ int afsk_demod_batch_split(const afsk_split_plan* plan, const int16_t* samples, 
                            uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes, int32_t* out_nbits,
                            int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status,
                            int32_t* out_corrected, int32_t* out_margins, int32_t margin_stride, void* hip_stream) {
-    if (!plan) return afsk::capi_fail(AFSK_E_INVALID_ARG, "null plan");
-    if (out_stride < 0 || margin_stride < 0) return afsk::capi_fail(AFSK_E_INVALID_ARG, "negative size");
+    const afsk::DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                               out_corrected, out_margins, margin_stride};
+    if (!plan) return afsk::fail(AFSK_E_INVALID_ARG, "null plan");
+    if (o.negative()) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
     if (plan->n == 0) return AFSK_OK;
-    if (!samples || !stream_offset || !stream_len || !out_nbytes || !out_nbits || !out_clock_idx ||
-        !out_term_frame || !out_status || (!out_bytes && out_stride > 0) || !d_scratch)
-        return afsk::capi_fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (int rc = afsk::capi_require_device()) return rc;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
-        return afsk::capi_fail(AFSK_E_INVALID_ARG, "the plan was created on another device than the current one");
-    afsk::SplitArgs a;
-    a.samples = samples; a.stream_offset = stream_offset; a.stream_len = stream_len;
+    if (!samples || !stream_offset || !stream_len || o.missing() || !d_scratch)
+        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(plan->device)) return rc;
+    afsk::SplitArgs a = o.args<afsk::SplitArgs>(samples, stream_offset, stream_len, amp_end_threshold, plan->n);
     a.bit_frames = plan->bf; a.plan_len = plan->plen; a.word_off = plan->word_off;
     a.seg_stream = plan->seg_stream; a.seg_k0 = plan->seg_k0;
-    a.seg_begin = 0; a.seg_end = 0;
     a.seg_symbols = plan->L.seg_symbols;
-    a.n_streams = plan->n;
-    a.amp_end = amp_end_threshold;
     uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
     a.ci = reinterpret_cast<int32_t*>(scratch);
     a.dec = reinterpret_cast<unsigned long long*>(scratch + plan->L.ci_bytes);
     a.loud = a.dec + plan->L.total_words;
-    a.out_bytes = out_bytes; a.out_stride = out_stride; a.out_nbytes = out_nbytes; a.out_nbits = out_nbits;
-    a.out_clock_idx = out_clock_idx; a.out_term_frame = out_term_frame; a.out_status = out_status;
-    a.out_corrected = out_corrected;
-    a.out_margins = margin_stride > 0 ? out_margins : nullptr;
-    a.margin_stride = margin_stride;
     const hipStream_t st = (hipStream_t)hip_stream;
     // A, B (1200 baud), B (every other rate), C: strictly in order on the caller's stream
     hipLaunchKernelGGL(afsk::split_clock_kernel, dim3(plan->n), dim3(64), 0, st, a);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return afsk::capi_hip_fail(e, "launch split_clock_kernel");
+    if (e != hipSuccess) return afsk::hip_fail(e, "launch split_clock_kernel");
     const int32_t nseg = (int32_t)plan->L.n_segments;
     if (plan->n_seg40 > 0) {
         a.seg_begin = 0; a.seg_end = plan->n_seg40;
         hipLaunchKernelGGL(afsk::split_segment_40_kernel, dim3(plan->n_seg40), dim3(64), 0, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return afsk::capi_hip_fail(e, "launch split_segment_40_kernel");
+        if ((e = hipGetLastError()) != hipSuccess) return afsk::hip_fail(e, "launch split_segment_40_kernel");
     }
     if (nseg > plan->n_seg40) {
         a.seg_begin = plan->n_seg40; a.seg_end = nseg;
         hipLaunchKernelGGL(afsk::split_segment_rt_kernel, dim3((nseg - plan->n_seg40 + 3) / 4), dim3(256), 0, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return afsk::capi_hip_fail(e, "launch split_segment_rt_kernel");
+        if ((e = hipGetLastError()) != hipSuccess) return afsk::hip_fail(e, "launch split_segment_rt_kernel");
     }
     hipLaunchKernelGGL(afsk::split_finish_kernel, dim3((plan->n + 3) / 4), dim3(256), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return afsk::capi_hip_fail(e, "launch split_finish_kernel");
+    if ((e = hipGetLastError()) != hipSuccess) return afsk::hip_fail(e, "launch split_finish_kernel");
     return AFSK_OK;
 }
 

@@ -259,6 +259,11 @@ class SoundOutput:
 # ------------------------------------------------------------------ Receiver
 
 
+def _text_or_bytes(data: bytes, string: bool):
+    """A payload as ``receive`` / ``load`` return it (ref:422-429): text when ``string``, but no data stays b""."""
+    return data.decode("utf-8") if (string and data != b"") else data
+
+
 def _check_decodable(bit_frames: int, mark_len: int, space_len: int, n_frames: int) -> None:
     """Raise what the reference raises when it reaches the sync search (ref:322-337)."""
     if n_frames < SYNC_WINDOW:
@@ -395,10 +400,7 @@ class Receiver:
             torch.cuda.synchronize()
         else:
             res = batch.demod_host_arrays(arrays, self.__bit_frames, self.__amp_end_threshold)
-        out = []
-        for data in res.payloads():
-            out.append(data.decode("utf-8") if (string and data != b"") else data)
-        return out
+        return [_text_or_bytes(data, string) for data in res.payloads()]
 
     def load_batch(self, filenames, string: bool = False, split: bool = False):
         """``load`` for many files: parallel .wav ingest into one device buffer
@@ -419,7 +421,7 @@ class Receiver:
             res = batch.demod_batch(samples, off, ln, self.__bit_frames, self.__amp_end_threshold,
                                     out_stride=stride, stream_len_host=ln.cpu().numpy())
         torch.cuda.synchronize()
-        return [d.decode("utf-8") if (string and d != b"") else d for d in res.payloads()]
+        return [_text_or_bytes(data, string) for data in res.payloads()]
 
     def __demod_split(self, samples, off, ln, max_len):
         from . import batch
@@ -450,7 +452,7 @@ class Receiver:
                                 out_stride=stride, stream_len_host=b_len.cpu().numpy())
         torch.cuda.synchronize()
         for o, data in zip(owner.cpu().tolist(), res.payloads()):
-            out[o].append(data.decode("utf-8") if (string and data != b"") else data)
+            out[o].append(_text_or_bytes(data, string))
         return out
 
 
@@ -484,7 +486,7 @@ def load_batch(receivers, filenames, string: bool = False):
                                 stream_len_host=lens[idx])
         torch.cuda.synchronize()
         for i, data in zip(idx, res.payloads()):
-            out[int(i)] = data.decode("utf-8") if (string and data != b"") else data
+            out[int(i)] = _text_or_bytes(data, string)
     return out
 
 

@@ -153,7 +153,7 @@ int afsk_demod_batch_uniform(const int16_t *samples, const int64_t *stream_offse
  * independent, :354-381).  The plan buckets the streams by bit_frames once (a stable sort on the host, one
  * upload of an index list + the bit_frames, 8 bytes per stream); afsk_demod_batch_grouped then decodes the
  * batch with ONE kernel launch that walks the streams bucket by bucket (inside windows of 4096 consecutive streams,
- * so that the streams in flight stay close in memory), so that the wavefronts resident on a
+ * 8192 for a ragged plan, so that the streams in flight stay close in memory), so that the wavefronts resident on a
  * compute unit run the same rate's code: 3 - 12 % faster than stream order when four or more rates are mixed
  * (below that the plan keeps stream order; one rate: the kernel of afsk_demod_batch_uniform).  Nothing but a
  * kernel launch: asynchronous on hip_stream like every device entry, safe inside a stream capture, and
@@ -169,8 +169,9 @@ int afsk_demod_batch_uniform(const int16_t *samples, const int64_t *stream_offse
  *                           array [n] of the lengths the launches will be given (NULL = afsk_group_plan_create).  One
  *                           wavefront decodes one stream whatever its length and a workgroup of four keeps its share of
  *                           a CU until its longest stream ends, so when the lengths differ (shortest below 3/4 of the
- *                           longest) the walk takes, inside every window of 4096 consecutive streams and every rate,
- *                           the LONGEST streams first -- also for a one-rate batch, whose uniform kernel then walks the
+ *                           longest) the walk takes, inside every window of 8192 consecutive streams (twice the
+ *                           window of a rate-only plan; AFSK_GROUP_WINDOW, when set, is both) and every rate, the
+ *                           LONGEST streams first -- also for a one-rate batch, whose uniform kernel then walks the
  *                           list.  Results do not depend on it (same outputs at the same stream numbers); lengths that
  *                           differ from those given later only cost speed.  The host entries do this by themselves.
  *  afsk_group_plan_info     n_streams, number of buckets, and per bucket (first `cap` of them, in launch
