@@ -104,6 +104,21 @@ SPLIT_SIGNATURES = {
 }
 
 
+# The live receiver (afsk_live_*), bound by lib() from a table of its own for the same reason.
+LIVE_SIGNATURES = {
+    "afsk_live_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i32p, _i64p]),
+    "afsk_live_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_void_p)]),
+    "afsk_live_info": (C.c_int, [C.c_void_p, _i32p, _i32p, _i64p]),
+    "afsk_live_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "afsk_live_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afsk_live_destroy": (C.c_int, [C.c_void_p]),
+}
+LIVE_OPEN_END, LIVE_OVERFLOW = 1, 2          # AFSK_LIVE_* flags
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -113,7 +128,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with afskmodem_amd/csrc/build.sh "
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

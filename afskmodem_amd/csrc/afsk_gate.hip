@@ -20,6 +20,27 @@ constexpr int kListenBlock = 2048;   // ref:189, 209, 310
 // with the non-temporal policy: every byte of a capture is read exactly once.
 typedef uint32_t vec16 __attribute__((ext_vector_type(4), aligned(2)));
 
+// sum |x| over the 2048 samples one wavefront holds as v[4] (lane l: samples 512 j + 8 l ... + 7 of load j):
+// v_sad_u16 accumulation (ref:94-98), then the wave sum with DPP (row_shr 1/2/4/8, row_bcast:15 / :31); lane 63
+// ends up with the total (__shfl_xor would be six ds_bpermute round trips).  amp = total >> 11 = int(sum / 2048).
+// Shared by block_amp_kernel and live_gate_kernel (afsk_live.hip).
+__device__ __forceinline__ int block_abs_sum(const vec16 (&v)[4]) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            acc = __builtin_amdgcn_sad_u16(v[j][k] ^ 0x80008000u, 0x80008000u, acc);   // sum |x|
+    int t = (int)acc;
+    t += __builtin_amdgcn_update_dpp(0, t, 0x111, 0xf, 0xf, true);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x112, 0xf, 0xf, true);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x114, 0xf, 0xf, true);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x118, 0xf, 0xf, true);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x142, 0xa, 0xf, false);
+    t += __builtin_amdgcn_update_dpp(0, t, 0x143, 0xc, 0xf, false);
+    return t;
+}
+
 __global__ __launch_bounds__(256) void block_amp_kernel(GateArgs a) {
     const int lane = threadIdx.x & 63;
     // (xcd_block: the 32 amplitudes of one 128-byte line are written by 8 workgroups -- let them sit on ONE XCD, so that
@@ -35,25 +56,11 @@ __global__ __launch_bounds__(256) void block_amp_kernel(GateArgs a) {
     const int32_t nb = len / kListenBlock;
     if (b >= nb) return;
     const int16_t* src = a.samples + a.stream_offset[s] + (int64_t)b * kListenBlock;
-    uint32_t acc = 0;
     vec16 v[4];
 #pragma unroll
     for (int j = 0; j < 4; j++)
         v[j] = __builtin_nontemporal_load(reinterpret_cast<const vec16*>(src + 512 * j + 8 * lane));
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            acc = __builtin_amdgcn_sad_u16(v[j][k] ^ 0x80008000u, 0x80008000u, acc);   // sum |x|
-    // wave sum with DPP (row_shr 1/2/4/8, row_bcast:15 / :31): lane 63 ends up with the total;
-    // __shfl_xor would be six ds_bpermute round trips
-    int t = (int)acc;
-    t += __builtin_amdgcn_update_dpp(0, t, 0x111, 0xf, 0xf, true);
-    t += __builtin_amdgcn_update_dpp(0, t, 0x112, 0xf, 0xf, true);
-    t += __builtin_amdgcn_update_dpp(0, t, 0x114, 0xf, 0xf, true);
-    t += __builtin_amdgcn_update_dpp(0, t, 0x118, 0xf, 0xf, true);
-    t += __builtin_amdgcn_update_dpp(0, t, 0x142, 0xa, 0xf, false);
-    t += __builtin_amdgcn_update_dpp(0, t, 0x143, 0xc, 0xf, false);
+    const int t = block_abs_sum(v);
     if (lane == 63) a.block_amp[(int64_t)s * a.max_blocks + b] = (int32_t)((uint32_t)t >> 11);    // int(sum/2048)
 }
 
@@ -130,3 +137,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // unit: build.sh compiles a fixed list of files, and the hashed afsk_demod* sources and afsk_capi.hip (which the CPU
 // stub-runtime test builds without device code) must stay as they are.
 #include "afsk_split.hip"
+// The live receiver (afsk_live_*: stateful chunked gate + demodulation of the bursts a push closes), for the same
+// reason.
+#include "afsk_live.hip"

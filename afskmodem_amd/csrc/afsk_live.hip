@@ -1,0 +1,354 @@
+// afsk_live.hip -- the live receiver (afsk_live_*, include/afsk_amd.h): Receiver.receive (afskmodem.py:299-319,
+// 402-417) for many channels fed chunk by chunk, with nothing but device state carried from one push to the next.
+//
+// A push is two launches, in order on the caller's stream (a captured graph of them is a linear chain):
+//   live_gate_kernel     one wave per channel: walks the push's whole 2048-sample blocks through gate_scan_kernel's
+//                        state machine (discard one block, wait for amp > amp_start, record through the first
+//                        amp < amp_end), stores recorded blocks from registers into the channel's record row, and
+//                        lays every burst the push closes out as a fixed demodulator slot (row offset + length).
+//   demod_uniform_kernel afsk::launch_demod_uniform over n_channels * slots slots, reading the bursts in place
+//                        (length 0 = unused or overflowed slot: status TOO_SHORT, nothing read).
+//
+// Per channel the device keeps (LiveChan) the gate mode, the stream position, the open burst's start, length and
+// row offset, and a 2048-sample carry with the partial block at the end of the stream.  Row layout: the open
+// burst's prefix at the front, then every block recorded in this push, bursts back to back; at the start of the
+// next push a burst that opened in the previous one (behind bursts that closed there) is moved to the front -- at
+// most one push's blocks, front to back (the source lies at least one block above the destination).  So a row needs
+// cap_blocks (the longest burst that is stored) + k_blocks (the most blocks one push walks) blocks.
+//
+// This file is compiled as part of afsk_gate.hip's translation unit (see the #include at its end): it uses that
+// file's kListenBlock, vec16 and block_abs_sum.
+#include <algorithm>
+#include <memory>
+#include <new>
+
+#include "../../include/afsk_amd.h"
+#include "afsk_capi_internal.h"
+
+namespace afsk {
+
+struct LiveChan {           // 32 bytes per channel
+    int64_t pos;            // samples of the current stream pushed so far; the carry holds the last pos & 2047
+    int64_t rec_start;      // open burst: stream index of its first sample
+    int64_t rec_len;        // open burst: samples recorded so far (whole blocks; may exceed the row's capacity)
+    int32_t mode;           // 0 = discard the next block, 1 = wait for a start block, 2 = recording
+    int32_t head;           // open burst: row offset of its first stored sample (0 unless it opened in the
+                            // previous push behind bursts that closed there; moved to 0 by the next push)
+};
+static_assert(sizeof(LiveChan) == 32, "LiveChan layout");
+
+// burst_len is int32: a burst recorded for longer than this (about 12 hours) is reported with this length
+constexpr int64_t kLiveLenMax = (int64_t)0x7fffffff & ~(int64_t)(kListenBlock - 1);
+
+struct LiveLayout {
+    int64_t n = 0;
+    int64_t cap_blocks = 0;     // blocks of a burst that are stored: max_burst_len / 2048
+    int64_t k_blocks = 0;       // most blocks one push walks: (2047 + max_chunk_len) / 2048
+    int64_t slots = 0;          // slots per channel and push: 1 + k_blocks / 3
+    int64_t row_len = 0;        // samples per record row: (cap_blocks + k_blocks) * 2048
+    int64_t o_carry = 0, o_slot_off = 0, o_slot_len = 0, o_rows = 0, bytes = 0;
+};
+
+inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+__host__ __device__ inline int64_t min64(int64_t x, int64_t y) { return x < y ? x : y; }
+
+// The state allocation: LiveChan [n] | carry int16 [n, 2048] | slot offset int64 [n, slots] | slot length int32
+// [n, slots] | record rows int16 [n, row_len] | 256 spare bytes; every part 256-byte aligned.
+inline int live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chunk_len, LiveLayout& L) {
+    if (n_channels < 1) return fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
+    if (max_burst_len < 2 * kListenBlock || max_burst_len > kMaxStreamLen)
+        return fail(AFSK_E_INVALID_ARG, "max_burst_len must lie in 4096 ... AFSK_MAX_STREAM_LEN");
+    if (max_chunk_len < 1 || max_chunk_len > kMaxStreamLen)
+        return fail(AFSK_E_INVALID_ARG, "max_chunk_len must lie in 1 ... AFSK_MAX_STREAM_LEN");
+    L.n = n_channels;
+    L.cap_blocks = max_burst_len / kListenBlock;
+    L.k_blocks = ((int64_t)kListenBlock - 1 + max_chunk_len) / kListenBlock;
+    L.slots = 1 + L.k_blocks / 3;
+    L.row_len = (L.cap_blocks + L.k_blocks) * kListenBlock;
+    if (L.n * L.slots > 0x7fffffffll)
+        return fail(AFSK_E_INVALID_ARG, "n_channels * slots exceeds the demodulator's int32 stream count");
+    L.o_carry = align256(32 * L.n);
+    L.o_slot_off = L.o_carry + align256(2 * kListenBlock * L.n);
+    L.o_slot_len = L.o_slot_off + align256(8 * L.n * L.slots);
+    L.o_rows = L.o_slot_len + align256(4 * L.n * L.slots);
+    L.bytes = L.o_rows + align256(2 * L.row_len * L.n) + 256;   // (n < 2^31, row_len < 2^31: no overflow)
+    return AFSK_OK;
+}
+
+struct LiveArgs {
+    LiveChan* chan;
+    int16_t* carry;
+    int64_t* slot_off;          // demodulator slots: offset from `rows`, length (0 = nothing to decode)
+    int32_t* slot_len;
+    int16_t* rows;
+    const int16_t* chunk;
+    int64_t chunk_stride;
+    int64_t row_len;
+    int64_t cap;                // cap_blocks * 2048: samples of a burst that are stored
+    int32_t chunk_len;
+    int32_t flush;
+    int32_t n;
+    int32_t slots;
+    int32_t amp_start;
+    int32_t amp_end;
+    int32_t* out_n_closed;
+    int64_t* out_burst_start;
+    int32_t* out_burst_len;
+    int32_t* out_flags;
+};
+
+// one block of the push: samples [b * 2048 - cl, + 2048) of the chunk (b >= 1, or b == 0 without a carry)
+__device__ __forceinline__ void live_load_chunk_block(vec16 (&v)[4], const int16_t* p, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = __builtin_nontemporal_load(reinterpret_cast<const vec16*>(p + 512 * j + 8 * lane));
+}
+
+// block 0 of a push that starts with cl carried samples: carry[0, cl) then chunk[0, 2048 - cl), sample by sample
+// (once per push and channel)
+__device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16_t* carry, const int16_t* src, int cl,
+                                                      int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = 512 * j + 8 * lane + 2 * k;
+            const uint16_t lo = (uint16_t)(i < cl ? carry[i] : src[i - cl]);
+            const uint16_t hi = (uint16_t)(i + 1 < cl ? carry[i + 1] : src[i + 1 - cl]);
+            v[j][k] = (uint32_t)lo | ((uint32_t)hi << 16);
+        }
+}
+
+__global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= a.n) return;
+    LiveChan st = a.chan[c];
+    int16_t* row = a.rows + (int64_t)c * a.row_len;
+    int16_t* carry = a.carry + (int64_t)c * kListenBlock;
+    const int16_t* src = a.chunk + (int64_t)c * a.chunk_stride;
+    const int64_t slot0 = (int64_t)c * a.slots;
+
+    // the open burst's stored prefix goes to the row front (it opened in the previous push behind closed bursts,
+    // so it is at most one push of blocks, and head >= 2048: copying block by block front to back never overwrites
+    // a block that is still to be read)
+    int64_t wp = 0;             // row offset of the next stored block
+    int64_t brow = 0;           // row offset of the open burst
+    if (st.mode == 2) {
+        const int64_t stored = min64(st.rec_len, a.cap);
+        if (st.head > 0)
+            for (int64_t o = 0; o < stored; o += kListenBlock) {
+                vec16 v[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = *reinterpret_cast<const vec16*>(row + st.head + o + 512 * j + 8 * lane);
+#pragma unroll
+                for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + o + 512 * j + 8 * lane) = v[j];
+            }
+        wp = stored;
+    }
+
+    const int cl = (int)(st.pos & (kListenBlock - 1));             // carried samples
+    const int32_t nblk = (int32_t)(((int64_t)cl + a.chunk_len) / kListenBlock);
+    const int64_t bpos0 = st.pos - cl;                              // stream index of block 0
+    int k = 0;                                                      // slots used
+    auto report = [&](int32_t flags) {
+        const bool ovf = st.rec_len > a.cap;
+        if (k < a.slots && lane == 0) {                             // (k < slots always holds: afsk_live_layout)
+            const int64_t i = slot0 + k;
+            a.out_burst_start[i] = st.rec_start;
+            a.out_burst_len[i] = (int32_t)min64(st.rec_len, kLiveLenMax);
+            a.out_flags[i] = flags | (ovf ? AFSK_LIVE_OVERFLOW : 0);
+            a.slot_off[i] = (int64_t)c * a.row_len + brow;
+            a.slot_len[i] = ovf ? 0 : (int32_t)st.rec_len;
+        }
+        k++;
+    };
+    vec16 cur[4], nxt[4];
+    if (nblk > 0) {
+        if (cl > 0) live_load_carry_block(cur, carry, src, cl, lane);
+        else live_load_chunk_block(cur, src, lane);
+    }
+    for (int32_t b = 0; b < nblk; b++) {
+        if (b + 1 < nblk) live_load_chunk_block(nxt, src + (int64_t)(b + 1) * kListenBlock - cl, lane);   // next block in flight
+        const int32_t amp = (int32_t)((uint32_t)__builtin_amdgcn_readlane(block_abs_sum(cur), 63) >> 11);
+        int ev = 0;                                                 // 1 = record the block, 2 = record it and close
+        if (st.mode == 0) {
+            st.mode = 1;                                            // ref:303
+        } else if (st.mode == 1) {
+            if (amp > a.amp_start) {                                // ref:306-309
+                st.mode = 2;
+                st.rec_start = bpos0 + (int64_t)b * kListenBlock;
+                st.rec_len = 0;
+                brow = wp;
+                ev = 1;
+            }
+        } else {
+            ev = amp < a.amp_end ? 2 : 1;                           // ref:316-318 (block included)
+        }
+        if (ev) {
+            // stored while the burst fits its capacity (and, as a guard, the row)
+            if (st.rec_len < a.cap && wp + kListenBlock <= a.row_len) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + wp + 512 * j + 8 * lane) = cur[j];
+                wp += kListenBlock;
+            }
+            st.rec_len += kListenBlock;
+            if (ev == 2) {
+                report(0);
+                st.mode = 0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) cur[j] = nxt[j];
+    }
+
+    if (a.flush) {
+        if (st.mode == 2) report(AFSK_LIVE_OPEN_END);               // gate_scan_kernel's open-ended burst
+        st = LiveChan{};                                            // a new stream; the partial block is dropped
+    } else {
+        // the tail (< 2048 samples) to the carry: carry[i] = stream sample nblk * 2048 + i for i < tail; without a
+        // whole block in this push only [cl, tail) is new
+        const int32_t tail = (int32_t)(((int64_t)cl + a.chunk_len) & (kListenBlock - 1));
+        const int64_t base = (int64_t)nblk * kListenBlock - cl;
+        for (int i = (nblk == 0 ? cl : 0) + lane; i < tail; i += 64) carry[i] = src[base + i];
+        st.pos += a.chunk_len;
+        st.head = st.mode == 2 ? (int32_t)brow : 0;
+    }
+    for (int i = k + lane; i < a.slots; i += 64) {                  // unused slots: length 0, nothing to decode
+        a.out_burst_start[slot0 + i] = 0;
+        a.out_burst_len[slot0 + i] = 0;
+        a.out_flags[slot0 + i] = 0;
+        a.slot_off[slot0 + i] = 0;
+        a.slot_len[slot0 + i] = 0;
+    }
+    if (lane == 0) {
+        a.out_n_closed[c] = k < a.slots ? k : a.slots;
+        a.chan[c] = st;
+    }
+}
+
+__global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const uint8_t* mask, int32_t n) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < n && (!mask || mask[c])) chan[c] = LiveChan{};
+}
+
+}  // namespace afsk
+
+struct afsk_live {
+    int device = -1;
+    afsk::LiveLayout L;
+    int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;
+    void* d = nullptr;
+    ~afsk_live() {
+        if (d) (void)hipFree(d);
+    }
+};
+
+extern "C" {
+
+int afsk_live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chunk_len, int32_t* out_slots,
+                     int64_t* out_state_bytes) {
+    afsk::LiveLayout L;
+    if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, L)) return rc;
+    if (out_slots) *out_slots = (int32_t)L.slots;
+    if (out_state_bytes) *out_state_bytes = L.bytes;
+    return AFSK_OK;
+}
+
+int afsk_live_create(int32_t n_channels, int32_t bit_frames, int32_t amp_start_threshold, int32_t amp_end_threshold,
+                     int32_t max_burst_len, int32_t max_chunk_len, afsk_live** out) {
+    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    *out = nullptr;
+    if (!afsk::bf_valid(bit_frames)) return afsk::fail_bit_frames();
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live> lv(new afsk_live());
+        if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, lv->L)) return rc;
+        if (int rc = afsk::require_device()) return rc;
+        hipError_t e = hipGetDevice(&lv->device);
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_create (hipGetDevice)");
+        lv->bit_frames = bit_frames;
+        lv->amp_start = amp_start_threshold;
+        lv->amp_end = amp_end_threshold;
+        lv->max_chunk_len = max_chunk_len;
+        e = hipMalloc(&lv->d, (size_t)lv->L.bytes);
+        if (e != hipSuccess) { lv->d = nullptr; return afsk::hip_fail(e, "afsk_live_create (hipMalloc)"); }
+        // only the channel states need a value: the carry, slots and rows are written before they are read
+        e = hipMemsetAsync(lv->d, 0, (size_t)lv->L.o_carry, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_create (zero the state)");
+        *out = lv.release();
+        return AFSK_OK;
+    });
+}
+
+int afsk_live_info(const afsk_live* live, int32_t* out_n_channels, int32_t* out_slots, int64_t* out_state_bytes) {
+    if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
+    if (out_n_channels) *out_n_channels = (int32_t)live->L.n;
+    if (out_slots) *out_slots = (int32_t)live->L.slots;
+    if (out_state_bytes) *out_state_bytes = live->L.bytes;
+    return AFSK_OK;
+}
+
+int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
+                   int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
+                   uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes, int32_t* out_nbits,
+                   int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status, int32_t* out_corrected,
+                   int32_t* out_margins, int32_t margin_stride, void* hip_stream) {
+    const afsk::DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
+                               out_corrected, out_margins, margin_stride};
+    if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
+    if (chunk_len < 0 || chunk_row_stride < 0 || o.negative()) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
+    if (chunk_len > live->max_chunk_len)
+        return afsk::fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
+    if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
+        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(live->device)) return rc;
+    const afsk::LiveLayout& L = live->L;
+    uint8_t* d = static_cast<uint8_t*>(live->d);
+    afsk::LiveArgs g{};
+    g.chan = reinterpret_cast<afsk::LiveChan*>(d);
+    g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
+    g.slot_off = reinterpret_cast<int64_t*>(d + L.o_slot_off);
+    g.slot_len = reinterpret_cast<int32_t*>(d + L.o_slot_len);
+    g.rows = reinterpret_cast<int16_t*>(d + L.o_rows);
+    g.chunk = chunk_len > 0 ? chunk : g.rows;        // (T = 0: never read)
+    g.chunk_stride = chunk_len > 0 ? chunk_row_stride : 0;
+    g.row_len = L.row_len;
+    g.cap = L.cap_blocks * afsk::kListenBlock;
+    g.chunk_len = chunk_len;
+    g.flush = flush != 0;
+    g.n = (int32_t)L.n;
+    g.slots = (int32_t)L.slots;
+    g.amp_start = live->amp_start;
+    g.amp_end = live->amp_end;
+    g.out_n_closed = out_n_closed;
+    g.out_burst_start = out_burst_start;
+    g.out_burst_len = out_burst_len;
+    g.out_flags = out_flags;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(afsk::live_gate_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return afsk::hip_fail(e, "launch live_gate_kernel");
+    afsk::DemodArgs a = o.args<afsk::DemodArgs>(g.rows, g.slot_off, g.slot_len, live->amp_end, (int32_t)(L.n * L.slots));
+    a.uniform_bit_frames = live->bit_frames;
+    e = afsk::launch_demod_uniform(a, st);
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch demod_uniform_kernel (live slots)");
+}
+
+int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_stream) {
+    if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(live->device)) return rc;
+    hipLaunchKernelGGL(afsk::live_reset_kernel, dim3((uint32_t)((live->L.n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)hip_stream, static_cast<afsk::LiveChan*>(live->d), d_mask_or_null,
+                       (int32_t)live->L.n);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_reset_kernel");
+}
+
+int afsk_live_destroy(afsk_live* live) {
+    delete live;      // the caller has synchronised the launches that use it
+    return AFSK_OK;
+}
+
+}  // extern "C"

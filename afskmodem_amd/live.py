@@ -1,0 +1,198 @@
+"""Live, chunked receive: ``Receiver.receive`` (ref:299-319, 402-417) for many channels whose audio arrives over time.
+
+A ``LiveReceiver`` keeps, on the device, every channel's gate state, stream position and partial block.  Each
+``push`` hands it the next T samples of every channel (a ``[n_channels, T]`` int16 tensor, any row stride) and
+returns the bursts that closed during those T samples, already demodulated -- two asynchronous launches
+(``afsk_live_push``), no host synchronisation, so one push of a fixed T can be captured into a graph and replayed
+for every chunk.  ``flush`` ends every stream (a burst still recording is reported as open-ended); ``reset`` drops
+channels without reporting.  Any sequence of pushes followed by a flush reports what ``gate_batch`` +
+``Receiver.decode_captures`` report on the concatenated capture.  Nothing here opens an audio device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native, batch
+from .modem import _text_or_bytes
+
+DEFAULT_MAX_BURST_LEN = 2 * _native.SAMPLE_RATE     # 2 s: longer bursts are reported as overflowed, not decoded
+DEFAULT_MAX_CHUNK_LEN = 8192
+
+
+def layout(n_channels: int, max_burst_len: int, max_chunk_len: int) -> tuple[int, int]:
+    """(slots per channel and push, device state bytes) of a live receiver (``afsk_live_layout``: host-only)."""
+    slots, nbytes = C.c_int32(), C.c_int64()
+    _native.check(_native.lib().afsk_live_layout(int(n_channels), int(max_burst_len), int(max_chunk_len),
+                                                 C.byref(slots), C.byref(nbytes)))
+    return int(slots.value), int(nbytes.value)
+
+
+@dataclass
+class LiveResult:
+    """Device-resident outputs of one push (torch tensors).  Slot ``(c, k)`` is the k-th burst channel c reported in
+    the push; ``demod`` row ``c * slots + k`` is its demodulation (status TOO_SHORT for unused and overflowed
+    slots)."""
+    n_closed: "object"       # int32 [n_channels] slots in use
+    burst_start: "object"    # int64 [n_channels, slots] first sample in the channel's stream
+    burst_len: "object"      # int32 [n_channels, slots] multiple of 2048
+    flags: "object"          # int32 [n_channels, slots] LIVE_OPEN_END | LIVE_OVERFLOW
+    demod: batch.DemodResult
+
+    @property
+    def slots(self) -> int:
+        return int(self.burst_len.shape[1])
+
+    def bursts(self, string: bool = False) -> list[tuple[int, int, int, "bytes | str"]]:
+        """Synchronise and return ``(channel, start, length, payload)`` per reported burst, channel by channel and in
+        time order.  The payload follows ``Receiver.decode_captures``: text when ``string``, b"" when nothing
+        decodes -- and b"" for an overflowed burst, which is not demodulated."""
+        torch = batch._torch()
+        torch.cuda.synchronize(self.n_closed.device)
+        nc = self.n_closed.cpu().numpy()
+        bs, bl, fl = (t.cpu().numpy() for t in (self.burst_start, self.burst_len, self.flags))
+        chans = np.nonzero(nc)[0]
+        if chans.size == 0:
+            return []
+        payloads = self.demod.payloads()
+        s = self.slots
+        out = []
+        for c in chans.tolist():
+            for k in range(int(nc[c])):
+                data = b"" if fl[c, k] & _native.LIVE_OVERFLOW else _text_or_bytes(payloads[c * s + k], string)
+                out.append((c, int(bs[c, k]), int(bl[c, k]), data))
+        return out
+
+
+class LiveReceiver(batch._NativePlan):
+    """A live receiver of ``n_channels`` independent channels at one baud rate (``bit_frames`` = 48000 / baud), with
+    the thresholds of ``Receiver`` (``threshold_gt`` / ``threshold_lt`` rules, as ``gate_batch``).
+
+    ``max_burst_len``: the longest burst that is stored and demodulated (samples, >= 4096); a longer one is still
+    gated exactly, and reported with its true start and length and ``LIVE_OVERFLOW``.  ``max_chunk_len``: the
+    largest T a push accepts.  Both size the device state (``layout``): per channel a record row of
+    ``(max_burst_len // 2048 + (2047 + max_chunk_len) // 2048) * 2048`` samples.  The receiver belongs to the device
+    that was current (or ``device``); ``close()`` only after its pushes have completed."""
+    _destroy = "afsk_live_destroy"
+
+    def __init__(self, n_channels: int, bit_frames: int, amp_start_threshold=18000, amp_end_threshold=14000,
+                 max_burst_len: int = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN, device=None):
+        torch = batch._torch()
+        batch.validate_bit_frames(int(bit_frames))
+        self.n_channels = int(n_channels)
+        self.bit_frames = int(bit_frames)
+        self.max_burst_len = int(max_burst_len)
+        self.max_chunk_len = int(max_chunk_len)
+        self.slots, self.state_bytes = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)
+        _native.require_device()
+        batch._drain_parked_plans()
+        super().__init__(device)
+        # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
+        self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self.bit_frames)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().afsk_live_create(
+                self.n_channels, self.bit_frames, batch.threshold_gt(amp_start_threshold),
+                batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+
+    def alloc_result(self, diagnostics: bool = False, margin_stride: int | None = None) -> LiveResult:
+        """Output buffers for ``push(out=...)`` (double-buffered pushes, graph capture).  ``diagnostics``: also the
+        demodulator's ``corrected`` / ``margins`` (``margin_stride`` symbols per slot, default: the longest burst)."""
+        torch = batch._torch()
+        n, s, dev = self.n_channels, self.slots, self.device
+        demod = batch.alloc_result(n * s, self.out_stride, dev)
+        if diagnostics:
+            ms = int(margin_stride) if margin_stride is not None else self.max_burst_len // self.bit_frames + 1
+            demod.corrected = torch.zeros(n * s, dtype=torch.int32, device=dev)
+            demod.margins = torch.zeros((n * s, ms), dtype=torch.int32, device=dev)
+        z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod)
+
+    def _chunk(self, chunk):
+        torch = batch._torch()
+        if chunk is None:
+            return torch.empty((self.n_channels, 0), dtype=torch.int16, device=self.device), False
+        uploaded = False
+        if isinstance(chunk, np.ndarray):
+            if chunk.dtype != np.int16:
+                raise TypeError("chunk must hold int16 samples")
+            if chunk.ndim != 2 or chunk.shape[0] != self.n_channels:
+                raise ValueError(f"chunk must be [n_channels={self.n_channels}, T], got {list(chunk.shape)}")
+            if chunk.shape[1] > self.max_chunk_len:
+                raise ValueError(f"T = {chunk.shape[1]} exceeds max_chunk_len = {self.max_chunk_len}")
+            chunk = torch.from_numpy(np.ascontiguousarray(chunk)).to(self.device)      # one copy
+            uploaded = True
+        if not isinstance(chunk, torch.Tensor):
+            raise TypeError("chunk must be an int16 CUDA tensor or a numpy int16 array")
+        if chunk.dtype != torch.int16:
+            raise TypeError("chunk must hold int16 samples")
+        if not chunk.is_cuda or chunk.device != self.device:
+            raise ValueError(f"chunk is on {chunk.device}, the receiver on {self.device}")
+        if chunk.dim() != 2 or chunk.shape[0] != self.n_channels:
+            raise ValueError(f"chunk must be [n_channels={self.n_channels}, T], got {list(chunk.shape)}")
+        if chunk.shape[1] > self.max_chunk_len:
+            raise ValueError(f"T = {chunk.shape[1]} exceeds max_chunk_len = {self.max_chunk_len}")
+        if chunk.shape[1] > 1 and chunk.stride(1) != 1:
+            raise ValueError("chunk rows must be contiguous (any row stride)")
+        return chunk, uploaded
+
+    def push(self, chunk, stream=None, out: LiveResult | None = None, flush: bool = False) -> LiveResult:
+        """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
+        column window of a [channels, time] buffer, no copy -- or a numpy array, uploaded with one copy; None = T 0)
+        to every channel's stream and return the bursts that closed, demodulated.  ``flush``: then end every stream
+        (``flush()``).  Asynchronous on ``stream`` (default: torch's current stream); ``out`` reuses buffers of
+        ``alloc_result``."""
+        torch = batch._torch()
+        chunk, uploaded = self._chunk(chunk)
+        dev = self.device
+        fresh = out is None
+        if fresh:
+            out = self.alloc_result()
+        elif (tuple(out.burst_len.shape) != (self.n_channels, self.slots) or out.burst_len.device != dev
+              or int(out.demod.nbytes.numel()) != self.n_channels * self.slots):
+            raise ValueError("out= was not allocated by this receiver's alloc_result")
+        d = out.demod
+        soft = (None, None, 0)
+        if d.corrected is not None and d.margins is not None:
+            soft = (d.corrected.data_ptr(), d.margins.data_ptr(), int(d.margins.shape[1]))
+        T = int(chunk.shape[1])
+        with torch.cuda.device(dev):
+            if fresh or uploaded:
+                batch._order_after_current(stream, dev)
+            if uploaded and stream is not None:
+                chunk.record_stream(stream)
+            _native.check(_native.lib().afsk_live_push(
+                self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T, int(bool(flush)),
+                out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
+                d.bytes.data_ptr(), int(d.bytes.shape[1]), d.nbytes.data_ptr(), d.nbits.data_ptr(),
+                d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(), *soft,
+                batch._stream_ptr(stream, dev)))
+        out._chunk_keepalive = chunk  # type: ignore[attr-defined]
+        return out
+
+    def flush(self, chunk=None, stream=None, out: LiveResult | None = None) -> LiveResult:
+        """``push(chunk, flush=True)``: end every channel's stream.  A burst still recording is reported (whole blocks,
+        ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0."""
+        return self.push(chunk, stream=stream, out=out, flush=True)
+
+    def reset(self, mask=None, stream=None) -> None:
+        """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /
+        uint8, host or device) is true, without reporting anything; they start new streams."""
+        torch = batch._torch()
+        dev = self.device
+        m = None
+        if mask is not None:
+            if isinstance(mask, torch.Tensor):
+                m = mask.to(device=dev, dtype=torch.uint8).contiguous()
+            else:
+                m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
+            if m.dim() != 1 or int(m.numel()) != self.n_channels:
+                raise ValueError(f"mask must hold n_channels = {self.n_channels} entries")
+        with torch.cuda.device(dev):
+            if m is not None:
+                batch._order_after_current(stream, dev)
+                if stream is not None:
+                    m.record_stream(stream)
+            _native.check(_native.lib().afsk_live_reset(self.handle, None if m is None else m.data_ptr(),
+                                                        batch._stream_ptr(stream, dev)))

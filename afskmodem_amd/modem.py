@@ -429,6 +429,14 @@ class Receiver:
         stride = batch.out_stride_for(max_len, self.__bit_frames)
         return batch.demod_batch_split(samples, off, ln, plan, self.__amp_end_threshold, out_stride=stride)
 
+    def live(self, n_channels: int, **capacities):
+        """A ``live.LiveReceiver`` of ``n_channels`` channels with this Receiver's baud rate and thresholds: the gate of
+        ``receive`` (ref:299-319) fed chunk by chunk, every burst demodulated in the push that closes it.
+        ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples) and ``device``."""
+        from .live import LiveReceiver
+        return LiveReceiver(n_channels, self.__bit_frames, self.__amp_start_threshold, self.__amp_end_threshold,
+                            **capacities)
+
     def decode_captures(self, captures, max_bursts: int = 16, string: bool = False):
         """What repeated ``receive()`` calls would return if each capture (a long int16
         recording) were played into the audio input: the live gate of ``__listen``

@@ -63,3 +63,47 @@ def snr_to_scale_q24(snr_db: float) -> int:
     sigma = 32767.5 / (10.0 ** (snr_db / 20.0))
     gen_std = (16.0 * (65536.0 ** 2 - 1.0) / 12.0) ** 0.5
     return int(round(sigma / gen_std * (1 << 24)))
+
+
+def live_channels(n: int, total: int, baud: int, seed: int, bursts_per_channel: int = 2,
+                  payload_lens=(4, 12, 24), snr_db: float = 30.0, silent_every: int = 0,
+                  training_time: float = 0.25, device=None):
+    """A [n, total] int16 device tensor of live channels (the live receiver's tests and tools/live_bench.py):
+    channel c carries ``bursts_per_channel`` Transmitter bursts (.wav samples, payload sizes drawn from
+    ``payload_lens``), burst k at a random lead inside the k-th equal share of the channel with at least two blocks of
+    quiet around it; every ``silent_every``-th channel (0 = none) stays silent; then oracle-identical noise at
+    ``snr_db`` over every channel.  Modulated on the device.  (The gate may start a block or two into a burst, as the
+    reference's does; the default training of 0.25 s leaves the clock recovery enough of it.)  Returns (samples, bursts) with bursts[c] = [(first
+    sample, payload bytes), ...] in time order."""
+    import torch
+
+    from . import batch
+    dev = batch._default_device(device)
+    rng = np.random.default_rng(seed)
+    bf = SAMPLE_RATE // int(baud)
+    ts = ts_cycles_for(baud, training_time)
+    share = total // max(bursts_per_channel, 1)
+    samples = torch.zeros((n, total), dtype=torch.int16, device=dev)
+    bursts = [[] for _ in range(n)]
+    live = np.ones(n, bool) if not silent_every else (np.arange(n) % silent_every != 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    for k in range(bursts_per_channel):
+        plen = rng.choice(np.asarray(payload_lens, np.int32), n).astype(np.int32)
+        flen = np.array([frames_needed(bf, ts, int(p)) for p in plen], np.int64)
+        room = share - flen - 4 * 2048
+        if (room[live] < 0).any():
+            raise ValueError("bursts do not fit their share of the channel")
+        lead = 2 * 2048 + (rng.random(n) * np.maximum(room, 0)).astype(np.int64)
+        off = np.arange(n, dtype=np.int64) * total + k * share + lead
+        ln = np.where(live, flen, 0).astype(np.int32)
+        payload = payload_bytes(seed * 31 + k, 0, n, int(max(payload_lens)))
+        batch.modulate_batch(t(payload), t(plen), t(np.full(n, bf, np.int32)), t(np.full(n, ts, np.int32)), t(off),
+                             t(ln), int(flen.max()), samples.view(-1), True)
+        for c in np.nonzero(live)[0].tolist():
+            bursts[c].append((int(k * share + lead[c]), payload[c, : plen[c]].tobytes()))
+    if snr_db is not None:
+        off = np.arange(n, dtype=np.int64) * total
+        batch.add_noise_batch(samples.view(-1), t(off), t(np.full(n, total, np.int32)), total,
+                              np.full(n, snr_to_scale_q24(snr_db), np.int32), seed=seed + 7)
+    torch.cuda.synchronize(dev)
+    return samples, bursts

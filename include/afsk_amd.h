@@ -414,6 +414,72 @@ int afsk_gate_batch_slots(const int16_t *samples, const int64_t *stream_offset,
                           int64_t *out_slot_offset, int32_t *out_slot_len, void *hip_stream);
 
 /*
+ * The live receiver (an addition: ABI version unchanged): Receiver.receive (:299-319, :402-417) for n_channels
+ * independent channels whose audio arrives chunk by chunk -- an SDR channelizer, a network fan-in, many sound cards.
+ * Nothing here opens an audio device: the chunks come from any int16 source.  A channel's STREAM is every chunk pushed
+ * to it since creation or since the last flush / reset; the gate is gate_scan_kernel's state machine over the
+ * stream's whole 2048-sample blocks (block k = samples [2048 k, 2048 k + 2048)): discard one block, wait for
+ * amp > amp_start, record through the first block with amp < amp_end (inclusive), repeat; no timeout, and a block
+ * may straddle two pushes.  Every burst that closes during a push is demodulated IN that push, as
+ * afsk_demod_batch_uniform over exactly its recorded samples.  All state (the partial block, the stream position, the
+ * gate) lives on the device: a push never synchronises with the host, so one push of a fixed chunk_len can be
+ * captured into a HIP graph once and replayed for every chunk.
+ *
+ * Capacities (samples): max_burst_len (>= 4096) bounds the bursts that are stored and demodulated; max_chunk_len
+ * bounds chunk_len.  With K = (2047 + max_chunk_len) / 2048 (the most whole blocks one push walks: a carry of 2047
+ * samples plus the chunk) a push reports at most  slots = 1 + K / 3  bursts per channel: one burst already open can
+ * close in the first block, every further one needs a discard, a start and an end block, and a flush adds the burst
+ * still recording.  The bound is exact: for every K some push or flush fills every slot.
+ *
+ *  afsk_live_layout   host-only (no device needed): the slots per channel and the device state bytes
+ *                     afsk_live_create would allocate for these arguments
+ *  afsk_live_create   bit_frames as afsk_demod_batch_uniform (AFSK_E_INVALID_BAUD); amp_start / amp_end as
+ *                     afsk_gate_batch; n_channels >= 1, 4096 <= max_burst_len <= AFSK_MAX_STREAM_LEN,
+ *                     1 <= max_chunk_len <= AFSK_MAX_STREAM_LEN, n_channels * slots < 2^31.  Allocates the state
+ *                     on the current device and zeroes it (synchronous); every channel starts a new stream.
+ *  afsk_live_info     n_channels, slots, state bytes; any pointer may be NULL
+ *  afsk_live_push     appends chunk_len samples (0 ... max_chunk_len) to EVERY channel: row c of the chunk starts at
+ *                     chunk + c * chunk_row_stride (samples, 2-byte alignment: a column window of a [channels, time]
+ *                     buffer is pushed without a copy; chunk may be NULL when chunk_len is 0).  flush != 0 then ends
+ *                     every stream: a burst still recording is reported (whole blocks only, AFSK_LIVE_OPEN_END, as
+ *                     afsk_gate_batch's open_end burst), the partial block is dropped, and the next push starts a new
+ *                     stream at sample 0 with its discard block.  Outputs, slot c * slots + k = the k-th burst
+ *                     channel c reported in this push:
+ *                       out_n_closed    int32 [n_channels] slots of channel c in use
+ *                       out_burst_start int64 [n_channels, slots] first sample of the burst in the channel's stream
+ *                       out_burst_len   int32 [n_channels, slots] samples recorded (a multiple of 2048)
+ *                       out_flags       int32 [n_channels, slots] AFSK_LIVE_* bits
+ *                       out_bytes ... margin_stride  the DemodOutputs of afsk_demod_batch_uniform over the
+ *                                       n_channels * slots slots (rows / arrays indexed by slot)
+ *                     An unused slot has length 0 (flags 0) and demod status AFSK_ST_TOO_SHORT.  A burst longer than
+ *                     max_burst_len is gated exactly like any other; the samples beyond the capacity are not stored,
+ *                     and when it closes it is reported with its true start and length (at most 2^31 - 2048),
+ *                     AFSK_LIVE_OVERFLOW and status AFSK_ST_TOO_SHORT: not demodulated.  chunk_len > max_chunk_len, a
+ *                     receiver of another device or a NULL pointer: AFSK_E_INVALID_ARG.  Two launches in order on
+ *                     hip_stream; pushes to one receiver must run in order (one stream, or ordered streams).
+ *  afsk_live_reset    drops the state of every channel (d_mask_or_null NULL) or of the channels whose DEVICE uint8
+ *                     mask entry is non-zero, without reporting anything: they start a new stream
+ *  afsk_live_destroy  after the launches that use the receiver have completed (NULL is fine)
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_SIGNATURES.)
+ */
+#define AFSK_LIVE_OPEN_END 1 /* reported by a flush while still recording (no quiet block yet)           */
+#define AFSK_LIVE_OVERFLOW 2 /* longer than max_burst_len: not stored in full, not demodulated             */
+typedef struct afsk_live afsk_live;
+extern int afsk_live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chunk_len, int32_t *out_slots,
+                            int64_t *out_state_bytes);
+extern int afsk_live_create(int32_t n_channels, int32_t bit_frames, int32_t amp_start_threshold,
+                            int32_t amp_end_threshold, int32_t max_burst_len, int32_t max_chunk_len, afsk_live **out);
+extern int afsk_live_info(const afsk_live *live, int32_t *out_n_channels, int32_t *out_slots,
+                          int64_t *out_state_bytes);
+extern int afsk_live_push(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                          int32_t flush, int32_t *out_n_closed, int64_t *out_burst_start, int32_t *out_burst_len,
+                          int32_t *out_flags, uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes,
+                          int32_t *out_nbits, int32_t *out_clock_idx, int32_t *out_term_frame, int32_t *out_status,
+                          int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride, void *hip_stream);
+extern int afsk_live_reset(afsk_live *live, const uint8_t *d_mask_or_null, void *hip_stream);
+extern int afsk_live_destroy(afsk_live *live);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,

@@ -1,0 +1,383 @@
+"""GPU parity (-m gpu) of the live receiver (afsk_live_*, ``LiveReceiver``): channels pushed chunk by chunk and
+flushed must report what the whole-capture gate reports -- the reference's own listen vectors, the oracle's
+``gate_stream``, ``gate_batch`` -- and demodulate every burst as ``demod_batch`` / the oracle do on the same samples.
+Expected values never come from the live path itself."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import afskmodem_amd as afskmodem
+from afskmodem_amd import _native, batch, synth
+from afskmodem_amd.live import LiveReceiver
+from oracle import afsk_oracle as O
+from tests.golden_inputs import build_capture
+from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
+BLOCK = 2048
+
+
+def sizes_for(kind, total, rng=None):
+    """Push sizes summing to total."""
+    if kind == "whole":
+        return [total]
+    if kind == "ragged":
+        out, left = [], total
+        while left > 0:
+            t = min(int(rng.choice([0, 1, 5, 2047, 2048, 2049, 4000, 9000, 15000])), left)
+            out.append(t)
+            left -= t
+        return out
+    step = int(kind)
+    return [min(step, total - p) for p in range(0, total, step)] or [0]
+
+
+def collect(res, got):
+    """Append the bursts one push reported to got[c] as dicts (synchronises)."""
+    nc = res.n_closed.cpu().numpy()
+    if not nc.any():
+        return
+    bs, bl, fl = (t.cpu().numpy() for t in (res.burst_start, res.burst_len, res.flags))
+    d = res.demod.cpu()
+    s = res.slots
+    for c in np.nonzero(nc)[0].tolist():
+        for k in range(int(nc[c])):
+            i = c * s + k
+            row = dict(start=int(bs[c, k]), len=int(bl[c, k]), flags=int(fl[c, k]),
+                       bytes=d.bytes[i, : min(int(d.nbytes[i]), d.bytes.shape[1])].tobytes())
+            row.update({f: int(getattr(d, f)[i]) for f in FIELDS})
+            got[c].append(row)
+
+
+def drive(rx, data, sizes, flush=True):
+    """Push the column windows of data ([n, L] device) of the given sizes, flush with the last one."""
+    got = [[] for _ in range(data.shape[0])]
+    pos = 0
+    for i, t in enumerate(sizes):
+        res = rx.push(data[:, pos: pos + t], flush=flush and i == len(sizes) - 1)
+        collect(res, got)
+        pos += t
+    assert pos == data.shape[1]
+    return got
+
+
+def padded(torch, caps, total=None):
+    total = total or max(max(len(c) for c in caps), 1)
+    host = np.zeros((len(caps), total), np.int16)
+    for i, c in enumerate(caps):
+        host[i, : len(c)] = c
+    return host, torch.from_numpy(host).to("cuda:0")
+
+
+def oracle_bursts(cap, a_start, a_end):
+    want, oe = O.gate_stream(cap, a_start, a_end, 4096)
+    return [(s, n, _native.LIVE_OPEN_END if (oe and j == len(want) - 1) else 0) for j, (s, n) in enumerate(want)]
+
+
+def check_demod_against_batch(torch, d_host, rows, bf, amp_end, stride):
+    """Every live burst's demod fields equal demod_batch over that burst of the uploaded whole capture."""
+    offs, lens, live_rows = [], [], []
+    for c, got in enumerate(rows):
+        for g in got:
+            if not g["flags"] & _native.LIVE_OVERFLOW:
+                offs.append(c * d_host.shape[1] + g["start"])
+                lens.append(g["len"])
+                live_rows.append(g)
+    if not offs:
+        return 0
+    flat = d_host.reshape(-1)
+    res = batch.demod_batch(flat, torch.tensor(offs, dtype=torch.int64, device="cuda:0"),
+                            torch.tensor(lens, dtype=torch.int32, device="cuda:0"), bf, amp_end,
+                            out_stride=stride).cpu()
+    for j, g in enumerate(live_rows):
+        for f in FIELDS:
+            assert g[f] == int(getattr(res, f)[j]), (j, f)
+        assert g["bytes"] == res.payloads()[j], j
+    return len(live_rows)
+
+
+@pytest.mark.parametrize("pair", [(18000, 14000), (9000, 2500)])
+def test_reference_listen_cases_in_every_chunking(golden, torch_cuda, pair):
+    torch = torch_cuda
+    a_start, a_end = pair
+    cases = [c for c in golden["listen_cases"] if c["amp_start"] == a_start]
+    assert len(cases) == 8
+    caps = [build_capture(c["recipe"]) for c in cases]
+    rng = np.random.default_rng(11)
+    # the open-ended case alone (no padding may close its burst), all others side by side, zero padded: after their
+    # last burst closed, quiet blocks change nothing
+    groups = [[i for i, c in enumerate(cases) if c["open_end"]], [i for i, c in enumerate(cases) if not c["open_end"]]]
+    for group in groups:
+        gcaps = [caps[i] for i in group]
+        host, dev = padded(torch, gcaps)
+        total = host.shape[1]
+        rx = LiveReceiver(len(group), 40, a_start, a_end, max_burst_len=65536, max_chunk_len=total)
+        first = None
+        for kind in ("whole", "2048", "1", "2047", "2049", "3000", "ragged"):
+            got = drive(rx, dev, sizes_for(kind, total, rng))
+            for j, i in enumerate(group):
+                c = cases[i]
+                spans = [(g["start"], g["len"], g["flags"]) for g in got[j]]
+                assert spans == oracle_bursts(host[j], a_start, a_end), (c["name"], kind)
+                want = [(b["start"], b["len"]) for b in c["bursts"]]
+                assert [(s, n) for s, n, _ in spans] == want, (c["name"], kind)
+                assert [f for _, _, f in spans] == [0] * (len(want) - c["open_end"]) + \
+                    [_native.LIVE_OPEN_END] * c["open_end"], (c["name"], kind)
+                for g, b in zip(got[j], c["bursts"]):
+                    if b["len"] == b["ref_len"]:
+                        assert g["bytes"].hex() == b["bytes_hex"], (c["name"], kind)
+            if first is None:
+                first = got
+                assert check_demod_against_batch(torch, dev, got, 40, a_end, rx.out_stride) > 0 or group == groups[0]
+            else:
+                assert got == first, kind
+        rx.close()
+
+
+def test_random_captures_and_the_slot_bound(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(8)                              # the captures of test_gpu_next_rows' gate test
+    caps = [rng.integers(-32768, 32768, int(n)).astype(np.int16) * (rng.integers(0, 2, int(n)).astype(np.int16))
+            for n in (0, 100, 2048, 4096, 50000, 123457)]
+    caps += [np.concatenate([rng.integers(-a, a + 1, 2048 * int(k)).astype(np.int16)
+                             for a, k in zip(rng.integers(1000, 32000, 12), rng.integers(1, 4, 12))])
+             for _ in range(20)]
+    for i, cap in enumerate(caps):
+        rx = LiveReceiver(1, 40, max_burst_len=1 << 17, max_chunk_len=15000)
+        d = torch.from_numpy(cap.reshape(1, -1).copy()).to("cuda:0")
+        for kind in ("2047", "8192", "ragged"):
+            got = drive(rx, d, sizes_for(kind, len(cap), rng))
+            assert [(g["start"], g["len"], g["flags"]) for g in got[0]] == oracle_bursts(cap, 18000, 14000), (i, kind)
+        rx.close()
+    # bursts closing every third block: after a burst opened with a 2047-sample carry, one push of max_chunk_len
+    # fills every slot (with a flush when K % 3 == 0)
+    for mc in (8192, 4097, 6144):
+        k = (2047 + mc) // BLOCK
+        amps = [0, 30000, 0] + [(30000, 30000, 0)[(i - 1) % 3] for i in range(1, k)]
+        cap = np.concatenate([np.tile(np.array([a, -a], np.int16), BLOCK // 2) for a in amps] +
+                             [np.zeros(2047 + mc - k * BLOCK + 1, np.int16)])[: 2 * BLOCK + 2047 + mc]
+        rx = LiveReceiver(2, 40, max_burst_len=8192, max_chunk_len=mc)
+        d = torch.from_numpy(np.stack([cap, np.zeros_like(cap)])).to("cuda:0")
+        pre = 2 * BLOCK + 2047
+        got = [[] for _ in range(2)]
+        for p in range(0, pre, mc):
+            collect(rx.push(d[:, p: min(p + mc, pre)]), got)
+        assert got == [[], []]
+        res = rx.push(d[:, pre: pre + mc], flush=k % 3 == 0)
+        torch.cuda.synchronize()
+        assert res.n_closed.cpu().tolist() == [rx.slots, 0], (mc, rx.slots)
+        collect(res, got)
+        assert [(g["start"], g["len"], g["flags"]) for g in got[0]] == oracle_bursts(cap, 18000, 14000)
+        rx.close()
+
+
+# (4800 baud has bit_frames 10, not a multiple of 4: the reference's receiver cannot decode it, and neither can this
+# one -- validate_bit_frames raises its error)
+@pytest.mark.parametrize("baud", [1200, 300, 2400])
+def test_real_payloads_in_noise(torch_cuda, baud):
+    torch = torch_cuda
+    bf = 48000 // baud
+    rng = np.random.default_rng(baud)
+    n, total = 12, 6 * 48000
+    tx = afskmodem.Transmitter(baud, 0.1)
+    host = np.zeros((n, total), np.int16)
+    sent = []
+    for c in range(n):
+        pos, mine = int(rng.integers(4096, 30000)), []
+        for k in range(3):
+            data = rng.integers(0, 256, int(rng.choice([3, 9, 20])), dtype=np.uint8).tobytes()
+            w = tx.wav_samples(data)
+            if pos + len(w) + 8192 > total:
+                break
+            host[c, pos: pos + len(w)] = w
+            mine.append(data)
+            pos += len(w) + int(rng.integers(6000, 20000))
+        sent.append(mine)
+    snr = np.where(np.arange(n) % 2 == 0, 20.0, 10.0)
+    for c in range(n):
+        host[c] = O.add_noise(host[c], 5, c, synth.snr_to_scale_q24(float(snr[c])))
+    dev = torch.from_numpy(host).to("cuda:0")
+    rx = afskmodem.Receiver(baud).live(n, max_burst_len=4 * 48000, max_chunk_len=4800)
+    got = drive(rx, dev, sizes_for("4800", total))
+    for c in range(n):
+        spans = [(g["start"], g["len"], g["flags"]) for g in got[c]]
+        assert spans == oracle_bursts(host[c], 18000, 14000), c
+        for g in got[c]:
+            assert g["bytes"] == O.load_frames(host[c, g["start"]: g["start"] + g["len"]], baud, 14000), c
+        if snr[c] == 20.0:
+            assert [g["bytes"] for g in got[c]] == sent[c], c
+    assert check_demod_against_batch(torch, dev, got, bf, 14000, rx.out_stride) >= n
+
+
+def test_overflow_is_flagged_and_not_decoded(torch_cuda):
+    torch = torch_cuda
+    tx = afskmodem.Transmitter(1200, 0.1)
+    burst = tx.wav_samples(b"after")
+    loud = np.tile(np.array([30000, -30000], np.int16), 10 * BLOCK)        # 20 loud blocks
+    cap = np.concatenate([np.zeros(3 * BLOCK, np.int16), loud, np.zeros(3 * BLOCK, np.int16), burst,
+                          np.zeros(5000, np.int16)])
+    other = np.concatenate([np.zeros(5000, np.int16), burst, np.zeros(len(cap) - 5000 - len(burst), np.int16)])
+    host = np.stack([cap, other])
+    dev = torch.from_numpy(host).to("cuda:0")
+    rx = LiveReceiver(2, 40, max_burst_len=16384, max_chunk_len=3000)
+    for kind in ("3000", "2048"):
+        got = drive(rx, dev, sizes_for(kind, len(cap)))
+        for c in range(2):
+            assert [(g["start"], g["len"], g["flags"]) for g in got[c]] == [
+                (s, n, f | (_native.LIVE_OVERFLOW if n > 16384 else 0)) for s, n, f in oracle_bursts(host[c], 18000, 14000)]
+        assert got[0][0]["flags"] == _native.LIVE_OVERFLOW and got[0][0]["len"] > 16384
+        assert got[0][0]["status"] == _native.ST_TOO_SHORT and got[0][0]["bytes"] == b""
+        assert [g["bytes"] for g in got[0][1:]] == [b"after"] and [g["bytes"] for g in got[1]] == [b"after"]
+        check_demod_against_batch(torch, dev, got, 40, 14000, rx.out_stride)
+    res = rx.push(dev[:, :3000])
+    assert all(p == b"" or isinstance(p, bytes) for _, _, _, p in res.bursts())
+    rx.close()
+
+
+def test_flush_starts_new_streams_and_masked_reset(golden, torch_cuda):
+    torch = torch_cuda
+    cases = [c for c in golden["listen_cases"] if c["amp_start"] == 18000 and not c["open_end"]][:4]
+    caps = [build_capture(c["recipe"]) for c in cases]
+    host, dev = padded(torch, caps)
+    rx = LiveReceiver(len(caps), 40, max_burst_len=65536, max_chunk_len=5000)
+    half = host.shape[1] // 2 + 1000
+    drive(rx, dev[:, :half], sizes_for("5000", half))             # flushed part-way through the first captures
+    got = drive(rx, dev, sizes_for("5000", host.shape[1]))        # a new stream: the whole captures from sample 0
+    g = batch.gate_batch(dev.reshape(-1), torch.arange(len(caps), device="cuda:0", dtype=torch.int64) * host.shape[1],
+                         torch.full((len(caps),), host.shape[1], dtype=torch.int32, device="cuda:0"), host.shape[1],
+                         18000, 14000, 16)
+    nb, bs, bl = (t.cpu().numpy() for t in (g.n_bursts, g.burst_start, g.burst_len))
+    for c in range(len(caps)):
+        assert [(x["start"], x["len"]) for x in got[c]] == [(int(bs[c, k]), int(bl[c, k])) for k in range(nb[c])]
+        assert [(x["start"], x["len"]) for x in got[c]] == [(b["start"], b["len"]) for b in cases[c]["bursts"]]
+    # masked reset: channels 0 and 2 restart where the reset happened, 1 and 3 keep their streams
+    got = [[] for _ in caps]
+    cut = 9 * BLOCK + 123
+    for p in range(0, cut, 4000):
+        collect(rx.push(dev[:, p: min(p + 4000, cut)]), got)
+    rx.reset(np.array([1, 0, 1, 0], bool))
+    for p in range(cut, host.shape[1], 4000):
+        collect(rx.push(dev[:, p: min(p + 4000, host.shape[1])], flush=p + 4000 >= host.shape[1]), got)
+    for c in range(len(caps)):
+        if c % 2 == 0:
+            want = [(s + cut, n, f) for s, n, f in oracle_bursts(host[c, cut:], 18000, 14000)]
+            before = [(s, n, f) for s, n, f in oracle_bursts(host[c, :cut], 18000, 14000) if f == 0]
+            assert [(x["start"], x["len"], x["flags"]) for x in got[c]] == before + [
+                (s - cut, n, f) for s, n, f in want], c
+        else:
+            assert [(x["start"], x["len"], x["flags"]) for x in got[c]] == oracle_bursts(host[c], 18000, 14000), c
+    rx.close()
+
+
+def test_graph_captured_push_matches_eager(golden, torch_cuda):
+    torch = torch_cuda
+    n, total, T = 64, 20 * 48000 // 10, 4096
+    samples, _ = synth.live_channels(n, total, 1200, seed=3, bursts_per_channel=2, silent_every=5, device="cuda:0")
+    eager = LiveReceiver(n, 40, max_burst_len=48000, max_chunk_len=T)
+    graphed = LiveReceiver(n, 40, max_burst_len=48000, max_chunk_len=T)
+    buf = torch.zeros((n, T), dtype=torch.int16, device="cuda:0")
+    out = graphed.alloc_result()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            graphed.push(buf, out=out)
+    torch.cuda.synchronize()
+    want, have = [[] for _ in range(n)], [[] for _ in range(n)]
+    n_push = total // T
+    for i in range(n_push):
+        collect(eager.push(samples[:, i * T: (i + 1) * T]), want)
+        buf.copy_(samples[:, i * T: (i + 1) * T])
+        graph.replay()
+        torch.cuda.synchronize()
+        collect(out, have)
+    collect(eager.flush(), want)
+    collect(graphed.flush(), have)
+    assert have == want and sum(map(len, want)) > n
+    eager.close()
+    graphed.close()
+
+
+def round_trip(torch, rx, samples, bursts, T, sample_channels, baud):
+    n, total = samples.shape
+    got = [[] for _ in range(n)]
+    for p in range(0, total, T):
+        res = rx.push(samples[:, p: min(p + T, total)], flush=p + T >= total)
+        for c, s, ln, payload in res.bursts():
+            got[c].append((s, ln, payload))
+    for c in range(n):
+        assert [p for _, _, p in got[c]] == [b for _, b in bursts[c]], c
+    host = samples[torch.as_tensor(sample_channels, device=samples.device)].cpu().numpy()
+    for j, c in enumerate(sample_channels):
+        assert [(s, ln) for s, ln, _ in got[c]] == O.gate_stream(host[j], 18000, 14000, 64)[0], c
+        for s, ln, p in got[c]:
+            assert p == O.load_frames(host[j, s: s + ln], baud, 14000), c
+
+
+def test_scale_past_the_large_launch_thresholds(torch_cuda):
+    torch = torch_cuda
+    n, total = 8256, 72000
+    samples, bursts = synth.live_channels(n, total, 1200, seed=21, bursts_per_channel=2, payload_lens=(3, 8),
+                                          silent_every=7, device="cuda:0")
+    rx = LiveReceiver(n, 40, max_burst_len=32768, max_chunk_len=2048)
+    assert n * rx.slots >= 8192
+    sample = np.random.default_rng(1).choice(n, 64, replace=False).tolist()
+    round_trip(torch, rx, samples, bursts, 2048, sample, 1200)
+    rx.close()
+
+
+def test_scale_65536_channels_4s(torch_cuda):
+    torch = torch_cuda
+    n, total = 65536, 4 * 48000
+    samples, bursts = synth.live_channels(n, total, 1200, seed=22, bursts_per_channel=2, payload_lens=(4, 12, 24),
+                                          silent_every=9, device="cuda:0")
+    rx = LiveReceiver(n, 40, max_burst_len=48000, max_chunk_len=8192)
+    sample = np.random.default_rng(2).choice(n, 1024, replace=False).tolist()
+    round_trip(torch, rx, samples, bursts, 8192, sample, 1200)
+    rx.close()
+    del samples
+    torch.cuda.empty_cache()
+
+
+def test_argument_checks(torch_cuda):
+    torch = torch_cuda
+    rx = LiveReceiver(4, 40, max_burst_len=8192, max_chunk_len=4096)
+    ok = torch.zeros((4, 100), dtype=torch.int16, device="cuda:0")
+    with pytest.raises(ValueError):
+        rx.push(torch.zeros((3, 100), dtype=torch.int16, device="cuda:0"))
+    with pytest.raises(TypeError):
+        rx.push(torch.zeros((4, 100), dtype=torch.int32, device="cuda:0"))
+    with pytest.raises(ValueError):
+        rx.push(torch.zeros((4, 100), dtype=torch.int16))                    # host tensor
+    with pytest.raises(ValueError):
+        rx.push(torch.zeros((4, 4097), dtype=torch.int16, device="cuda:0"))  # T > max_chunk_len
+    with pytest.raises(ValueError):
+        rx.push(np.zeros((4, 4097), np.int16))
+    with pytest.raises(ValueError):
+        rx.push(torch.zeros((100, 4), dtype=torch.int16, device="cuda:0").t())   # columns, not rows
+    with pytest.raises(ValueError):
+        rx.reset(np.ones(3, bool))
+    torch.cuda.synchronize()
+    assert rx.push(ok).n_closed.cpu().tolist() == [0] * 4                     # nothing was launched before
+    out = rx.alloc_result()
+    d = out.demod
+    lib = _native.lib()
+    tail = (d.bytes.data_ptr(), int(d.bytes.shape[1]), d.nbytes.data_ptr(), d.nbits.data_ptr(), d.clock_idx.data_ptr(),
+            d.term_frame.data_ptr(), d.status.data_ptr(), None, None, 0, None)
+    heads = (out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr())
+    for i in range(4):
+        h = list(heads)
+        h[i] = None
+        assert lib.afsk_live_push(rx.handle, ok.data_ptr(), 100, 100, 0, *h, *tail) == _native.E_INVALID_ARG
+    assert lib.afsk_live_push(rx.handle, None, 100, 100, 0, *heads, *tail) == _native.E_INVALID_ARG
+    assert lib.afsk_live_push(rx.handle, ok.data_ptr(), 100, 4097, 0, *heads, *tail) == _native.E_INVALID_ARG
+    bad_tail = (d.bytes.data_ptr(), int(d.bytes.shape[1]), None) + tail[3:]
+    assert lib.afsk_live_push(rx.handle, ok.data_ptr(), 100, 100, 0, *heads, *bad_tail) == _native.E_INVALID_ARG
+    n_ch, slots, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    assert lib.afsk_live_info(rx.handle, C.byref(n_ch), C.byref(slots), C.byref(nbytes)) == 0
+    assert (n_ch.value, slots.value, nbytes.value) == (4, rx.slots, rx.state_bytes)
+    torch.cuda.synchronize()
+    rx.close()

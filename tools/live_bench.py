@@ -1,0 +1,198 @@
+#!/usr/bin/env python3
+"""live_bench.py -- the live receiver (LiveReceiver / afsk_live_push) on synthetic channels, one push per chunk.
+
+    python tools/live_bench.py [--shapes 65536x2048,65536x8192,64x48000] [--seconds 4] [--reps 3] [--json OUT]
+                               [--no-verify] [--kernel-stats STATS_CSV]
+
+Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
+noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
+silent) into one [channels, seconds * 48000] buffer.  Every push is a column window of that buffer (no copy), captured
+once into a HIP graph per window position and replayed; HIP events around each replay give us per push.  Reported:
+the median and mean us per push, the audio real-time factor (seconds of audio per channel / wall seconds of the
+pushes), and the algorithmic bytes per push over the mean push time as a share of the 8 TB/s HBM peak:
+2 B per pushed sample read + 2 B per recorded sample written + the row compaction (read + write) + what the
+demodulator must read of every closed burst (bench.py's active samples: up to the squelch-triggering symbol) + the
+outputs.  The gate's own bytes (everything but the demodulator's) are printed apart: with --kernel-stats (the
+stats CSV of a `rocprofv3 --kernel-trace --stats` run of this tool) the gate kernel's share of peak comes from its
+own kernel time.  Unless --no-verify, a seeded sample of channels is checked against Receiver.decode_captures on the
+same streams, and every channel's payloads against the transmitted ones.
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import afskmodem_amd as afskmodem  # noqa: E402
+from afskmodem_amd import batch, synth  # noqa: E402
+from afskmodem_amd.live import LiveReceiver  # noqa: E402
+
+PEAK = 8.0e12
+BAUD, BF = 1200, 40
+BLOCK = 2048
+
+
+def walk_bytes(amp, T, n_push, cap_blocks, a_start=18000, a_end=14000):
+    """The gate's data movement over the whole stream, from the block amplitudes [n, nb] (the walk of
+    live_gate_kernel, vectorised over channels): samples written to the rows and moved by the compaction."""
+    n, nb = amp.shape
+    mode = np.zeros(n, np.int8)
+    rec = np.zeros(n, np.int64)           # blocks recorded in the open burst
+    opened_behind = np.zeros(n, bool)     # the open burst opened in this push behind a burst that closed in it
+    closed_here = np.zeros(n, bool)
+    written = moved = 0
+    done = np.array([((b + 1) * BLOCK + T - 1) // T - 1 for b in range(nb)])   # push in which block b completes
+    b = 0
+    for p in range(n_push):
+        # start of push p: the open burst that opened behind closed ones moves to the row front
+        moved += int(np.minimum(rec[(mode == 2) & opened_behind], cap_blocks).sum()) * BLOCK
+        opened_behind[:] = False
+        closed_here[:] = False
+        while b < nb and done[b] == p:
+            a = amp[:, b]
+            m0, m1, m2 = mode == 0, mode == 1, mode == 2
+            start = m1 & (a > a_start)
+            written += int((start | (m2 & (rec < cap_blocks))).sum()) * BLOCK
+            rec = np.where(start, 1, np.where(m2, rec + 1, rec))
+            opened_behind |= start & closed_here
+            close = m2 & (a < a_end)
+            closed_here |= close
+            mode = np.where(m0, 1, np.where(start, 2, np.where(close, 0, mode))).astype(np.int8)
+            b += 1
+    return written, moved
+
+
+def run_shape(torch, n, T, seconds, reps, verify, seed):
+    total = int(seconds * 48000)
+    n_push = total // T
+    total = n_push * T
+    samples, sent = synth.live_channels(n, total, BAUD, seed, bursts_per_channel=2, payload_lens=(4, 12, 24),
+                                        silent_every=8, device="cuda")
+    max_burst = 48000
+    rx = LiveReceiver(n, BF, max_burst_len=max_burst, max_chunk_len=T)
+    outs = [rx.alloc_result() for _ in range(2)]
+    # eager pass: the bursts, for the checks and the byte count
+    got = [[] for _ in range(n)]
+    closed_active = 0
+    out_bytes = 0
+    for p in range(n_push):
+        res = rx.push(samples[:, p * T: (p + 1) * T], out=outs[p % 2], flush=p == n_push - 1)
+        torch.cuda.synchronize()
+        d = res.demod
+        active = torch.clamp(torch.clamp(d.term_frame.long() + (d.nbits.long() + 1) * BF, min=4096),
+                             max=res.burst_len.reshape(-1).long())
+        active = torch.where(res.burst_len.reshape(-1) > 0, active, 0)
+        closed_active += int(active.sum())
+        out_bytes += int(torch.clamp(d.nbytes, max=d.bytes.shape[1]).sum())
+        if verify:
+            for c, s, ln, payload in res.bursts():
+                got[c].append((s, ln, payload))
+    # outputs: the gate's n_closed, burst start / length / flags and the demodulator's slot offset / length; the
+    # demodulator's five int32 fields per slot plus the payload bytes
+    gate_out = n_push * n * (4 + rx.slots * (8 + 4 + 4 + 8 + 4))
+    out_bytes += n_push * n * rx.slots * 20
+    # the gate's data movement, from the block amplitudes of the same streams
+    nb = total // BLOCK
+    g = batch.gate_batch(samples.reshape(-1), torch.arange(n, device="cuda", dtype=torch.int64) * total,
+                         torch.full((n,), total, dtype=torch.int32, device="cuda"), total, max_bursts=1, slots=False)
+    amp = g.block_amp[:, :nb].cpu().numpy()
+    del g
+    written, moved = walk_bytes(amp, T, n_push, max_burst // BLOCK)
+    gate_bytes = 2 * n * total + 2 * written + 4 * moved + gate_out
+    alg_bytes = gate_bytes + 2 * closed_active + out_bytes
+    checks = {}
+    if verify:
+        ok = sum(1 for c in range(n) if [p for _, _, p in got[c]] == [b for _, b in sent[c]])
+        checks["roundtrip_channels"] = f"{ok}/{n}"
+        rng = np.random.default_rng(seed)
+        sample = sorted(rng.choice(n, min(n, 256), replace=False).tolist())
+        host = samples[torch.as_tensor(sample, device="cuda")].cpu().numpy()
+        want = afskmodem.Receiver(BAUD).decode_captures(list(host), max_bursts=64)
+        checks["decode_captures_sample"] = f"{sum(want[j] == [p for _, _, p in got[c]] for j, c in enumerate(sample))}" \
+                                           f"/{len(sample)}"
+    # graphs: one per column window, replayed in stream order
+    rx.reset()
+    graphs = []
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for p in range(n_push):
+            gph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gph, stream=side):
+                rx.push(samples[:, p * T: (p + 1) * T], out=outs[p % 2])
+            graphs.append(gph)
+    torch.cuda.synchronize()
+    times = []
+    for r in range(reps + 1):
+        rx.flush()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_push)]
+        for p in range(n_push):
+            ev[p][0].record()
+            graphs[p].replay()
+            ev[p][1].record()
+        torch.cuda.synchronize()
+        if r:                                          # the first pass warms up
+            times += [a.elapsed_time(b) * 1e3 for a, b in ev]
+    us = np.asarray(times)
+    mean_us = float(us.mean())
+    rec = dict(shape=f"{n}x{T}", channels=n, T=T, pushes=n_push, seconds_per_channel=total / 48000, slots=rx.slots,
+               us_per_push_median=round(float(np.median(us)), 2), us_per_push_mean=round(mean_us, 2),
+               us_per_push_p90=round(float(np.percentile(us, 90)), 2),
+               realtime_factor=round((T / 48000) / (mean_us * 1e-6), 1),
+               alg_bytes_per_push=int(alg_bytes / n_push), gate_bytes_per_push=int(gate_bytes / n_push),
+               recorded_samples=int(written), compaction_samples=int(moved), demod_active_samples=int(closed_active),
+               share_of_peak_push=round(alg_bytes / n_push / (mean_us * 1e-6) / PEAK, 3), **checks)
+    del graphs, samples
+    rx.close()
+    torch.cuda.empty_cache()
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="65536x2048,65536x8192,64x48000")
+    ap.add_argument("--seconds", type=float, default=4.0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--json")
+    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--kernel-stats", help="rocprofv3 --stats kernel CSV of a run of this tool: adds the gate's share")
+    ap.add_argument("--results", help="with --kernel-stats: the JSON of the timed run to annotate")
+    ap.add_argument("--profiled-shape", help="with --kernel-stats: the one shape the profiled run timed")
+    args = ap.parse_args()
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        doc = json.load(open(args.results))
+        doc["profiled_shape"] = args.profiled_shape
+        for r in rows:
+            name = r.get("Name") or r.get("KernelName") or ""
+            if "live_gate_kernel" in name:
+                doc["gate_kernel_calls"] = int(r["Calls"])
+                doc["gate_kernel_mean_us"] = round(float(r["AverageNs"]) / 1e3, 2)
+            if "demod_uniform" in name:
+                doc.setdefault("demod_kernels", []).append(dict(name=name[:80], calls=int(r["Calls"]),
+                                                                 mean_us=round(float(r["AverageNs"]) / 1e3, 2)))
+        for rec in doc.get("results", []):
+            if "gate_kernel_mean_us" in doc and rec["shape"] == doc.get("profiled_shape"):
+                rec["gate_kernel_share_of_peak"] = round(rec["gate_bytes_per_push"] / (doc["gate_kernel_mean_us"] * 1e-6)
+                                                         / PEAK, 3)
+        print(json.dumps(doc))
+        return
+    import torch
+    res = []
+    for s in args.shapes.split(","):
+        n, T = (int(x) for x in s.split("x"))
+        rec = run_shape(torch, n, T, args.seconds, args.reps, not args.no_verify, args.seed)
+        print(json.dumps(rec), flush=True)
+        res.append(rec)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(dict(tool="tools/live_bench.py", seconds=args.seconds, reps=args.reps, results=res), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
