@@ -119,6 +119,21 @@ LIVE_SIGNATURES = {
 LIVE_OPEN_END, LIVE_OVERFLOW = 1, 2          # AFSK_LIVE_* flags
 
 
+# The live transmitter (afsk_live_tx_*), bound by lib() from a table of its own for the same reason.
+LIVE_TX_SIGNATURES = {
+    "afsk_live_tx_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i64p]),
+    "afsk_live_tx_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "afsk_live_tx_info": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i64p]),
+    "afsk_live_tx_submit": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afsk_live_tx_pull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "afsk_live_tx_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afsk_live_tx_destroy": (C.c_int, [C.c_void_p]),
+}
+# AFSK_LIVE_TX_* submit statuses
+LIVE_TX_QUEUED, LIVE_TX_QUEUE_FULL, LIVE_TX_TOO_LONG, LIVE_TX_BAD_CHANNEL, LIVE_TX_UNSORTED = 0, 1, 2, 3, 4
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -128,7 +143,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with afskmodem_amd/csrc/build.sh "
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
+                                  *LIVE_TX_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,523 @@
+// afsk_live_tx.hip -- the live transmitter (afsk_live_tx_*, include/afsk_amd.h): Transmitter.transmit
+// (afskmodem.py:472-478) for many channels played out chunk by chunk, each channel with a device-resident queue of
+// messages that go out back to back.
+//
+// A submit is two launches: live_tx_order_kernel (one block) finds the first message whose channel is below its
+// predecessor's, then live_tx_submit_kernel walks every run of equal channels before it with one thread, in order:
+// check, take a ring entry, assign the start, copy the payload.  Nothing but the array order decides the queue order.
+//
+// A pull is two launches, in order on the caller's stream (a captured graph of them is a linear chain):
+//   live_tx_tile_kernel   one wave per (channel, 1, 2 or 4 consecutive tiles of kTxTile samples of the pull): loads
+//                         the channel state and its descriptor ring at once (the ring into LDS when it fits), then per
+//                         tile finds the message whose tones meet it and renders it with modulate_kernel_t's
+//                         scheme (payload window, tone-kind ballot, quarter-symbol bitmap, tone_words), 8 samples per
+//                         16-byte store; reads the channel state, writes only the caller's buffer
+//   live_tx_commit_kernel one thread per channel: advances pos, retires the messages that have ended, writes pending
+//
+// Every message is at least 4 symbols + the 4800-sample silent tail long, so the tones of two messages of a channel
+// are at least 4800 samples apart and a tile of at most 4096 samples meets the tones of one message at most.
+//
+// This file is compiled as part of afsk_synth.hip's translation unit (see the #include at its end): it uses that
+// file's store16, hamming_codeword / symbol_is_mark, q_words, kWinBytes and tone_words.
+#include <memory>
+#include <new>
+
+#include "../../include/afsk_amd.h"
+#include "afsk_capi_internal.h"
+
+namespace afsk {
+
+struct TxChan {             // 32 bytes per channel
+    int64_t pos;            // samples of the current stream pulled so far
+    int64_t end;            // end (stream index) of the last message queued; <= pos once the queue has drained
+    int32_t head;           // ring entry of the oldest message not yet fully emitted
+    int32_t count;          // messages queued or on air
+    int32_t pad[2];
+};
+static_assert(sizeof(TxChan) == 32, "TxChan layout");
+
+struct TxDesc {             // 16 bytes per ring entry
+    int64_t start;          // stream index of the first sample
+    int32_t n_samples;      // .wav samples of the message: tones + 4800 silent samples
+    int32_t payload_len;
+};
+static_assert(sizeof(TxDesc) == 16, "TxDesc layout");
+
+constexpr int kTxThreads = 64;                                  // one wave per block
+constexpr int kTxIters = 8;                                     // 16-byte stores per lane and tile
+constexpr int kTxTile = kTxThreads * 8 * kTxIters;              // samples per tile
+static_assert(kTxTile < AFSK_TAIL_SILENCE, "a tile must not meet the tones of two messages");
+static_assert(kTxTile / 56 + 4 <= kWinBytes, "payload window too small for the tile");
+constexpr int kTxLdsRing = 64;                                  // rings up to this depth are read from LDS
+constexpr int kTxMinBlocks = 8192;                              // 32 waves per CU before tiles are shared
+constexpr int kTxMaxDepth = 1024;
+constexpr int kTxMaxPayload = 65536;
+
+struct TxLayout {
+    int64_t n = 0, depth = 0, max_payload = 0;
+    int64_t o_desc = 0, o_slots = 0, o_scratch = 0, bytes = 0;
+};
+
+inline int64_t tx_align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+// The state allocation: TxChan [n] | TxDesc [n, depth] | payload slots uint8 [n, depth, max_payload] | 256 bytes of
+// submit scratch (the first unsorted message); every part 256-byte aligned.
+inline int live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, TxLayout& L) {
+    if (n_channels < 1) return fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
+    if (queue_depth < 1 || queue_depth > kTxMaxDepth)
+        return fail(AFSK_E_INVALID_ARG, "queue_depth must lie in 1 ... 1024");
+    if (max_payload_len < 0 || max_payload_len > kTxMaxPayload)
+        return fail(AFSK_E_INVALID_ARG, "max_payload_len must lie in 0 ... 65536");
+    if ((int64_t)n_channels * queue_depth > 0x7fffffffll)
+        return fail(AFSK_E_INVALID_ARG, "n_channels * queue_depth exceeds 2^31 - 1");
+    L.n = n_channels;
+    L.depth = queue_depth;
+    L.max_payload = max_payload_len;
+    L.o_desc = tx_align256(32 * L.n);
+    L.o_slots = L.o_desc + tx_align256(16 * L.n * L.depth);
+    L.o_scratch = L.o_slots + tx_align256(L.n * L.depth * L.max_payload);
+    L.bytes = L.o_scratch + 256;
+    return AFSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------- submit
+
+__global__ __launch_bounds__(256) void live_tx_order_kernel(const int32_t* channel, int32_t n, int32_t* first_bad) {
+    __shared__ int32_t red[256];
+    int32_t m = n;
+    for (int32_t i = (int32_t)threadIdx.x + 1; i < n; i += 256)
+        if (channel[i] < channel[i - 1]) { m = i; break; }      // a thread's indices rise: its first is its least
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *first_bad = red[0];
+}
+
+struct TxSubmitArgs {
+    TxChan* chan;
+    TxDesc* desc;
+    uint8_t* slots;
+    const int32_t* first_bad;
+    const int32_t* channel;
+    const int64_t* payload_offset;
+    const int32_t* payload_len;
+    const uint8_t* payload;
+    const int32_t* out_index;   // NULL: outputs of message i at i
+    int32_t* out_status;
+    int64_t* out_start;
+    int32_t* out_n_samples;
+    int32_t n_msgs;
+    int32_t n;
+    int32_t depth;
+    int32_t max_payload;
+    int32_t bf;
+    int32_t n_train_sym;
+};
+
+__global__ __launch_bounds__(256) void live_tx_submit_kernel(TxSubmitArgs a) {
+    const int32_t i = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= a.n_msgs) return;
+    auto put = [&](int32_t j, int32_t status, int64_t start, int32_t ns) {
+        const int32_t k = a.out_index ? a.out_index[j] : j;
+        if ((uint32_t)k >= (uint32_t)a.n_msgs) return;          // (not a permutation: nothing written for it)
+        a.out_status[k] = status;
+        a.out_start[k] = start;
+        a.out_n_samples[k] = ns;
+    };
+    const int32_t first_bad = *a.first_bad;
+    if (i >= first_bad) { put(i, AFSK_LIVE_TX_UNSORTED, -1, 0); return; }
+    const int32_t ch = a.channel[i];
+    if (i > 0 && a.channel[i - 1] == ch) return;                // not the first of its run
+    const bool ok = ch >= 0 && ch < a.n;
+    TxChan st = ok ? a.chan[ch] : TxChan{};
+    for (int32_t j = i; j < first_bad && a.channel[j] == ch; j++) {
+        const int32_t plen = a.payload_len[j];
+        if (!ok) { put(j, AFSK_LIVE_TX_BAD_CHANNEL, -1, 0); continue; }
+        if (plen < 0 || plen > a.max_payload) { put(j, AFSK_LIVE_TX_TOO_LONG, -1, 0); continue; }
+        if (st.count >= a.depth) { put(j, AFSK_LIVE_TX_QUEUE_FULL, -1, 0); continue; }
+        const int64_t start = st.pos > st.end ? st.pos : st.end;
+        const int32_t ns = a.bf * (a.n_train_sym + 4 + 14 * plen) + AFSK_TAIL_SILENCE;   // <= AFSK_MAX_STREAM_LEN
+        int32_t slot = st.head + st.count;
+        if (slot >= a.depth) slot -= a.depth;
+        const int64_t e = (int64_t)ch * a.depth + slot;
+        a.desc[e] = TxDesc{start, ns, plen};
+        uint8_t* dst = a.slots + e * a.max_payload;
+        const uint8_t* src = a.payload + a.payload_offset[j];
+        for (int32_t b = 0; b < plen; b++) dst[b] = src[b];
+        st.end = start + ns;
+        st.count++;
+        put(j, AFSK_LIVE_TX_QUEUED, start, ns);
+    }
+    if (ok) a.chan[ch] = st;
+}
+
+// --------------------------------------------------------------------------------------------------------- pull
+
+struct TxPullArgs {
+    const TxChan* chan;
+    const TxDesc* desc;
+    const uint8_t* slots;
+    int16_t* out;
+    int64_t out_stride;
+    int32_t T;
+    int32_t tiles;              // tiles per channel: ceil(T / kTxTile)
+    int32_t tiles_per_block;    // consecutive tiles of one channel a block renders
+    int32_t blocks_per_row;     // ceil(tiles / tiles_per_block)
+    int32_t depth;
+    int32_t max_payload;
+    uint32_t bf;
+    uint32_t n_train_sym;
+};
+
+// The two samples of relative frame x (even): frame x's tone value twice (wav quirk ref:239-244).
+__device__ __forceinline__ uint32_t tone_pair(uint32_t x, float rcp_q, const uint32_t* qb) {
+    const uint32_t Q = (uint32_t)(((float)x + 0.5f) * rcp_q);
+    return ((qb[Q >> 5] >> (Q & 31u)) & 1u) ? kHi2 : kLo2;
+}
+
+// Samples x .. x+7 of a message (x relative to its first sample, any sign and parity), zero outside its tones
+// [0, lim).  xb: the relative frame of the first symbol in qb.  With the quirk, sample m is frame m & ~1, so an odd x
+// takes the pairs of frames x-1 ... x+7 and shifts them by one sample.
+template <bool SMALLQ>
+__device__ __forceinline__ store16 msg_words(int32_t x, int32_t lim, int32_t xb, uint32_t q, float rcp_q,
+                                             uint32_t mq, const uint32_t* qb, bool odd) {
+    store16 w{0u, 0u, 0u, 0u};
+    if (x + 8 <= 0 || x >= lim) return w;
+    const int32_t xe = x & ~1;
+    uint32_t p4 = 0u;                                                // the pair of frame xe + 8 (odd x only)
+    if (xe >= 0 && xe + 10 <= lim) {
+        w = tone_words<true, SMALLQ>((uint32_t)(xe - xb), q, rcp_q, mq, qb);
+        if (odd) p4 = tone_pair((uint32_t)(xe + 8 - xb), rcp_q, qb);
+    } else {                                                         // the message's first or last tone samples
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int32_t f = xe + 2 * d;
+            w[d] = (f >= 0 && f < lim) ? tone_pair((uint32_t)(f - xb), rcp_q, qb) : 0u;
+        }
+        if (odd && xe + 8 < lim) p4 = tone_pair((uint32_t)(xe + 8 - xb), rcp_q, qb);
+    }
+    if (odd) {
+        w[0] = __builtin_amdgcn_alignbit(w[1], w[0], 16);
+        w[1] = __builtin_amdgcn_alignbit(w[2], w[1], 16);
+        w[2] = __builtin_amdgcn_alignbit(w[3], w[2], 16);
+        w[3] = __builtin_amdgcn_alignbit(p4, w[3], 16);
+    }
+    return w;
+}
+
+__device__ __forceinline__ void tx_store(int16_t* dst0, uint32_t j0, uint32_t len, store16 w) {
+    int16_t* dst = dst0 + j0;
+    if (j0 + 8u <= len) {
+        *reinterpret_cast<store16*>(dst) = w;
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++)
+            if (j0 + j < len) dst[j] = (int16_t)(w[j >> 1] >> (16u * (j & 1u)));
+    }
+}
+
+template <bool SMALLQ>
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel(TxPullArgs a) {
+    __shared__ uint8_t win[kWinBytes];
+    __shared__ unsigned long long kinds[kTxTile / 4 / 64 + 2];
+    __shared__ uint32_t qbits[q_words(kTxTile)];
+    __shared__ TxDesc ring[kTxLdsRing];
+    const int bid = xcd_block((int)blockIdx.x, (int)gridDim.x);
+    const int c = bid / a.blocks_per_row;
+    const int b = bid - c * a.blocks_per_row;
+    const uint32_t bf = a.bf;
+    const uint32_t n_train_sym = a.n_train_sym;
+    // the channel state and its whole descriptor ring, loaded at once (neither address depends on the other load)
+    const TxChan ch = a.chan[c];
+    const TxDesc* gring = a.desc + (int64_t)c * a.depth;
+    const uint8_t* gpay = a.slots + (int64_t)c * a.depth * a.max_payload;
+    const bool lds_ring = a.depth <= kTxLdsRing;
+    if (lds_ring && (int)threadIdx.x < a.depth) ring[threadIdx.x] = gring[threadIdx.x];
+    __syncthreads();
+
+    for (int k = 0; k < a.tiles_per_block; k++) {
+        const int t = b * a.tiles_per_block + k;
+        if (t >= a.tiles) break;                                       // block-uniform
+        if (k > 0) __syncthreads();                                    // the previous tile's qbits / win are read
+        const uint32_t t0 = (uint32_t)t * kTxTile;
+        const uint32_t len = min((uint32_t)kTxTile, (uint32_t)a.T - t0);   // samples of this tile
+        int16_t* dst0 = a.out + (int64_t)c * a.out_stride + t0;
+        const int64_t p0 = ch.pos + t0;
+
+        // the message whose tones [start, start + n_samples - 4800) meet [p0, p0 + len): the ring is in stream order
+        int64_t m0 = 0;                 // p0 relative to the message's first sample
+        int32_t lim = 0;                // tone samples of the message (0: the tile is silent)
+        uint32_t plen = 0;
+        int32_t slot = 0;
+        for (int32_t i = 0, e = ch.head; i < ch.count; i++, e = (e + 1 == a.depth ? 0 : e + 1)) {
+            const TxDesc d = lds_ring ? ring[e] : gring[e];
+            if (d.start >= p0 + len) break;
+            const int32_t tones = d.n_samples - AFSK_TAIL_SILENCE;
+            if (d.start + tones > p0) {
+                m0 = p0 - d.start;
+                lim = tones;
+                plen = (uint32_t)d.payload_len;
+                slot = e;
+                break;
+            }
+        }
+        if (lim == 0) {
+#pragma unroll
+            for (int it = 0; it < kTxIters; it++) {
+                const uint32_t j0 = ((uint32_t)it * kTxThreads + threadIdx.x) * 8u;
+                if (j0 >= len) break;
+                tx_store(dst0, j0, len, store16{0u, 0u, 0u, 0u});
+            }
+            continue;
+        }
+
+        // the tile meets the tones: m0 lies in (-len, lim)
+        const int32_t x0 = (int32_t)m0;
+        const uint32_t lo = x0 > 0 ? (uint32_t)x0 : 0u;
+        const uint32_t Sb = lo / bf;                                   // first symbol the tile touches
+        const uint32_t n_sym = n_train_sym + 4u + 14u * plen;
+        const uint32_t data0 = n_train_sym + 4u;
+        const uint32_t first_byte = ((Sb > data0 ? Sb - data0 : 0u) / 7u) >> 1;
+        const uint32_t last = (lo + kTxTile + 15u) / bf + 2u;          // exclusive upper bound + slack (odd phase)
+        const uint32_t nsym_blk = last - Sb + 1u;
+        if (Sb + nsym_blk > data0) {                                   // block-uniform: data symbols
+            // the bytes the tile's data symbols read: fewer than nsym_blk / 14 + 4 from first_byte
+            const uint8_t* payload = gpay + (int64_t)slot * a.max_payload;
+            const uint32_t need = min((uint32_t)kWinBytes, nsym_blk / 14u + 4u);
+            for (uint32_t i = threadIdx.x; i < need; i += kTxThreads) {
+                const uint32_t idx = first_byte + i;
+                win[i] = idx < plen ? payload[idx] : (uint8_t)0;
+            }
+            __syncthreads();
+        }
+        {
+            const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+            for (uint32_t r0 = wave * 64u; r0 < nsym_blk; r0 += kTxThreads) {
+                const uint32_t S = Sb + r0 + lane;
+                const bool mk = S < n_sym && symbol_is_mark(S, n_train_sym, first_byte, win);
+                const unsigned long long m = __ballot(mk);
+                if (lane == 0) kinds[r0 >> 6] = m;
+            }
+        }
+        __syncthreads();
+        {
+            // quarter bitmap as modulate_kernel_t: word w = symbols Sb + 8w .. 8w+7, space 0b0011, mark 0b0101
+            const uint32_t nwords = (nsym_blk + 7u) >> 3;
+            for (uint32_t w = threadIdx.x; w <= nwords; w += kTxThreads) {
+                uint32_t x = w < nwords ? (uint32_t)(kinds[w >> 3] >> ((w & 7u) * 8u)) & 0xFFu : 0u;
+                x = (x | (x << 12)) & 0x000F000Fu;
+                x = (x | (x << 6)) & 0x03030303u;
+                x = (x | (x << 3)) & 0x11111111u;
+                qbits[w] = 0x33333333u ^ (x * 6u);
+            }
+        }
+        __syncthreads();
+        const uint32_t q = bf >> 2;
+        const float rcp_q = 1.0f / (float)q;
+        const uint32_t mq = (65536u + q - 1u) / q;
+        const int32_t xb = (int32_t)(Sb * bf);
+        const bool odd = (x0 & 1) != 0;
+#pragma unroll 2
+        for (int it = 0; it < kTxIters; it++) {
+            const uint32_t j0 = ((uint32_t)it * kTxThreads + threadIdx.x) * 8u;
+            if (j0 >= len) break;
+            tx_store(dst0, j0, len, msg_words<SMALLQ>(x0 + (int32_t)j0, lim, xb, q, rcp_q, mq, qbits, odd));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void live_tx_commit_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
+                                                             int32_t depth, int32_t T, int32_t* pending) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    TxChan st = chan[c];
+    st.pos += T;
+    while (st.count > 0) {
+        const TxDesc d = desc[(int64_t)c * depth + st.head];
+        if (d.start + d.n_samples > st.pos) break;
+        st.head = st.head + 1 == depth ? 0 : st.head + 1;
+        st.count--;
+    }
+    chan[c] = st;
+    pending[c] = st.count;
+}
+
+__global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const uint8_t* mask, int32_t* pending,
+                                                            int32_t n) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < n && (!mask || mask[c])) {
+        chan[c] = TxChan{};
+        if (pending) pending[c] = 0;
+    }
+}
+
+}  // namespace afsk
+
+struct afsk_live_tx {
+    int device = -1;
+    afsk::TxLayout L;
+    int32_t bit_frames = 0, n_train_sym = 0;
+    void* d = nullptr;
+    ~afsk_live_tx() {
+        if (d) (void)hipFree(d);
+    }
+};
+
+extern "C" {
+
+int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, int64_t* out_state_bytes) {
+    afsk::TxLayout L;
+    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
+    if (out_state_bytes) *out_state_bytes = L.bytes;
+    return AFSK_OK;
+}
+
+int afsk_live_tx_create(int32_t n_channels, int32_t bit_frames, int32_t ts_cycles, int32_t queue_depth,
+                        int32_t max_payload_len, afsk_live_tx** out) {
+    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    *out = nullptr;
+    if (bit_frames < 4 || (bit_frames & 3) != 0 || bit_frames > AFSK_SAMPLE_RATE)
+        return afsk::fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 in 4 ... 48000");
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
+        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
+        const int64_t ts = ts_cycles > 0 ? ts_cycles : 0;               // ref:457: range(negative) runs zero times
+        const int64_t longest = (int64_t)bit_frames * (2 * ts + 4 + 14 * (int64_t)max_payload_len) + AFSK_TAIL_SILENCE;
+        if (longest > AFSK_MAX_STREAM_LEN)
+            return afsk::fail(AFSK_E_INVALID_ARG, "the longest message would exceed AFSK_MAX_STREAM_LEN samples");
+        if (int rc = afsk::require_device()) return rc;
+        hipError_t e = hipGetDevice(&tx->device);
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (hipGetDevice)");
+        tx->bit_frames = bit_frames;
+        tx->n_train_sym = (int32_t)(2 * ts);
+        e = hipMalloc(&tx->d, (size_t)tx->L.bytes);
+        if (e != hipSuccess) { tx->d = nullptr; return afsk::hip_fail(e, "afsk_live_tx_create (hipMalloc)"); }
+        // only the channel states need a value: ring entries and payload slots are written before they are read
+        e = hipMemsetAsync(tx->d, 0, (size_t)tx->L.o_desc, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (zero the state)");
+        *out = tx.release();
+        return AFSK_OK;
+    });
+}
+
+int afsk_live_tx_info(const afsk_live_tx* tx, int32_t* out_n_channels, int32_t* out_queue_depth,
+                      int32_t* out_max_payload_len, int64_t* out_state_bytes) {
+    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (out_n_channels) *out_n_channels = (int32_t)tx->L.n;
+    if (out_queue_depth) *out_queue_depth = (int32_t)tx->L.depth;
+    if (out_max_payload_len) *out_max_payload_len = (int32_t)tx->L.max_payload;
+    if (out_state_bytes) *out_state_bytes = tx->L.bytes;
+    return AFSK_OK;
+}
+
+int afsk_live_tx_submit(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel, const int64_t* payload_offset,
+                        const int32_t* payload_len, const uint8_t* payload, const int32_t* out_index,
+                        int32_t* out_status, int64_t* out_start, int32_t* out_n_samples, void* hip_stream) {
+    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (n_msgs < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
+    if (n_msgs == 0) return AFSK_OK;
+    if (!channel || !payload_offset || !payload_len || !payload || !out_status || !out_start || !out_n_samples)
+        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
+    const afsk::TxLayout& L = tx->L;
+    uint8_t* d = static_cast<uint8_t*>(tx->d);
+    int32_t* first_bad = reinterpret_cast<int32_t*>(d + L.o_scratch);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(afsk::live_tx_order_kernel, dim3(1), dim3(256), 0, st, channel, n_msgs, first_bad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_order_kernel");
+    afsk::TxSubmitArgs a{};
+    a.chan = reinterpret_cast<afsk::TxChan*>(d);
+    a.desc = reinterpret_cast<afsk::TxDesc*>(d + L.o_desc);
+    a.slots = d + L.o_slots;
+    a.first_bad = first_bad;
+    a.channel = channel;
+    a.payload_offset = payload_offset;
+    a.payload_len = payload_len;
+    a.payload = payload;
+    a.out_index = out_index;
+    a.out_status = out_status;
+    a.out_start = out_start;
+    a.out_n_samples = out_n_samples;
+    a.n_msgs = n_msgs;
+    a.n = (int32_t)L.n;
+    a.depth = (int32_t)L.depth;
+    a.max_payload = (int32_t)L.max_payload;
+    a.bf = tx->bit_frames;
+    a.n_train_sym = tx->n_train_sym;
+    hipLaunchKernelGGL(afsk::live_tx_submit_kernel, dim3((uint32_t)((n_msgs + 255) / 256)), dim3(256), 0, st, a);
+    e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_submit_kernel");
+}
+
+int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, int32_t* out_pending,
+                      void* hip_stream) {
+    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (n_samples < 0 || out_row_stride < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
+    if (n_samples > AFSK_MAX_STREAM_LEN) return afsk::fail(AFSK_E_INVALID_ARG, "n_samples exceeds AFSK_MAX_STREAM_LEN");
+    const afsk::TxLayout& L = tx->L;
+    if (L.n > 1 && n_samples > 0 && out_row_stride < n_samples)
+        return afsk::fail(AFSK_E_INVALID_ARG, "out_row_stride below n_samples: the rows would overlap");
+    if ((n_samples > 0 && !out) || !out_pending) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    const int32_t tiles = (int32_t)((n_samples + afsk::kTxTile - 1) / afsk::kTxTile);
+    if ((int64_t)tiles * L.n > 0x7fffffffll) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels * tiles exceeds 2^31 - 1");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
+    uint8_t* d = static_cast<uint8_t*>(tx->d);
+    afsk::TxChan* chan = reinterpret_cast<afsk::TxChan*>(d);
+    const afsk::TxDesc* desc = reinterpret_cast<const afsk::TxDesc*>(d + L.o_desc);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    hipError_t e;
+    if (n_samples > 0) {
+        afsk::TxPullArgs a{};
+        a.chan = chan;
+        a.desc = desc;
+        a.slots = d + L.o_slots;
+        a.out = out;
+        a.out_stride = out_row_stride;
+        a.T = n_samples;
+        a.tiles = tiles;
+        // several consecutive tiles per block share the loads of the channel state and ring, as long as the grid keeps
+        // at least 32 waves per CU
+        const int64_t all = (int64_t)tiles * L.n;
+        a.tiles_per_block = all >= 4 * afsk::kTxMinBlocks ? 4 : (all >= 2 * afsk::kTxMinBlocks ? 2 : 1);
+        a.blocks_per_row = (tiles + a.tiles_per_block - 1) / a.tiles_per_block;
+        a.depth = (int32_t)L.depth;
+        a.max_payload = (int32_t)L.max_payload;
+        a.bf = (uint32_t)tx->bit_frames;
+        a.n_train_sym = (uint32_t)tx->n_train_sym;
+        const dim3 grid((uint32_t)(a.blocks_per_row * L.n));
+        if (tx->bit_frames / 4 >= 8) hipLaunchKernelGGL(afsk::live_tx_tile_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a);
+        else hipLaunchKernelGGL(afsk::live_tx_tile_kernel<true>, grid, dim3(afsk::kTxThreads), 0, st, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_tile_kernel");
+    }
+    hipLaunchKernelGGL(afsk::live_tx_commit_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st, chan, desc,
+                       (int32_t)L.n, (int32_t)L.depth, n_samples, out_pending);
+    e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_commit_kernel");
+}
+
+int afsk_live_tx_reset(afsk_live_tx* tx, const uint8_t* d_mask_or_null, int32_t* out_pending_or_null,
+                       void* hip_stream) {
+    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (int rc = afsk::require_device()) return rc;
+    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
+    hipLaunchKernelGGL(afsk::live_tx_reset_kernel, dim3((uint32_t)((tx->L.n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)hip_stream, static_cast<afsk::TxChan*>(tx->d), d_mask_or_null, out_pending_or_null,
+                       (int32_t)tx->L.n);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_reset_kernel");
+}
+
+int afsk_live_tx_destroy(afsk_live_tx* tx) {
+    delete tx;        // the caller has synchronised the launches that use it
+    return AFSK_OK;
+}
+
+}  // extern "C"

@@ -292,3 +292,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 }
 
 }  // namespace afsk
+
+// The live transmitter (afsk_live_tx_*: per-channel message queues pulled chunk by chunk) is compiled as part of this
+// translation unit: build.sh compiles a fixed list of files, and it renders with this file's tone_words scheme.
+#include "afsk_live_tx.hip"

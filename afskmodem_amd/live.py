@@ -1,4 +1,6 @@
-"""Live, chunked receive: ``Receiver.receive`` (ref:299-319, 402-417) for many channels whose audio arrives over time.
+"""Live, chunked receive and transmit.
+
+Receive: ``Receiver.receive`` (ref:299-319, 402-417) for many channels whose audio arrives over time.
 
 A ``LiveReceiver`` keeps, on the device, every channel's gate state, stream position and partial block.  Each
 ``push`` hands it the next T samples of every channel (a ``[n_channels, T]`` int16 tensor, any row stride) and
@@ -6,7 +8,11 @@ returns the bursts that closed during those T samples, already demodulated -- tw
 (``afsk_live_push``), no host synchronisation, so one push of a fixed T can be captured into a graph and replayed
 for every chunk.  ``flush`` ends every stream (a burst still recording is reported as open-ended); ``reset`` drops
 channels without reporting.  Any sequence of pushes followed by a flush reports what ``gate_batch`` +
-``Receiver.decode_captures`` report on the concatenated capture.  Nothing here opens an audio device.
+``Receiver.decode_captures`` report on the concatenated capture.
+
+Transmit: a ``LiveTransmitter`` keeps a queue of messages per channel on the device; each ``pull`` writes the next T
+samples of every channel (``afsk_live_tx_pull``), the queued messages back to back, each exactly what
+``Transmitter.save`` writes for it.  Nothing here opens an audio device.
 """
 from __future__ import annotations
 
@@ -196,3 +202,184 @@ class LiveReceiver(batch._NativePlan):
                     m.record_stream(stream)
             _native.check(_native.lib().afsk_live_reset(self.handle, None if m is None else m.data_ptr(),
                                                         batch._stream_ptr(stream, dev)))
+
+
+# ------------------------------------------------------------------------------------------------- live transmit
+
+DEFAULT_QUEUE_DEPTH = 4
+DEFAULT_MAX_PAYLOAD_LEN = 256
+
+
+def tx_layout(n_channels: int, queue_depth: int, max_payload_len: int) -> int:
+    """Device state bytes of a live transmitter (``afsk_live_tx_layout``: host-only)."""
+    nbytes = C.c_int64()
+    _native.check(_native.lib().afsk_live_tx_layout(int(n_channels), int(queue_depth), int(max_payload_len),
+                                                    C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def tx_bit_frames(baud_rate) -> int:
+    """``48000 / baud_rate`` when it is a positive multiple of 4 (the live transmitter's rates), else ValueError."""
+    b = int(baud_rate)
+    if b != baud_rate or b <= 0 or _native.SAMPLE_RATE % b != 0 or (_native.SAMPLE_RATE // b) % 4 != 0:
+        raise ValueError(f"baud rate {baud_rate!r}: 48000 / baud must be a positive multiple of 4")
+    return _native.SAMPLE_RATE // b
+
+
+@dataclass
+class SubmitResult:
+    """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order."""
+    status: "object"         # int32 [n] LIVE_TX_QUEUED / _QUEUE_FULL / _TOO_LONG / _BAD_CHANNEL
+    start: "object"          # int64 [n] stream index of the first sample (-1: rejected)
+    n_samples: "object"      # int32 [n] samples of the message (0: rejected)
+
+    def cpu(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Synchronise and return (status, start, n_samples) as numpy arrays."""
+        return tuple(t.cpu().numpy() for t in (self.status, self.start, self.n_samples))
+
+
+class LiveTransmitter(batch._NativePlan):
+    """A live transmitter of ``n_channels`` independent channels at one baud rate and training time: the samples
+    ``Transmitter(baud_rate, training_time).wav_samples`` makes of each queued message, played back to back, pulled
+    as the next T samples of every channel (``pull``) -- the mirror image of ``LiveReceiver.push``.
+
+    Each channel queues up to ``queue_depth`` messages not yet fully emitted, of at most ``max_payload_len`` bytes,
+    on the device.  A channel's stream is numbered from 0 at creation or ``reset``; a message queued on a busy channel
+    follows the previous one with no gap, one queued on an idle channel starts at the next sample pulled.  Submits and
+    pulls never synchronise with the host; a pull of a fixed T into a fixed buffer can be captured into a graph.  The
+    transmitter belongs to the device that was current (or ``device``); ``close()`` only after its launches have
+    completed."""
+    _destroy = "afsk_live_tx_destroy"
+
+    def __init__(self, n_channels: int, baud_rate: int = 1200, training_time: float = 0.5,
+                 queue_depth: int = DEFAULT_QUEUE_DEPTH, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, device=None):
+        torch = batch._torch()
+        from .modem import Transmitter
+        self.bit_frames = tx_bit_frames(baud_rate)
+        if int(n_channels) < 1:
+            raise ValueError("n_channels must be at least 1")
+        self.n_channels = int(n_channels)
+        self.baud_rate = int(baud_rate)
+        self.ts_cycles = Transmitter(self.baud_rate, training_time).ts_cycles     # ref:438 (negative: no cycles)
+        self.queue_depth = int(queue_depth)
+        self.max_payload_len = int(max_payload_len)
+        self.state_bytes = tx_layout(self.n_channels, self.queue_depth, self.max_payload_len)
+        _native.require_device()
+        batch._drain_parked_plans()
+        super().__init__(device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().afsk_live_tx_create(
+                self.n_channels, self.bit_frames, int(self.ts_cycles), self.queue_depth, self.max_payload_len,
+                C.byref(self._h)))
+        # messages queued or on air per channel after the last pull (0 for channels reset since)
+        self.pending = torch.zeros(self.n_channels, dtype=torch.int32, device=self.device)
+
+    def message_len(self, payload_len) -> "int | np.ndarray":
+        """Samples of a message of ``payload_len`` bytes: tones + the 4800-sample silent tail (ref:452-469)."""
+        ts = max(self.ts_cycles, 0)
+        return self.bit_frames * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
+
+    def submit(self, channels, payloads, stream=None) -> SubmitResult:
+        """Queue ``payloads[i]`` (str -- UTF-8 -- or bytes) on channel ``channels[i]`` (a sequence, or one int for
+        all).  A channel's messages are queued in list order.  Everything goes up in one copy; the outputs are device
+        tensors in list order, and nothing synchronises.  Asynchronous on ``stream`` (default: torch's current
+        stream)."""
+        torch = batch._torch()
+        data = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in payloads]
+        n = len(data)
+        ch = np.broadcast_to(np.asarray(channels, np.int64), (n,)) if np.ndim(channels) == 0 else \
+            np.asarray(channels, np.int64)
+        if ch.shape != (n,):
+            raise ValueError(f"{ch.size} channels for {n} payloads")
+        dev = self.device
+        out = SubmitResult(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+                           torch.empty(n, dtype=torch.int32, device=dev))
+        if n == 0:
+            return out
+        ch32 = np.where((ch < 0) | (ch >= self.n_channels), -1, ch).astype(np.int32)   # -1: AFSK_LIVE_TX_BAD_CHANNEL
+        perm = np.argsort(ch32, kind="stable")                 # the C entry walks non-decreasing channels
+        ordered = bool((perm == np.arange(n)).all())
+        lens = np.array([len(d) for d in data], np.int64)[perm]
+        offs = np.zeros(n, np.int64)
+        np.cumsum(lens[:-1], out=offs[1:])
+        # one host buffer, one copy: offsets int64 | channels int32 | lengths int32 | out_index int32 | payload bytes
+        head = 8 * n + 4 * n + 4 * n + (0 if ordered else 4 * n)
+        host = torch.empty(head + int(lens.sum()), dtype=torch.uint8, pin_memory=True)
+        h = host.numpy()
+        h[: 8 * n].view(np.int64)[:] = offs
+        h[8 * n: 12 * n].view(np.int32)[:] = ch32[perm]
+        h[12 * n: 16 * n].view(np.int32)[:] = np.minimum(lens, 2 ** 31 - 1)
+        if not ordered:
+            h[16 * n: 20 * n].view(np.int32)[:] = perm
+        h[head:] = np.frombuffer(b"".join(data[i] for i in perm.tolist()), np.uint8)
+        with torch.cuda.device(dev):
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(s):
+                d = host.to(dev, non_blocking=True)
+            if stream is not None:
+                batch._order_after_current(stream, dev)      # (the outputs were allocated on the current stream)
+                d.record_stream(stream)
+            base = d.data_ptr()
+            _native.check(_native.lib().afsk_live_tx_submit(
+                self.handle, n, base + 8 * n, base, base + 12 * n, base + head, None if ordered else base + 16 * n,
+                out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(), batch._stream_ptr(s, dev)))
+        out._keepalive = d  # type: ignore[attr-defined]
+        return out
+
+    def pull(self, T: int, out=None, stream=None):
+        """Write samples ``[pos, pos + T)`` of every channel into ``out`` ([n_channels, >= T] int16 CUDA tensor with
+        contiguous rows and any row stride -- e.g. a column window of a [channels, time] buffer; None: a new [n, T]
+        tensor) and return ``out[:, :T]``.  Nothing of ``out`` outside those T columns is written.  Then every
+        channel advances by T, the messages that ended are retired and ``pending`` is updated.  Asynchronous on
+        ``stream`` (default: torch's current stream)."""
+        torch = batch._torch()
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        if T > _native.MAX_STREAM_LEN:
+            raise ValueError(f"T = {T} exceeds AFSK_MAX_STREAM_LEN")
+        dev = self.device
+        fresh = out is None
+        if fresh:
+            out = torch.empty((self.n_channels, T), dtype=torch.int16, device=dev)
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be an int16 CUDA tensor")
+        if out.dtype != torch.int16:
+            raise TypeError("out must hold int16 samples")
+        if not out.is_cuda or out.device != dev:
+            raise ValueError(f"out is on {out.device}, the transmitter on {dev}")
+        if out.dim() != 2 or out.shape[0] != self.n_channels or out.shape[1] < T:
+            raise ValueError(f"out must be [n_channels={self.n_channels}, >= {T}], got {list(out.shape)}")
+        if T > 1 and out.stride(1) != 1:
+            raise ValueError("out rows must be contiguous (any row stride)")
+        if self.n_channels > 1 and T > 0 and out.stride(0) < T:
+            raise ValueError(f"out row stride {out.stride(0)} is below T = {T}: the rows would overlap")
+        with torch.cuda.device(dev):
+            if fresh:
+                batch._order_after_current(stream, dev)
+            _native.check(_native.lib().afsk_live_tx_pull(
+                self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T, self.pending.data_ptr(),
+                batch._stream_ptr(stream, dev)))
+        return out[:, :T]
+
+    def reset(self, mask=None, stream=None) -> None:
+        """Drop every queued message -- a half-sent one too -- of every channel (``mask`` None) or of the channels where
+        ``mask`` ([n_channels] bool / uint8, host or device) is true: their streams restart at sample 0, their
+        ``pending`` entries become 0."""
+        torch = batch._torch()
+        dev = self.device
+        m = None
+        if mask is not None:
+            if isinstance(mask, torch.Tensor):
+                m = mask.to(device=dev, dtype=torch.uint8).contiguous()
+            else:
+                m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
+            if m.dim() != 1 or int(m.numel()) != self.n_channels:
+                raise ValueError(f"mask must hold n_channels = {self.n_channels} entries")
+        with torch.cuda.device(dev):
+            if m is not None:
+                batch._order_after_current(stream, dev)
+                if stream is not None:
+                    m.record_stream(stream)
+            _native.check(_native.lib().afsk_live_tx_reset(self.handle, None if m is None else m.data_ptr(),
+                                                           self.pending.data_ptr(), batch._stream_ptr(stream, dev)))

@@ -506,6 +506,7 @@ class Transmitter:
 
     def __init__(self, baud_rate: int = 1200, training_time: float = 0.5):
         self.__baud_rate = baud_rate
+        self.__training_time = training_time
         self.__ts_cycles: int = int(baud_rate * training_time / 2)       # ref:438
         self.__space_tone = _space_array(baud_rate)
         self.__mark_tone = _mark_array(baud_rate)
@@ -605,6 +606,15 @@ class Transmitter:
             except OSError:
                 pass
             self.save(payloads[int(i)], names[int(i)])
+
+    def live(self, n_channels: int, queue_depth: int = 4, max_payload_len: int = 256, device=None):
+        """A ``live.LiveTransmitter`` of ``n_channels`` channels with this Transmitter's baud rate and training time:
+        messages queued per channel, played back to back, every channel's next T samples per ``pull`` -- what
+        ``transmit`` (ref:472-478) plays, for many channels at once.  ``48000 / baud`` must be a multiple of 4
+        (ValueError otherwise)."""
+        from .live import LiveTransmitter
+        return LiveTransmitter(n_channels, self.__baud_rate, self.__training_time, queue_depth=queue_depth,
+                               max_payload_len=max_payload_len, device=device)
 
     def wav_samples(self, data: str | bytes, total: int | None = None) -> np.ndarray:
         """The int16 samples ``save`` would put in the .wav, optionally zero padded to total."""

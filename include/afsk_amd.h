@@ -480,6 +480,67 @@ extern int afsk_live_reset(afsk_live *live, const uint8_t *d_mask_or_null, void 
 extern int afsk_live_destroy(afsk_live *live);
 
 /*
+ * The live transmitter (an addition: ABI version unchanged): Transmitter.transmit (:472-478) for n_channels
+ * independent channels at one bit_frames and training length.  Every channel has a device-resident queue of up to
+ * queue_depth messages; each pull writes the next n_samples samples of every channel's stream, the queued messages
+ * back to back.  A channel's stream is what it produced since it was created or reset, numbered from 0; pos = samples
+ * pulled so far.  A message of payload p is the .wav samples of Transmitter.save (:452-469 with the writer's
+ * decimate/duplicate quirk :239-244): n_samples = bit_frames * (2 * ts_cycles + 4 + 14 * len(p)) + 4800.  Samples
+ * outside any message are 0.  Submits and pulls never synchronise with the host; a pull of a fixed n_samples into a
+ * fixed buffer can be captured into a graph.
+ *
+ *  afsk_live_tx_layout   host-only (no device needed): the device state bytes afsk_live_tx_create would allocate
+ *  afsk_live_tx_create   bit_frames a multiple of 4 in 4 ... 48000 (the device modulator's symbol geometry; every rate a
+ *                        Receiver decodes), else AFSK_E_INVALID_BAUD; ts_cycles as Transmitter (a negative value: no
+ *                        training cycles); n_channels >= 1, 1 <= queue_depth <= 1024, 0 <= max_payload_len <= 65536,
+ *                        n_channels * queue_depth < 2^31, the longest message <= AFSK_MAX_STREAM_LEN samples.
+ *                        Allocates the state on the current device and zeroes it (synchronous).
+ *  afsk_live_tx_info     n_channels, queue_depth, max_payload_len, state bytes; any pointer may be NULL
+ *  afsk_live_tx_submit   queues n_msgs messages (DEVICE arrays): message i goes to channel[i], its payload is
+ *                        payload_len[i] bytes at payload + payload_offset[i].  channel[] must be non-decreasing: from
+ *                        the first message whose channel is below its predecessor's on, every message gets
+ *                        AFSK_LIVE_TX_UNSORTED.  A channel's messages are queued in array order; a queued message
+ *                        starts at max(pos, end of the channel's last queued message).  Rejected messages
+ *                        (AFSK_LIVE_TX_QUEUE_FULL: queue_depth messages not yet fully emitted; _TOO_LONG: payload_len
+ *                        outside 0 ... max_payload_len; _BAD_CHANNEL) take no queue entry.  Outputs (int32 status, int64
+ *                        start = stream index of the first sample, int32 n_samples; -1 and 0 for a rejected message)
+ *                        of message i go to entry out_index[i] (a permutation of 0 ... n_msgs - 1), or to entry i
+ *                        when out_index is NULL.  The payload bytes are copied: the inputs may be reused once the
+ *                        launches have run.  Two launches on hip_stream.
+ *  afsk_live_tx_pull     writes samples [pos, pos + n_samples) of channel c to out + c * out_row_stride (samples,
+ *                        2-byte alignment: a column window of a [channels, time] buffer works; out_row_stride >=
+ *                        n_samples when n_channels > 1; out may be NULL when n_samples is 0) and nothing else of out,
+ *                        then advances pos, retires the messages that have ended and writes out_pending[c] (int32
+ *                        [n_channels]): the messages still queued or on air.  Two launches in order on hip_stream.
+ *  afsk_live_tx_reset    drops every queued message (a half-sent one too) of every channel (d_mask_or_null NULL) or of
+ *                        the channels whose DEVICE uint8 mask entry is non-zero: their streams restart at 0 and their
+ *                        out_pending_or_null entries (when given) become 0
+ *  afsk_live_tx_destroy  after the launches that use the transmitter have completed (NULL is fine)
+ * Submits, pulls and resets of one transmitter must run in order (one stream, or ordered streams).
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_TX_SIGNATURES.)
+ */
+#define AFSK_LIVE_TX_QUEUED 0      /* accepted: start / n_samples are valid                                     */
+#define AFSK_LIVE_TX_QUEUE_FULL 1  /* the channel already holds queue_depth messages not yet fully emitted       */
+#define AFSK_LIVE_TX_TOO_LONG 2    /* payload_len outside 0 ... max_payload_len                                  */
+#define AFSK_LIVE_TX_BAD_CHANNEL 3 /* channel outside 0 ... n_channels - 1                                      */
+#define AFSK_LIVE_TX_UNSORTED 4    /* at or after the first message whose channel is below its predecessor's    */
+typedef struct afsk_live_tx afsk_live_tx;
+extern int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len,
+                               int64_t *out_state_bytes);
+extern int afsk_live_tx_create(int32_t n_channels, int32_t bit_frames, int32_t ts_cycles, int32_t queue_depth,
+                               int32_t max_payload_len, afsk_live_tx **out);
+extern int afsk_live_tx_info(const afsk_live_tx *tx, int32_t *out_n_channels, int32_t *out_queue_depth,
+                             int32_t *out_max_payload_len, int64_t *out_state_bytes);
+extern int afsk_live_tx_submit(afsk_live_tx *tx, int32_t n_msgs, const int32_t *channel, const int64_t *payload_offset,
+                               const int32_t *payload_len, const uint8_t *payload, const int32_t *out_index,
+                               int32_t *out_status, int64_t *out_start, int32_t *out_n_samples, void *hip_stream);
+extern int afsk_live_tx_pull(afsk_live_tx *tx, int16_t *out, int64_t out_row_stride, int32_t n_samples,
+                             int32_t *out_pending, void *hip_stream);
+extern int afsk_live_tx_reset(afsk_live_tx *tx, const uint8_t *d_mask_or_null, int32_t *out_pending_or_null,
+                              void *hip_stream);
+extern int afsk_live_tx_destroy(afsk_live_tx *tx);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
