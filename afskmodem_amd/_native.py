@@ -134,6 +134,16 @@ LIVE_TX_SIGNATURES = {
 LIVE_TX_QUEUED, LIVE_TX_QUEUE_FULL, LIVE_TX_TOO_LONG, LIVE_TX_BAD_CHANNEL, LIVE_TX_UNSORTED = 0, 1, 2, 3, 4
 
 
+# The live objects with a rate per channel (afsk_live_create_mixed, afsk_live_tx_create_mixed,
+# afsk_live_tx_state_bytes_mixed), bound by lib() from a table of their own for the same reason.
+LIVE_MIXED_SIGNATURES = {
+    "afsk_live_create_mixed": (C.c_int, [C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(C.c_void_p)]),
+    "afsk_live_tx_create_mixed": (C.c_int, [C.c_int32, _i32p, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "afsk_live_tx_state_bytes_mixed": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i64p]),
+}
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -144,7 +154,7 @@ def lib() -> C.CDLL:
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
-                                  *LIVE_TX_SIGNATURES.items()):
+                                  *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -14,6 +14,10 @@
 //                         16-byte store; reads the channel state, writes only the caller's buffer
 //   live_tx_commit_kernel one thread per channel: advances pos, retires the messages that have ended, writes pending
 //
+// A mixed transmitter (afsk_live_tx_create_mixed) keeps each channel's bit_frames and training symbols in a TxGeom
+// array past the uniform layout; submit and live_tx_tile_kernel_mixed read them per channel, and the tile kernel picks
+// the small- or large-q tone code per wave (a wave renders tiles of one channel, so the branch is wave-uniform).
+//
 // Every message is at least 4 symbols + the 4800-sample silent tail long, so the tones of two messages of a channel
 // are at least 4800 samples apart and a tile of at most 4096 samples meets the tones of one message at most.
 //
@@ -42,6 +46,12 @@ struct TxDesc {             // 16 bytes per ring entry
     int32_t payload_len;
 };
 static_assert(sizeof(TxDesc) == 16, "TxDesc layout");
+
+struct TxGeom {             // 8 bytes per channel of a mixed transmitter
+    int32_t bf;             // bit_frames: a multiple of 4 in 4 ... 48000
+    int32_t n_train_sym;    // 2 * ts_cycles (ts_cycles >= 0)
+};
+static_assert(sizeof(TxGeom) == 8, "TxGeom layout");
 
 constexpr int kTxThreads = 64;                                  // one wave per block
 constexpr int kTxIters = 8;                                     // 16-byte stores per lane and tile
@@ -80,6 +90,9 @@ inline int live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_p
     return AFSK_OK;
 }
 
+// A mixed transmitter's allocation: the uniform layout, then TxGeom [n] (256-byte aligned: L.bytes is).
+inline int64_t live_tx_mixed_bytes(const TxLayout& L) { return L.bytes + tx_align256(8 * L.n); }
+
 // ------------------------------------------------------------------------------------------------------- submit
 
 __global__ __launch_bounds__(256) void live_tx_order_kernel(const int32_t* channel, int32_t n, int32_t* first_bad) {
@@ -115,6 +128,7 @@ struct TxSubmitArgs {
     int32_t max_payload;
     int32_t bf;
     int32_t n_train_sym;
+    const TxGeom* geom;         // mixed: per-channel bf / n_train_sym (NULL: the two above)
 };
 
 __global__ __launch_bounds__(256) void live_tx_submit_kernel(TxSubmitArgs a) {
@@ -133,13 +147,14 @@ __global__ __launch_bounds__(256) void live_tx_submit_kernel(TxSubmitArgs a) {
     if (i > 0 && a.channel[i - 1] == ch) return;                // not the first of its run
     const bool ok = ch >= 0 && ch < a.n;
     TxChan st = ok ? a.chan[ch] : TxChan{};
+    const TxGeom g = ok && a.geom ? a.geom[ch] : TxGeom{a.bf, a.n_train_sym};
     for (int32_t j = i; j < first_bad && a.channel[j] == ch; j++) {
         const int32_t plen = a.payload_len[j];
         if (!ok) { put(j, AFSK_LIVE_TX_BAD_CHANNEL, -1, 0); continue; }
         if (plen < 0 || plen > a.max_payload) { put(j, AFSK_LIVE_TX_TOO_LONG, -1, 0); continue; }
         if (st.count >= a.depth) { put(j, AFSK_LIVE_TX_QUEUE_FULL, -1, 0); continue; }
         const int64_t start = st.pos > st.end ? st.pos : st.end;
-        const int32_t ns = a.bf * (a.n_train_sym + 4 + 14 * plen) + AFSK_TAIL_SILENCE;   // <= AFSK_MAX_STREAM_LEN
+        const int32_t ns = g.bf * (g.n_train_sym + 4 + 14 * plen) + AFSK_TAIL_SILENCE;   // <= AFSK_MAX_STREAM_LEN
         int32_t slot = st.head + st.count;
         if (slot >= a.depth) slot -= a.depth;
         const int64_t e = (int64_t)ch * a.depth + slot;
@@ -219,8 +234,22 @@ __device__ __forceinline__ void tx_store(int16_t* dst0, uint32_t j0, uint32_t le
     }
 }
 
+// The tile's samples, 8 per lane and store (the message's tones from relative sample x0 on, zero past lim).
 template <bool SMALLQ>
-__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel(TxPullArgs a) {
+__device__ __forceinline__ void tx_render(int16_t* dst0, uint32_t len, int32_t x0, int32_t lim, int32_t xb, uint32_t q,
+                                          float rcp_q, uint32_t mq, const uint32_t* qbits, bool odd) {
+#pragma unroll 2
+    for (int it = 0; it < kTxIters; it++) {
+        const uint32_t j0 = ((uint32_t)it * kTxThreads + threadIdx.x) * 8u;
+        if (j0 >= len) break;
+        tx_store(dst0, j0, len, msg_words<SMALLQ>(x0 + (int32_t)j0, lim, xb, q, rcp_q, mq, qbits, odd));
+    }
+}
+
+// KIND 0 / 1: a uniform transmitter whose q = bf / 4 is >= 8 / < 8 (a.bf, a.n_train_sym); KIND 2: a mixed one, the
+// channel's geometry from geom[c] and the tone code chosen per wave
+template <int KIND>
+__device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom) {
     __shared__ uint8_t win[kWinBytes];
     __shared__ unsigned long long kinds[kTxTile / 4 / 64 + 2];
     __shared__ uint32_t qbits[q_words(kTxTile)];
@@ -228,10 +257,16 @@ __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     const int bid = xcd_block((int)blockIdx.x, (int)gridDim.x);
     const int c = bid / a.blocks_per_row;
     const int b = bid - c * a.blocks_per_row;
-    const uint32_t bf = a.bf;
-    const uint32_t n_train_sym = a.n_train_sym;
-    // the channel state and its whole descriptor ring, loaded at once (neither address depends on the other load)
+    uint32_t bf = a.bf;
+    uint32_t n_train_sym = a.n_train_sym;
+    // the channel state (and geometry) and its whole descriptor ring, loaded at once (no address depends on another
+    // of these loads)
     const TxChan ch = a.chan[c];
+    if (KIND == 2) {
+        const TxGeom g = geom[c];
+        bf = (uint32_t)g.bf;
+        n_train_sym = (uint32_t)g.n_train_sym;
+    }
     const TxDesc* gring = a.desc + (int64_t)c * a.depth;
     const uint8_t* gpay = a.slots + (int64_t)c * a.depth * a.max_payload;
     const bool lds_ring = a.depth <= kTxLdsRing;
@@ -320,13 +355,23 @@ __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8
         const uint32_t mq = (65536u + q - 1u) / q;
         const int32_t xb = (int32_t)(Sb * bf);
         const bool odd = (x0 & 1) != 0;
-#pragma unroll 2
-        for (int it = 0; it < kTxIters; it++) {
-            const uint32_t j0 = ((uint32_t)it * kTxThreads + threadIdx.x) * 8u;
-            if (j0 >= len) break;
-            tx_store(dst0, j0, len, msg_words<SMALLQ>(x0 + (int32_t)j0, lim, xb, q, rcp_q, mq, qbits, odd));
+        if (KIND == 2) {                                               // block- (= wave-) uniform
+            if (q < 8u) tx_render<true>(dst0, len, x0, lim, xb, q, rcp_q, mq, qbits, odd);
+            else tx_render<false>(dst0, len, x0, lim, xb, q, rcp_q, mq, qbits, odd);
+        } else {
+            tx_render<KIND == 1>(dst0, len, x0, lim, xb, q, rcp_q, mq, qbits, odd);
         }
     }
+}
+
+template <bool SMALLQ>
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel(TxPullArgs a) {
+    live_tx_tile<SMALLQ ? 1 : 0>(a, nullptr);
+}
+
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel_mixed(
+    TxPullArgs a, const TxGeom* geom) {
+    live_tx_tile<2>(a, geom);
 }
 
 __global__ __launch_bounds__(256) void live_tx_commit_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
@@ -359,7 +404,9 @@ __global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const 
 struct afsk_live_tx {
     int device = -1;
     afsk::TxLayout L;
-    int32_t bit_frames = 0, n_train_sym = 0;
+    int32_t bit_frames = 0, n_train_sym = 0;   // (a mixed transmitter: 0, see o_geom)
+    int64_t o_geom = 0;                         // mixed: offset of TxGeom [n] in d (0: uniform)
+    int64_t bytes = 0;                          // the allocation: L.bytes, or live_tx_mixed_bytes(L)
     void* d = nullptr;
     ~afsk_live_tx() {
         if (d) (void)hipFree(d);
@@ -375,30 +422,93 @@ int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_pay
     return AFSK_OK;
 }
 
+namespace {
+
+bool tx_bf_valid(int32_t bf) { return bf >= 4 && (bf & 3) == 0 && bf <= AFSK_SAMPLE_RATE; }
+int tx_fail_bit_frames() {
+    return afsk::fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 in 4 ... 48000");
+}
+int64_t tx_train_sym(int32_t ts_cycles) { return 2 * (int64_t)(ts_cycles > 0 ? ts_cycles : 0); }   // ref:457
+int tx_check_longest(int32_t bf, int64_t n_train_sym, int32_t max_payload_len) {
+    const int64_t longest = (int64_t)bf * (n_train_sym + 4 + 14 * (int64_t)max_payload_len) + AFSK_TAIL_SILENCE;
+    if (longest > AFSK_MAX_STREAM_LEN)
+        return afsk::fail(AFSK_E_INVALID_ARG, "the longest message would exceed AFSK_MAX_STREAM_LEN samples");
+    return AFSK_OK;
+}
+
+// The device part of create: allocate `tx->bytes`, zero the channel states, upload the mixed geometry (synchronous).
+int tx_allocate(afsk_live_tx* tx, const afsk::TxGeom* geom_host) {
+    if (int rc = afsk::require_device()) return rc;
+    hipError_t e = hipGetDevice(&tx->device);
+    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (hipGetDevice)");
+    e = hipMalloc(&tx->d, (size_t)tx->bytes);
+    if (e != hipSuccess) { tx->d = nullptr; return afsk::hip_fail(e, "afsk_live_tx_create (hipMalloc)"); }
+    // only the channel states (and the geometry) need a value: ring entries and payload slots are written before
+    // they are read
+    e = hipMemsetAsync(tx->d, 0, (size_t)tx->L.o_desc, nullptr);
+    if (e == hipSuccess && geom_host)
+        e = hipMemcpyAsync(static_cast<uint8_t*>(tx->d) + tx->o_geom, geom_host, (size_t)(8 * tx->L.n),
+                           hipMemcpyHostToDevice, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (initialise the state)");
+    return AFSK_OK;
+}
+
+}  // namespace
+
 int afsk_live_tx_create(int32_t n_channels, int32_t bit_frames, int32_t ts_cycles, int32_t queue_depth,
                         int32_t max_payload_len, afsk_live_tx** out) {
     if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     *out = nullptr;
-    if (bit_frames < 4 || (bit_frames & 3) != 0 || bit_frames > AFSK_SAMPLE_RATE)
-        return afsk::fail(AFSK_E_INVALID_BAUD, "bit_frames must be a multiple of 4 in 4 ... 48000");
+    if (!tx_bf_valid(bit_frames)) return tx_fail_bit_frames();
     return afsk::no_throw([&] {
         std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
         if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
-        const int64_t ts = ts_cycles > 0 ? ts_cycles : 0;               // ref:457: range(negative) runs zero times
-        const int64_t longest = (int64_t)bit_frames * (2 * ts + 4 + 14 * (int64_t)max_payload_len) + AFSK_TAIL_SILENCE;
-        if (longest > AFSK_MAX_STREAM_LEN)
-            return afsk::fail(AFSK_E_INVALID_ARG, "the longest message would exceed AFSK_MAX_STREAM_LEN samples");
-        if (int rc = afsk::require_device()) return rc;
-        hipError_t e = hipGetDevice(&tx->device);
-        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (hipGetDevice)");
+        const int64_t nts = tx_train_sym(ts_cycles);
+        if (int rc = tx_check_longest(bit_frames, nts, max_payload_len)) return rc;
         tx->bit_frames = bit_frames;
-        tx->n_train_sym = (int32_t)(2 * ts);
-        e = hipMalloc(&tx->d, (size_t)tx->L.bytes);
-        if (e != hipSuccess) { tx->d = nullptr; return afsk::hip_fail(e, "afsk_live_tx_create (hipMalloc)"); }
-        // only the channel states need a value: ring entries and payload slots are written before they are read
-        e = hipMemsetAsync(tx->d, 0, (size_t)tx->L.o_desc, nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (zero the state)");
+        tx->n_train_sym = (int32_t)nts;
+        tx->bytes = tx->L.bytes;
+        if (int rc = tx_allocate(tx.get(), nullptr)) return rc;
+        *out = tx.release();
+        return AFSK_OK;
+    });
+}
+
+int afsk_live_tx_state_bytes_mixed(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len,
+                                   int64_t* out_state_bytes) {
+    afsk::TxLayout L;
+    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
+    if (out_state_bytes) *out_state_bytes = afsk::live_tx_mixed_bytes(L);
+    return AFSK_OK;
+}
+
+int afsk_live_tx_create_mixed(int32_t n_channels, const int32_t* bit_frames_host, const int32_t* ts_cycles_host,
+                              int32_t queue_depth, int32_t max_payload_len, afsk_live_tx** out) {
+    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    *out = nullptr;
+    if (n_channels < 1) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
+    if (!bit_frames_host || !ts_cycles_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    for (int32_t c = 0; c < n_channels; c++)
+        if (!tx_bf_valid(bit_frames_host[c])) return tx_fail_bit_frames();
+    bool same = true;
+    for (int32_t c = 1; c < n_channels && same; c++)
+        same = bit_frames_host[c] == bit_frames_host[0] && tx_train_sym(ts_cycles_host[c]) == tx_train_sym(ts_cycles_host[0]);
+    // one geometry for every channel: the uniform transmitter (its launches, its state bytes)
+    if (same) return afsk_live_tx_create(n_channels, bit_frames_host[0], ts_cycles_host[0], queue_depth, max_payload_len,
+                                         out);
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
+        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
+        std::unique_ptr<afsk::TxGeom[]> geom(new afsk::TxGeom[(size_t)n_channels]);
+        for (int32_t c = 0; c < n_channels; c++) {
+            const int64_t nts = tx_train_sym(ts_cycles_host[c]);
+            if (int rc = tx_check_longest(bit_frames_host[c], nts, max_payload_len)) return rc;
+            geom[(size_t)c] = afsk::TxGeom{bit_frames_host[c], (int32_t)nts};
+        }
+        tx->o_geom = tx->L.bytes;
+        tx->bytes = afsk::live_tx_mixed_bytes(tx->L);
+        if (int rc = tx_allocate(tx.get(), geom.get())) return rc;
         *out = tx.release();
         return AFSK_OK;
     });
@@ -410,7 +520,7 @@ int afsk_live_tx_info(const afsk_live_tx* tx, int32_t* out_n_channels, int32_t* 
     if (out_n_channels) *out_n_channels = (int32_t)tx->L.n;
     if (out_queue_depth) *out_queue_depth = (int32_t)tx->L.depth;
     if (out_max_payload_len) *out_max_payload_len = (int32_t)tx->L.max_payload;
-    if (out_state_bytes) *out_state_bytes = tx->L.bytes;
+    if (out_state_bytes) *out_state_bytes = tx->bytes;
     return AFSK_OK;
 }
 
@@ -450,6 +560,7 @@ int afsk_live_tx_submit(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel
     a.max_payload = (int32_t)L.max_payload;
     a.bf = tx->bit_frames;
     a.n_train_sym = tx->n_train_sym;
+    a.geom = tx->o_geom ? reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom) : nullptr;
     hipLaunchKernelGGL(afsk::live_tx_submit_kernel, dim3((uint32_t)((n_msgs + 255) / 256)), dim3(256), 0, st, a);
     e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_submit_kernel");
@@ -492,7 +603,10 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
         a.bf = (uint32_t)tx->bit_frames;
         a.n_train_sym = (uint32_t)tx->n_train_sym;
         const dim3 grid((uint32_t)(a.blocks_per_row * L.n));
-        if (tx->bit_frames / 4 >= 8) hipLaunchKernelGGL(afsk::live_tx_tile_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a);
+        if (tx->o_geom)
+            hipLaunchKernelGGL(afsk::live_tx_tile_kernel_mixed, grid, dim3(afsk::kTxThreads), 0, st, a,
+                               reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom));
+        else if (tx->bit_frames / 4 >= 8) hipLaunchKernelGGL(afsk::live_tx_tile_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a);
         else hipLaunchKernelGGL(afsk::live_tx_tile_kernel<true>, grid, dim3(afsk::kTxThreads), 0, st, a);
         e = hipGetLastError();
         if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_tile_kernel");

@@ -13,6 +13,11 @@ channels without reporting.  Any sequence of pushes followed by a flush reports 
 Transmit: a ``LiveTransmitter`` keeps a queue of messages per channel on the device; each ``pull`` writes the next T
 samples of every channel (``afsk_live_tx_pull``), the queued messages back to back, each exactly what
 ``Transmitter.save`` writes for it.  Nothing here opens an audio device.
+
+Both take one rate for all channels or one per channel (a sequence of n_channels), interleaved in any order, so a
+``[channels, time]`` buffer of mixed rates is pushed or pulled as it is (``afsk_live_create_mixed``,
+``afsk_live_tx_create_mixed``); ``from_receivers`` / ``from_transmitters`` build one channel per Receiver /
+Transmitter.  ``channel_bit_frames`` holds every channel's rate on both kinds.
 """
 from __future__ import annotations
 
@@ -26,6 +31,20 @@ from .modem import _text_or_bytes
 
 DEFAULT_MAX_BURST_LEN = 2 * _native.SAMPLE_RATE     # 2 s: longer bursts are reported as overflowed, not decoded
 DEFAULT_MAX_CHUNK_LEN = 8192
+
+
+def _per_channel(value, n_channels: int, name: str):
+    """None for a scalar ``value``, else its entries as a list of length n_channels (ValueError otherwise)."""
+    if np.ndim(value) == 0:
+        return None
+    v = list(np.asarray(value).tolist()) if isinstance(value, np.ndarray) else list(value)
+    if np.ndim(v) != 1 or len(v) != n_channels:
+        raise ValueError(f"{name} must be one value or a sequence of n_channels = {n_channels}, got {np.shape(v)}")
+    return v
+
+
+def _i32_ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def layout(n_channels: int, max_burst_len: int, max_chunk_len: int) -> tuple[int, int]:
@@ -73,8 +92,12 @@ class LiveResult:
 
 
 class LiveReceiver(batch._NativePlan):
-    """A live receiver of ``n_channels`` independent channels at one baud rate (``bit_frames`` = 48000 / baud), with
-    the thresholds of ``Receiver`` (``threshold_gt`` / ``threshold_lt`` rules, as ``gate_batch``).
+    """A live receiver of ``n_channels`` independent channels at one baud rate (``bit_frames`` = 48000 / baud) or one
+    per channel (``bit_frames`` a sequence of n_channels, in any order), with the thresholds of ``Receiver``
+    (``threshold_gt`` / ``threshold_lt`` rules, as ``gate_batch``) shared by all channels.  Channel c then reports
+    what a one-rate receiver at its rate reports for it.  ``bit_frames`` stays the int of a one-rate receiver (also
+    when every entry of a sequence is equal: that is the one-rate receiver) and is None for a mixed one;
+    ``channel_bit_frames`` (int32 [n_channels]) holds every channel's.
 
     ``max_burst_len``: the longest burst that is stored and demodulated (samples, >= 4096); a longer one is still
     gated exactly, and reported with its true start and length and ``LIVE_OVERFLOW``.  ``max_chunk_len``: the
@@ -86,9 +109,17 @@ class LiveReceiver(batch._NativePlan):
     def __init__(self, n_channels: int, bit_frames: int, amp_start_threshold=18000, amp_end_threshold=14000,
                  max_burst_len: int = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN, device=None):
         torch = batch._torch()
-        batch.validate_bit_frames(int(bit_frames))
         self.n_channels = int(n_channels)
-        self.bit_frames = int(bit_frames)
+        rates = _per_channel(bit_frames, self.n_channels, "bit_frames")
+        if rates is None:
+            batch.validate_bit_frames(int(bit_frames))
+            rates = [int(bit_frames)] * max(self.n_channels, 1)
+        elif any(int(b) != b for b in rates):
+            raise ValueError("bit_frames must hold integers")
+        batch.validate_bit_frames(np.asarray(rates, np.int64))
+        self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
+        mixed = len(set(rates)) > 1
+        self.bit_frames = None if mixed else int(rates[0]) if rates else None
         self.max_burst_len = int(max_burst_len)
         self.max_chunk_len = int(max_chunk_len)
         self.slots, self.state_bytes = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)
@@ -96,11 +127,34 @@ class LiveReceiver(batch._NativePlan):
         batch._drain_parked_plans()
         super().__init__(device)
         # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
-        self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self.bit_frames)
+        self._min_bf = int(min(rates))
+        self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self._min_bf)
         with torch.cuda.device(self.device):
-            _native.check(_native.lib().afsk_live_create(
-                self.n_channels, self.bit_frames, batch.threshold_gt(amp_start_threshold),
-                batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+            if mixed:
+                _native.check(_native.lib().afsk_live_create_mixed(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), batch.threshold_gt(amp_start_threshold),
+                    batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+                nbytes = C.c_int64()
+                _native.check(_native.lib().afsk_live_info(self.handle, None, None, C.byref(nbytes)))
+                self.state_bytes = int(nbytes.value)
+            else:
+                _native.check(_native.lib().afsk_live_create(
+                    self.n_channels, self.bit_frames, batch.threshold_gt(amp_start_threshold),
+                    batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+
+    @classmethod
+    def from_receivers(cls, receivers, **capacities) -> "LiveReceiver":
+        """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  Their thresholds must agree
+        (ValueError otherwise): the gate's thresholds are the receiver's.  ``capacities``: ``max_burst_len`` /
+        ``max_chunk_len`` (samples) and ``device``."""
+        receivers = list(receivers)
+        if not receivers:
+            raise ValueError("from_receivers needs at least one Receiver")
+        th = {(r.amp_start_threshold, r.amp_end_threshold) for r in receivers}
+        if len(th) != 1:
+            raise ValueError(f"the receivers' thresholds differ: {sorted(th)}")
+        start, end = th.pop()
+        return cls(len(receivers), [r.bit_frames for r in receivers], start, end, **capacities)
 
     def alloc_result(self, diagnostics: bool = False, margin_stride: int | None = None) -> LiveResult:
         """Output buffers for ``push(out=...)`` (double-buffered pushes, graph capture).  ``diagnostics``: also the
@@ -109,7 +163,7 @@ class LiveReceiver(batch._NativePlan):
         n, s, dev = self.n_channels, self.slots, self.device
         demod = batch.alloc_result(n * s, self.out_stride, dev)
         if diagnostics:
-            ms = int(margin_stride) if margin_stride is not None else self.max_burst_len // self.bit_frames + 1
+            ms = int(margin_stride) if margin_stride is not None else self.max_burst_len // self._min_bf + 1
             demod.corrected = torch.zeros(n * s, dtype=torch.int32, device=dev)
             demod.margins = torch.zeros((n * s, ms), dtype=torch.int32, device=dev)
         z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
@@ -226,6 +280,15 @@ def tx_bit_frames(baud_rate) -> int:
     return _native.SAMPLE_RATE // b
 
 
+def tx_state_bytes_mixed(n_channels: int, queue_depth: int, max_payload_len: int) -> int:
+    """Device state bytes of a live transmitter whose channels' geometries differ (``afsk_live_tx_state_bytes_mixed``:
+    host-only)."""
+    nbytes = C.c_int64()
+    _native.check(_native.lib().afsk_live_tx_state_bytes_mixed(int(n_channels), int(queue_depth),
+                                                               int(max_payload_len), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
 @dataclass
 class SubmitResult:
     """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order."""
@@ -243,6 +306,12 @@ class LiveTransmitter(batch._NativePlan):
     ``Transmitter(baud_rate, training_time).wav_samples`` makes of each queued message, played back to back, pulled
     as the next T samples of every channel (``pull``) -- the mirror image of ``LiveReceiver.push``.
 
+    ``baud_rate`` and ``training_time`` may also be sequences of n_channels (either one, in any order): channel c then
+    plays what ``Transmitter(baud_rate[c], training_time[c])`` plays.  ``baud_rate``, ``bit_frames`` and
+    ``ts_cycles`` stay those of a one-geometry transmitter (also when every channel's geometry is equal: that is the
+    one-geometry transmitter) and are None for a mixed one; ``channel_bit_frames`` and ``channel_ts_cycles`` (int32
+    [n_channels]) hold every channel's.
+
     Each channel queues up to ``queue_depth`` messages not yet fully emitted, of at most ``max_payload_len`` bytes,
     on the device.  A channel's stream is numbered from 0 at creation or ``reset``; a message queued on a busy channel
     follows the previous one with no gap, one queued on an idle channel starts at the next sample pulled.  Submits and
@@ -255,29 +324,74 @@ class LiveTransmitter(batch._NativePlan):
                  queue_depth: int = DEFAULT_QUEUE_DEPTH, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, device=None):
         torch = batch._torch()
         from .modem import Transmitter
-        self.bit_frames = tx_bit_frames(baud_rate)
         if int(n_channels) < 1:
             raise ValueError("n_channels must be at least 1")
         self.n_channels = int(n_channels)
-        self.baud_rate = int(baud_rate)
-        self.ts_cycles = Transmitter(self.baud_rate, training_time).ts_cycles     # ref:438 (negative: no cycles)
+        bauds = _per_channel(baud_rate, self.n_channels, "baud_rate")
+        times = _per_channel(training_time, self.n_channels, "training_time")
+        if bauds is None and times is None:
+            self.bit_frames = tx_bit_frames(baud_rate)
+            self.baud_rate = int(baud_rate)
+            self.ts_cycles = Transmitter(self.baud_rate, training_time).ts_cycles  # ref:438 (negative: no cycles)
+            self.channel_bit_frames = np.full(self.n_channels, self.bit_frames, np.int32)
+            self.channel_ts_cycles = np.full(self.n_channels, self.ts_cycles, np.int32)
+            mixed = False
+        else:
+            bauds = bauds if bauds is not None else [baud_rate] * self.n_channels
+            times = times if times is not None else [training_time] * self.n_channels
+            self.channel_bit_frames = np.asarray([tx_bit_frames(b) for b in bauds], np.int32)
+            self.channel_ts_cycles = np.asarray([Transmitter(int(b), t).ts_cycles for b, t in zip(bauds, times)],
+                                                np.int32)
+            # one geometry for all channels (bit_frames and training symbols): the one-geometry transmitter
+            train = np.maximum(self.channel_ts_cycles, 0)
+            mixed = bool((self.channel_bit_frames != self.channel_bit_frames[0]).any() or (train != train[0]).any())
+            self.bit_frames = None if mixed else int(self.channel_bit_frames[0])
+            self.baud_rate = None if mixed else int(bauds[0])
+            self.ts_cycles = None if mixed else int(self.channel_ts_cycles[0])
         self.queue_depth = int(queue_depth)
         self.max_payload_len = int(max_payload_len)
         self.state_bytes = tx_layout(self.n_channels, self.queue_depth, self.max_payload_len)
+        if mixed:
+            self.state_bytes = tx_state_bytes_mixed(self.n_channels, self.queue_depth, self.max_payload_len)
         _native.require_device()
         batch._drain_parked_plans()
         super().__init__(device)
         with torch.cuda.device(self.device):
-            _native.check(_native.lib().afsk_live_tx_create(
-                self.n_channels, self.bit_frames, int(self.ts_cycles), self.queue_depth, self.max_payload_len,
-                C.byref(self._h)))
+            if mixed:
+                _native.check(_native.lib().afsk_live_tx_create_mixed(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_ts_cycles),
+                    self.queue_depth, self.max_payload_len, C.byref(self._h)))
+            else:
+                _native.check(_native.lib().afsk_live_tx_create(
+                    self.n_channels, self.bit_frames, int(self.ts_cycles), self.queue_depth, self.max_payload_len,
+                    C.byref(self._h)))
         # messages queued or on air per channel after the last pull (0 for channels reset since)
         self.pending = torch.zeros(self.n_channels, dtype=torch.int32, device=self.device)
 
-    def message_len(self, payload_len) -> "int | np.ndarray":
-        """Samples of a message of ``payload_len`` bytes: tones + the 4800-sample silent tail (ref:452-469)."""
-        ts = max(self.ts_cycles, 0)
-        return self.bit_frames * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
+    @classmethod
+    def from_transmitters(cls, transmitters, **capacities) -> "LiveTransmitter":
+        """One channel per ``Transmitter`` (channel c at ``transmitters[c]``'s baud rate and training time).
+        ``capacities``: ``queue_depth``, ``max_payload_len`` and ``device``."""
+        transmitters = list(transmitters)
+        if not transmitters:
+            raise ValueError("from_transmitters needs at least one Transmitter")
+        return cls(len(transmitters), [t.baud_rate for t in transmitters], [t.training_time for t in transmitters],
+                   **capacities)
+
+    def message_len(self, payload_len, channels=None) -> "int | np.ndarray":
+        """Samples of a message of ``payload_len`` bytes: tones + the 4800-sample silent tail (ref:452-469), at the
+        geometry of ``channels`` (an int or an array, broadcast against ``payload_len``; None: the one geometry of a
+        one-geometry transmitter, every channel's -- an [n_channels] array, broadcast -- of a mixed one)."""
+        if channels is None and self.bit_frames is not None:
+            ts = max(self.ts_cycles, 0)
+            return self.bit_frames * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
+        idx = np.arange(self.n_channels) if channels is None else np.asarray(channels, np.int64)
+        if np.any((idx < 0) | (idx >= self.n_channels)):
+            raise ValueError(f"channels must lie in 0 ... {self.n_channels - 1}")
+        bf = self.channel_bit_frames.astype(np.int64)[idx]
+        ts = np.maximum(self.channel_ts_cycles.astype(np.int64)[idx], 0)
+        out = bf * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
+        return int(out) if np.ndim(out) == 0 else out
 
     def submit(self, channels, payloads, stream=None) -> SubmitResult:
         """Queue ``payloads[i]`` (str -- UTF-8 -- or bytes) on channel ``channels[i]`` (a sequence, or one int for

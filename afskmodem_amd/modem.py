@@ -294,6 +294,10 @@ class Receiver:
         return self.__bit_frames
 
     @property
+    def amp_start_threshold(self) -> int:
+        return self.__amp_start_threshold
+
+    @property
     def amp_end_threshold(self) -> int:
         return self.__amp_end_threshold
 
@@ -513,6 +517,14 @@ class Transmitter:
         self.__training_cycle = np.concatenate([self.__mark_tone, self.__space_tone])
         self.__sound_out: SoundOutput | None = None                      # lazy, ref:442
         self.__log = Log("afskmodem.Transmitter")
+
+    @property
+    def baud_rate(self) -> int:
+        return self.__baud_rate
+
+    @property
+    def training_time(self) -> float:
+        return self.__training_time
 
     @property
     def ts_cycles(self) -> int:

@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define AFSK_ABI_VERSION 2 /* 2: afsk_group_plan_* / afsk_demod_batch_grouped, AFSK_ST_BAD_LENGTH, afsk_wav_egress */
+#define AFSK_ABI_VERSION 2 /* 2: afsk_group_plan_* / afsk_demod_batch_grouped, AFSK_ST_BAD_LENGTH, afsk_wav_egress;
+                              the live entries and, after them, the per-channel-rate *_mixed entries are additions
+                              to version 2 */
 
 /* return codes */
 #define AFSK_OK 0
@@ -480,6 +482,38 @@ extern int afsk_live_reset(afsk_live *live, const uint8_t *d_mask_or_null, void 
 extern int afsk_live_destroy(afsk_live *live);
 
 /*
+ * Per-channel rates (added after ABI version 2; the version is unchanged): a live receiver or transmitter whose
+ * channels each have their own bit_frames (and, for the transmitter, training length), interleaved in any order --
+ * the [channels, time] buffer of a channelizer or network fan-in as it comes.  The objects they return are the
+ * afsk_live / afsk_live_tx objects of this header: push, reset, info, submit, pull and destroy serve both kinds.
+ *
+ *  afsk_live_create_mixed   bit_frames_host: HOST array [n_channels], each as afsk_demod_batch_uniform
+ *                           (AFSK_E_INVALID_BAUD); n_channels < 1 or a NULL array: AFSK_E_INVALID_ARG; the rest as
+ *                           afsk_live_create (one pair of thresholds for all channels).  A burst of channel c is
+ *                           demodulated at bit_frames_host[c] -- bit for bit what a uniform receiver of that rate reports
+ *                           for the same channel.  Every entry equal: exactly afsk_live_create.  Otherwise the
+ *                           receiver also owns a group plan over its n_channels * slots demodulator slots (slot
+ *                           c * slots + k at bit_frames_host[c]; afsk_group_plan_create, 8 bytes per slot on the
+ *                           device, which afsk_live_info adds to afsk_live_layout's bytes), and the push's second
+ *                           launch is afsk_demod_batch_grouped over the slots -- still two launches, nothing on the
+ *                           host in between, capturable.
+ *  afsk_live_tx_create_mixed  bit_frames_host, ts_cycles_host: HOST arrays [n_channels]; each bit_frames a multiple of
+ *                           4 in 4 ... 48000 (AFSK_E_INVALID_BAUD), each ts_cycles as afsk_live_tx_create, and every
+ *                           channel's longest message bit_frames * (2 * ts_cycles + 4 + 14 * max_payload_len) + 4800 <=
+ *                           AFSK_MAX_STREAM_LEN; n_channels < 1 or a NULL array: AFSK_E_INVALID_ARG.  Channel c plays
+ *                           what a uniform transmitter of its geometry plays.  Every channel with the same bit_frames
+ *                           and training length: exactly afsk_live_tx_create.  Otherwise the state is
+ *                           afsk_live_tx_layout's plus int32 [n_channels, 2] (bit_frames, training symbols), which
+ *                           afsk_live_tx_info reports.
+ *  afsk_live_tx_state_bytes_mixed  host-only (no device needed): the state bytes of such a mixed transmitter
+ *                           (afsk_live_tx_layout + the per-channel part, 256-byte aligned)
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_MIXED_SIGNATURES.)
+ */
+extern int afsk_live_create_mixed(int32_t n_channels, const int32_t *bit_frames_host, int32_t amp_start_threshold,
+                                  int32_t amp_end_threshold, int32_t max_burst_len, int32_t max_chunk_len,
+                                  afsk_live **out);
+
+/*
  * The live transmitter (an addition: ABI version unchanged): Transmitter.transmit (:472-478) for n_channels
  * independent channels at one bit_frames and training length.  Every channel has a device-resident queue of up to
  * queue_depth messages; each pull writes the next n_samples samples of every channel's stream, the queued messages
@@ -539,6 +573,11 @@ extern int afsk_live_tx_pull(afsk_live_tx *tx, int16_t *out, int64_t out_row_str
 extern int afsk_live_tx_reset(afsk_live_tx *tx, const uint8_t *d_mask_or_null, int32_t *out_pending_or_null,
                               void *hip_stream);
 extern int afsk_live_tx_destroy(afsk_live_tx *tx);
+/* per-channel rates: see afsk_live_create_mixed above */
+extern int afsk_live_tx_create_mixed(int32_t n_channels, const int32_t *bit_frames_host, const int32_t *ts_cycles_host,
+                                     int32_t queue_depth, int32_t max_payload_len, afsk_live_tx **out);
+extern int afsk_live_tx_state_bytes_mixed(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len,
+                                          int64_t *out_state_bytes);
 
 /*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
