@@ -311,11 +311,14 @@ def _cached_plan(bit_frames, n: int, dev, stream_len_host=None) -> "GroupPlan":
 
 
 class _NativePlan:
-    """What ``GroupPlan`` and ``SplitPlan`` share: the native handle, the device the plan belongs to, and its release
-    through the native destroy function named by ``_destroy``."""
+    """What the native handles share (``GroupPlan``, ``SplitPlan``, ``live.LiveReceiver``, ``live.LiveTransmitter``):
+    the constructor's prologue (a device is required, plans parked inside a capture are freed), the native handle, the
+    device it belongs to, and its release through the native destroy function named by ``_destroy``."""
     _destroy: str
 
     def __init__(self, device):
+        _native.require_device()
+        _drain_parked_plans()
         self.device = _default_device(device)
         self._h = C.c_void_p()
 
@@ -370,8 +373,7 @@ class GroupPlan(_NativePlan):
 
     def __init__(self, bit_frames, device=None, stream_len=None):
         torch = _torch()
-        _native.require_device()
-        _drain_parked_plans()
+        super().__init__(device)
         self.bit_frames = np.ascontiguousarray(np.asarray(bit_frames, dtype=np.int32).reshape(-1))
         self.n = int(self.bit_frames.size)
         self.stream_len = None
@@ -379,7 +381,6 @@ class GroupPlan(_NativePlan):
             self.stream_len = np.ascontiguousarray(np.asarray(stream_len, dtype=np.int32).reshape(-1))
             if self.stream_len.size != self.n:
                 raise ValueError(f"stream_len holds {self.stream_len.size} values for {self.n} streams")
-        super().__init__(device)
         i32 = C.POINTER(C.c_int32)
         with torch.cuda.device(self.device):
             _native.check(_native.lib().afsk_group_plan_create_ragged(
@@ -596,13 +597,11 @@ class SplitPlan(_NativePlan):
     def __init__(self, stream_len_host, bit_frames, device=None, segment_symbols: int = 0):
         torch = _torch()
         lens, bf, seg = _split_host_arrays(stream_len_host, bit_frames, segment_symbols)
-        _native.require_device()
-        _drain_parked_plans()
+        super().__init__(device)
         self.stream_len = lens
         self.bit_frames = bf
         self.n = int(lens.size)
         self.segment_symbols = seg
-        super().__init__(device)
         i32 = C.POINTER(C.c_int32)
         lib = _native.lib()
         with torch.cuda.device(self.device):

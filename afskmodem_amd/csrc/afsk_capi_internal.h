@@ -1,6 +1,7 @@
-// afsk_capi_internal.h -- host-side pieces the C-ABI translation units share (afsk_capi.hip, afsk_split.hip):
-// the library's last-error slot, the exception barrier of the exported entries, and the argument checks and
-// output fields every demod entry has in common.  Host code only; not part of the installed interface.
+// afsk_capi_internal.h -- host-side pieces the C-ABI translation units share (afsk_capi.hip, afsk_split.hip,
+// afsk_live.hip, afsk_live_tx.hip): the library's last-error slot, the exception barrier of the exported entries, the
+// argument checks and output fields every demod entry has in common, and the owner of a handle's device state.  Host
+// code only; not part of the installed interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,6 +74,49 @@ struct DemodOutputs {
         a.out_margins = margin_stride > 0 ? margins : nullptr;
         a.margin_stride = margin_stride;
         return a;
+    }
+};
+
+// The device state of a handle (a split plan, a live receiver or transmitter): one allocation on the device that was
+// current at creation, freed with the handle (whose launches the caller has synchronised).  afsk_capi.hip includes
+// this header but calls none of it: its test build runs against a fake runtime without hipMemsetAsync.
+struct DeviceState {
+    int device = -1;
+    void* d = nullptr;
+    int64_t bytes = 0;
+
+    DeviceState() = default;
+    DeviceState(const DeviceState&) = delete;
+    DeviceState& operator=(const DeviceState&) = delete;
+    ~DeviceState() {
+        if (d) (void)hipFree(d);
+    }
+    uint8_t* ptr() const { return static_cast<uint8_t*>(d); }
+
+    // Synchronous: require a device and record it, allocate `nbytes` (nothing for 0), zero the first `zero_bytes`,
+    // upload `host_bytes` of `host` (when not null) at offset `host_at`.  `entry` names the caller in the errors.
+    int create(const char* entry, int64_t nbytes, int64_t zero_bytes, const void* host = nullptr, int64_t host_at = 0,
+               int64_t host_bytes = 0) {
+        if (int rc = require_device()) return rc;
+        const std::string name(entry);
+        hipError_t e = hipGetDevice(&device);
+        if (e != hipSuccess) return hip_fail(e, (name + " (hipGetDevice)").c_str());
+        if (nbytes == 0) return AFSK_OK;
+        e = hipMalloc(&d, (size_t)nbytes);
+        if (e != hipSuccess) { d = nullptr; return hip_fail(e, (name + " (hipMalloc)").c_str()); }
+        bytes = nbytes;
+        if (zero_bytes > 0) e = hipMemsetAsync(d, 0, (size_t)zero_bytes, nullptr);
+        if (e == hipSuccess && host)
+            e = hipMemcpyAsync(ptr() + host_at, host, (size_t)host_bytes, hipMemcpyHostToDevice, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess)
+            return hip_fail(e, (name + (zero_bytes > 0 ? " (initialise the state)" : " (upload)")).c_str());
+        return AFSK_OK;
+    }
+    // AFSK_E_NO_DEVICE without a device, AFSK_E_INVALID_ARG unless the current device is the one of the state
+    int check_current() const {
+        if (int rc = require_device()) return rc;
+        return plan_on_current_device(device);
     }
 };
 

@@ -11,9 +11,8 @@
 //
 // A mixed receiver (afsk_live_create_mixed: a bit_frames per channel) runs the same gate; slot s belongs to channel
 // s / slots, so every slot's rate is known at creation, and the second launch is afsk_demod_batch_grouped over the
-// slots with a group plan the receiver builds then (the per-stream kernel in rate-sorted order).  kLiveMixedGrouped
-// selects the alternative that was measured against it: the per-stream kernel in slot order over a per-slot bit_frames
-// array kept past the uniform layout.
+// slots with a group plan the receiver builds then (the per-stream kernel in rate-sorted order; DESIGN.md 8.2 has
+// the measurement against the per-stream kernel in slot order).
 //
 // Per channel the device keeps (LiveChan) the gate mode, the stream position, the open burst's start, length and
 // row offset, and a 2048-sample carry with the partial block at the end of the stream.  Row layout: the open
@@ -27,6 +26,7 @@
 #include <algorithm>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "../../include/afsk_amd.h"
 #include "afsk_capi_internal.h"
@@ -57,11 +57,6 @@ struct LiveLayout {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-// The mixed receiver's demod launch: true = a group plan over the slots (afsk_group_plan_create: 8 bytes per slot
-// on the device) walked by afsk_demod_batch_grouped, rate-sorted; false = the per-stream kernel in slot order over a
-// per-slot bit_frames array (int32 [n, slots] at L.bytes, 256-byte aligned).  At 65536 channels x T 8192 over four
-// interleaved rates the grouped walk's demod launch takes 228 us against 264 us; at T 2048 the two tie.
-constexpr bool kLiveMixedGrouped = true;
 __host__ __device__ inline int64_t min64(int64_t x, int64_t y) { return x < y ? x : y; }
 
 // The state allocation: LiveChan [n] | carry int16 [n, 2048] | slot offset int64 [n, slots] | slot length int32
@@ -246,16 +241,12 @@ __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const u
 }  // namespace afsk
 
 struct afsk_live {
-    int device = -1;
+    afsk::DeviceState state;            // the layout's L.bytes
     afsk::LiveLayout L;
     int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;   // (a mixed receiver: bit_frames 0)
-    int64_t o_slot_bf = 0;              // mixed, per-stream launch: offset of the per-slot bit_frames in d
-    afsk_group_plan* plan = nullptr;    // mixed, grouped launch: the plan over the slots
-    int64_t bytes = 0;                  // device bytes: L.bytes (+ the per-slot bit_frames or the plan)
-    void* d = nullptr;
+    afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
     ~afsk_live() {
         if (plan) (void)afsk_group_plan_destroy(plan);
-        if (d) (void)hipFree(d);
     }
 };
 
@@ -272,27 +263,27 @@ int afsk_live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chun
 
 namespace {
 
-// The device part of create: allocate lv->bytes, zero the channel states and upload the per-slot bit_frames
-// (slot_bf_host, n * slots, when the launch reads them from the allocation) -- synchronous.
-int live_allocate(afsk_live* lv, int32_t amp_start_threshold, int32_t amp_end_threshold, int32_t max_chunk_len,
-                  const int32_t* slot_bf_host) {
-    if (int rc = afsk::require_device()) return rc;
-    hipError_t e = hipGetDevice(&lv->device);
-    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_create (hipGetDevice)");
-    lv->amp_start = amp_start_threshold;
-    lv->amp_end = amp_end_threshold;
-    lv->max_chunk_len = max_chunk_len;
-    e = hipMalloc(&lv->d, (size_t)lv->bytes);
-    if (e != hipSuccess) { lv->d = nullptr; return afsk::hip_fail(e, "afsk_live_create (hipMalloc)"); }
-    // only the channel states (and the slot rates) need a value: the carry, slots and rows are written before they
-    // are read
-    e = hipMemsetAsync(lv->d, 0, (size_t)lv->L.o_carry, nullptr);
-    if (e == hipSuccess && slot_bf_host)
-        e = hipMemcpyAsync(static_cast<uint8_t*>(lv->d) + lv->o_slot_bf, slot_bf_host,
-                           (size_t)(4 * lv->L.n * lv->L.slots), hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_create (initialise the state)");
-    return AFSK_OK;
+// Both create entries, after their own argument checks: bit_frames[c] per channel when `mixed`, else bit_frames[0]
+// for every channel (the uniform receiver).
+int live_create(int32_t n_channels, const int32_t* bit_frames, bool mixed, int32_t amp_start_threshold,
+                int32_t amp_end_threshold, int32_t max_burst_len, int32_t max_chunk_len, afsk_live** out) {
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live> lv(new afsk_live());
+        const afsk::LiveLayout& L = lv->L;
+        if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, lv->L)) return rc;
+        std::vector<int32_t> slot_bf(mixed ? (size_t)(L.n * L.slots) : 0);
+        for (size_t s = 0; s < slot_bf.size(); s++) slot_bf[s] = bit_frames[(int64_t)s / L.slots];
+        lv->bit_frames = mixed ? 0 : bit_frames[0];
+        lv->amp_start = amp_start_threshold;
+        lv->amp_end = amp_end_threshold;
+        lv->max_chunk_len = max_chunk_len;
+        // only the channel states need a value: the carry, slots and rows are written before they are read
+        if (int rc = lv->state.create("afsk_live_create", L.bytes, L.o_carry)) return rc;
+        if (mixed)
+            if (int rc = afsk_group_plan_create(slot_bf.data(), (int32_t)slot_bf.size(), &lv->plan)) return rc;
+        *out = lv.release();
+        return AFSK_OK;
+    });
 }
 
 }  // namespace
@@ -302,15 +293,8 @@ int afsk_live_create(int32_t n_channels, int32_t bit_frames, int32_t amp_start_t
     if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     *out = nullptr;
     if (!afsk::bf_valid(bit_frames)) return afsk::fail_bit_frames();
-    return afsk::no_throw([&] {
-        std::unique_ptr<afsk_live> lv(new afsk_live());
-        if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, lv->L)) return rc;
-        lv->bit_frames = bit_frames;
-        lv->bytes = lv->L.bytes;
-        if (int rc = live_allocate(lv.get(), amp_start_threshold, amp_end_threshold, max_chunk_len, nullptr)) return rc;
-        *out = lv.release();
-        return AFSK_OK;
-    });
+    return live_create(n_channels, &bit_frames, false, amp_start_threshold, amp_end_threshold, max_burst_len,
+                       max_chunk_len, out);
 }
 
 int afsk_live_create_mixed(int32_t n_channels, const int32_t* bit_frames_host, int32_t amp_start_threshold,
@@ -325,34 +309,15 @@ int afsk_live_create_mixed(int32_t n_channels, const int32_t* bit_frames_host, i
         same = same && bit_frames_host[c] == bit_frames_host[0];
     }
     // one rate for every channel: the uniform receiver (its launches, its state bytes)
-    if (same) return afsk_live_create(n_channels, bit_frames_host[0], amp_start_threshold, amp_end_threshold,
-                                      max_burst_len, max_chunk_len, out);
-    return afsk::no_throw([&] {
-        std::unique_ptr<afsk_live> lv(new afsk_live());
-        if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, lv->L)) return rc;
-        const afsk::LiveLayout& L = lv->L;
-        std::unique_ptr<int32_t[]> slot_bf(new int32_t[(size_t)(L.n * L.slots)]);
-        for (int64_t s = 0; s < L.n * L.slots; s++) slot_bf[(size_t)s] = bit_frames_host[s / L.slots];
-        lv->bytes = L.bytes + 8 * L.n * L.slots;                   // the plan: index list + bit_frames per slot
-        if (!afsk::kLiveMixedGrouped) {
-            lv->o_slot_bf = L.bytes;
-            lv->bytes = L.bytes + afsk::align256(4 * L.n * L.slots);
-        }
-        if (int rc = live_allocate(lv.get(), amp_start_threshold, amp_end_threshold, max_chunk_len,
-                                   afsk::kLiveMixedGrouped ? nullptr : slot_bf.get()))
-            return rc;
-        if (afsk::kLiveMixedGrouped)
-            if (int rc = afsk_group_plan_create(slot_bf.get(), (int32_t)(L.n * L.slots), &lv->plan)) return rc;
-        *out = lv.release();
-        return AFSK_OK;
-    });
+    return live_create(n_channels, bit_frames_host, !same, amp_start_threshold, amp_end_threshold, max_burst_len,
+                       max_chunk_len, out);
 }
 
 int afsk_live_info(const afsk_live* live, int32_t* out_n_channels, int32_t* out_slots, int64_t* out_state_bytes) {
     if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
     if (out_n_channels) *out_n_channels = (int32_t)live->L.n;
     if (out_slots) *out_slots = (int32_t)live->L.slots;
-    if (out_state_bytes) *out_state_bytes = live->bytes;
+    if (out_state_bytes) *out_state_bytes = live->state.bytes + (live->plan ? 8 * live->L.n * live->L.slots : 0);
     return AFSK_OK;
 }
 
@@ -369,10 +334,9 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
         return afsk::fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
     if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
         return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(live->device)) return rc;
+    if (int rc = live->state.check_current()) return rc;
     const afsk::LiveLayout& L = live->L;
-    uint8_t* d = static_cast<uint8_t*>(live->d);
+    uint8_t* d = live->state.ptr();
     afsk::LiveArgs g{};
     g.chan = reinterpret_cast<afsk::LiveChan*>(d);
     g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
@@ -402,11 +366,6 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
                                         o.nbytes, o.nbits, o.clock_idx, o.term_frame, o.status, o.corrected,
                                         o.margins, o.margin_stride, st);
     afsk::DemodArgs a = o.args<afsk::DemodArgs>(g.rows, g.slot_off, g.slot_len, live->amp_end, (int32_t)(L.n * L.slots));
-    if (live->o_slot_bf) {
-        a.bit_frames = reinterpret_cast<const int32_t*>(d + live->o_slot_bf);
-        e = afsk::launch_demod(a, st);
-        return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch demod_kernel (live slots)");
-    }
     a.uniform_bit_frames = live->bit_frames;
     e = afsk::launch_demod_uniform(a, st);
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch demod_uniform_kernel (live slots)");
@@ -414,10 +373,9 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
 
 int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_stream) {
     if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(live->device)) return rc;
+    if (int rc = live->state.check_current()) return rc;
     hipLaunchKernelGGL(afsk::live_reset_kernel, dim3((uint32_t)((live->L.n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)hip_stream, static_cast<afsk::LiveChan*>(live->d), d_mask_or_null,
+                       (hipStream_t)hip_stream, static_cast<afsk::LiveChan*>(live->state.d), d_mask_or_null,
                        (int32_t)live->L.n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_reset_kernel");

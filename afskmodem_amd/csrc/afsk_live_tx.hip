@@ -25,6 +25,7 @@
 // file's store16, hamming_codeword / symbol_is_mark, q_words, kWinBytes and tone_words.
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "../../include/afsk_amd.h"
 #include "afsk_capi_internal.h"
@@ -402,25 +403,11 @@ __global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const 
 }  // namespace afsk
 
 struct afsk_live_tx {
-    int device = -1;
+    afsk::DeviceState state;                    // the layout's L.bytes, or live_tx_mixed_bytes(L)
     afsk::TxLayout L;
     int32_t bit_frames = 0, n_train_sym = 0;   // (a mixed transmitter: 0, see o_geom)
-    int64_t o_geom = 0;                         // mixed: offset of TxGeom [n] in d (0: uniform)
-    int64_t bytes = 0;                          // the allocation: L.bytes, or live_tx_mixed_bytes(L)
-    void* d = nullptr;
-    ~afsk_live_tx() {
-        if (d) (void)hipFree(d);
-    }
+    int64_t o_geom = 0;                         // mixed: offset of TxGeom [n] in the state (0: uniform)
 };
-
-extern "C" {
-
-int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, int64_t* out_state_bytes) {
-    afsk::TxLayout L;
-    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
-    if (out_state_bytes) *out_state_bytes = L.bytes;
-    return AFSK_OK;
-}
 
 namespace {
 
@@ -436,51 +423,60 @@ int tx_check_longest(int32_t bf, int64_t n_train_sym, int32_t max_payload_len) {
     return AFSK_OK;
 }
 
-// The device part of create: allocate `tx->bytes`, zero the channel states, upload the mixed geometry (synchronous).
-int tx_allocate(afsk_live_tx* tx, const afsk::TxGeom* geom_host) {
-    if (int rc = afsk::require_device()) return rc;
-    hipError_t e = hipGetDevice(&tx->device);
-    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (hipGetDevice)");
-    e = hipMalloc(&tx->d, (size_t)tx->bytes);
-    if (e != hipSuccess) { tx->d = nullptr; return afsk::hip_fail(e, "afsk_live_tx_create (hipMalloc)"); }
-    // only the channel states (and the geometry) need a value: ring entries and payload slots are written before
-    // they are read
-    e = hipMemsetAsync(tx->d, 0, (size_t)tx->L.o_desc, nullptr);
-    if (e == hipSuccess && geom_host)
-        e = hipMemcpyAsync(static_cast<uint8_t*>(tx->d) + tx->o_geom, geom_host, (size_t)(8 * tx->L.n),
-                           hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return afsk::hip_fail(e, "afsk_live_tx_create (initialise the state)");
+// afsk_live_tx_layout and afsk_live_tx_state_bytes_mixed: the state bytes of a uniform or a mixed transmitter
+int tx_state_bytes(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, bool mixed,
+                   int64_t* out_state_bytes) {
+    afsk::TxLayout L;
+    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
+    if (out_state_bytes) *out_state_bytes = mixed ? afsk::live_tx_mixed_bytes(L) : L.bytes;
     return AFSK_OK;
 }
 
+// Both create entries, after their own argument checks: bit_frames[c] / ts_cycles[c] per channel when `mixed`, else
+// bit_frames[0] / ts_cycles[0] for every channel (the uniform transmitter).
+int tx_create(int32_t n_channels, const int32_t* bit_frames, const int32_t* ts_cycles, bool mixed, int32_t queue_depth,
+              int32_t max_payload_len, afsk_live_tx** out) {
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
+        const afsk::TxLayout& L = tx->L;
+        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
+        std::vector<afsk::TxGeom> geom(mixed ? (size_t)n_channels : 1);
+        for (size_t c = 0; c < geom.size(); c++) {
+            const int64_t nts = tx_train_sym(ts_cycles[c]);
+            if (int rc = tx_check_longest(bit_frames[c], nts, max_payload_len)) return rc;
+            geom[c] = afsk::TxGeom{bit_frames[c], (int32_t)nts};
+        }
+        tx->o_geom = mixed ? L.bytes : 0;
+        if (!mixed) { tx->bit_frames = geom[0].bf; tx->n_train_sym = geom[0].n_train_sym; }
+        // only the channel states (and the geometry) need a value: ring entries and payload slots are written before
+        // they are read
+        if (int rc = tx->state.create("afsk_live_tx_create", mixed ? afsk::live_tx_mixed_bytes(L) : L.bytes, L.o_desc,
+                                      mixed ? geom.data() : nullptr, tx->o_geom, 8 * L.n))
+            return rc;
+        *out = tx.release();
+        return AFSK_OK;
+    });
+}
+
 }  // namespace
+
+extern "C" {
+
+int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, int64_t* out_state_bytes) {
+    return tx_state_bytes(n_channels, queue_depth, max_payload_len, false, out_state_bytes);
+}
+
+int afsk_live_tx_state_bytes_mixed(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len,
+                                   int64_t* out_state_bytes) {
+    return tx_state_bytes(n_channels, queue_depth, max_payload_len, true, out_state_bytes);
+}
 
 int afsk_live_tx_create(int32_t n_channels, int32_t bit_frames, int32_t ts_cycles, int32_t queue_depth,
                         int32_t max_payload_len, afsk_live_tx** out) {
     if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     *out = nullptr;
     if (!tx_bf_valid(bit_frames)) return tx_fail_bit_frames();
-    return afsk::no_throw([&] {
-        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
-        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
-        const int64_t nts = tx_train_sym(ts_cycles);
-        if (int rc = tx_check_longest(bit_frames, nts, max_payload_len)) return rc;
-        tx->bit_frames = bit_frames;
-        tx->n_train_sym = (int32_t)nts;
-        tx->bytes = tx->L.bytes;
-        if (int rc = tx_allocate(tx.get(), nullptr)) return rc;
-        *out = tx.release();
-        return AFSK_OK;
-    });
-}
-
-int afsk_live_tx_state_bytes_mixed(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len,
-                                   int64_t* out_state_bytes) {
-    afsk::TxLayout L;
-    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
-    if (out_state_bytes) *out_state_bytes = afsk::live_tx_mixed_bytes(L);
-    return AFSK_OK;
+    return tx_create(n_channels, &bit_frames, &ts_cycles, false, queue_depth, max_payload_len, out);
 }
 
 int afsk_live_tx_create_mixed(int32_t n_channels, const int32_t* bit_frames_host, const int32_t* ts_cycles_host,
@@ -495,23 +491,7 @@ int afsk_live_tx_create_mixed(int32_t n_channels, const int32_t* bit_frames_host
     for (int32_t c = 1; c < n_channels && same; c++)
         same = bit_frames_host[c] == bit_frames_host[0] && tx_train_sym(ts_cycles_host[c]) == tx_train_sym(ts_cycles_host[0]);
     // one geometry for every channel: the uniform transmitter (its launches, its state bytes)
-    if (same) return afsk_live_tx_create(n_channels, bit_frames_host[0], ts_cycles_host[0], queue_depth, max_payload_len,
-                                         out);
-    return afsk::no_throw([&] {
-        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
-        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
-        std::unique_ptr<afsk::TxGeom[]> geom(new afsk::TxGeom[(size_t)n_channels]);
-        for (int32_t c = 0; c < n_channels; c++) {
-            const int64_t nts = tx_train_sym(ts_cycles_host[c]);
-            if (int rc = tx_check_longest(bit_frames_host[c], nts, max_payload_len)) return rc;
-            geom[(size_t)c] = afsk::TxGeom{bit_frames_host[c], (int32_t)nts};
-        }
-        tx->o_geom = tx->L.bytes;
-        tx->bytes = afsk::live_tx_mixed_bytes(tx->L);
-        if (int rc = tx_allocate(tx.get(), geom.get())) return rc;
-        *out = tx.release();
-        return AFSK_OK;
-    });
+    return tx_create(n_channels, bit_frames_host, ts_cycles_host, !same, queue_depth, max_payload_len, out);
 }
 
 int afsk_live_tx_info(const afsk_live_tx* tx, int32_t* out_n_channels, int32_t* out_queue_depth,
@@ -520,7 +500,7 @@ int afsk_live_tx_info(const afsk_live_tx* tx, int32_t* out_n_channels, int32_t* 
     if (out_n_channels) *out_n_channels = (int32_t)tx->L.n;
     if (out_queue_depth) *out_queue_depth = (int32_t)tx->L.depth;
     if (out_max_payload_len) *out_max_payload_len = (int32_t)tx->L.max_payload;
-    if (out_state_bytes) *out_state_bytes = tx->bytes;
+    if (out_state_bytes) *out_state_bytes = tx->state.bytes;
     return AFSK_OK;
 }
 
@@ -532,10 +512,9 @@ int afsk_live_tx_submit(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel
     if (n_msgs == 0) return AFSK_OK;
     if (!channel || !payload_offset || !payload_len || !payload || !out_status || !out_start || !out_n_samples)
         return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
+    if (int rc = tx->state.check_current()) return rc;
     const afsk::TxLayout& L = tx->L;
-    uint8_t* d = static_cast<uint8_t*>(tx->d);
+    uint8_t* d = tx->state.ptr();
     int32_t* first_bad = reinterpret_cast<int32_t*>(d + L.o_scratch);
     const hipStream_t st = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(afsk::live_tx_order_kernel, dim3(1), dim3(256), 0, st, channel, n_msgs, first_bad);
@@ -577,9 +556,8 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
     if ((n_samples > 0 && !out) || !out_pending) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     const int32_t tiles = (int32_t)((n_samples + afsk::kTxTile - 1) / afsk::kTxTile);
     if ((int64_t)tiles * L.n > 0x7fffffffll) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels * tiles exceeds 2^31 - 1");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
-    uint8_t* d = static_cast<uint8_t*>(tx->d);
+    if (int rc = tx->state.check_current()) return rc;
+    uint8_t* d = tx->state.ptr();
     afsk::TxChan* chan = reinterpret_cast<afsk::TxChan*>(d);
     const afsk::TxDesc* desc = reinterpret_cast<const afsk::TxDesc*>(d + L.o_desc);
     const hipStream_t st = (hipStream_t)hip_stream;
@@ -620,10 +598,9 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
 int afsk_live_tx_reset(afsk_live_tx* tx, const uint8_t* d_mask_or_null, int32_t* out_pending_or_null,
                        void* hip_stream) {
     if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(tx->device)) return rc;
+    if (int rc = tx->state.check_current()) return rc;
     hipLaunchKernelGGL(afsk::live_tx_reset_kernel, dim3((uint32_t)((tx->L.n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)hip_stream, static_cast<afsk::TxChan*>(tx->d), d_mask_or_null, out_pending_or_null,
+                       (hipStream_t)hip_stream, static_cast<afsk::TxChan*>(tx->state.d), d_mask_or_null, out_pending_or_null,
                        (int32_t)tx->L.n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_reset_kernel");

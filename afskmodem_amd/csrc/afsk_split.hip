@@ -398,16 +398,12 @@ static int split_layout(const int32_t* len, const int32_t* bf, int32_t n, int32_
 }  // namespace afsk
 
 struct afsk_split_plan {
-    int device = -1;
+    afsk::DeviceState state;           // bit_frames [n] | plan_len [n] | word_off [n] (8-aligned) | seg_stream | seg_k0
     int32_t n = 0;
     afsk::SplitLayout L;
     int32_t n_seg40 = 0;               // segments [0, n_seg40) are 1200-baud ones
-    void* d = nullptr;                 // bit_frames [n] | plan_len [n] | word_off [n] (8-aligned) | seg_stream | seg_k0
     int32_t *bf = nullptr, *plen = nullptr, *seg_stream = nullptr, *seg_k0 = nullptr;
     int64_t* word_off = nullptr;
-    ~afsk_split_plan() {
-        if (d) (void)hipFree(d);
-    }
 };
 
 extern "C" {
@@ -434,9 +430,6 @@ int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_fr
         if (int rc = afsk::split_layout(stream_len_host, bit_frames_host, n_streams, segment_symbols, pl->L, &word_off,
                                         &seg_stream, &seg_k0))
             return rc;
-        if (int rc = afsk::require_device()) return rc;
-        hipError_t e = hipGetDevice(&pl->device);
-        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_split_plan_create (hipGetDevice)");
         pl->n = n_streams;
         int32_t n40 = 0;
         for (size_t g = 0; g < seg_stream.size(); g++) n40 += bit_frames_host[seg_stream[g]] == 40;
@@ -444,7 +437,6 @@ int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_fr
         const size_t n = (size_t)n_streams, ns = seg_stream.size();
         const size_t o_plen = 4 * n, o_woff = ((8 * n + 7) / 8) * 8, o_seg = o_woff + 8 * n, o_k0 = o_seg + 4 * ns;
         const size_t bytes = o_k0 + 4 * ns;
-        if (bytes == 0) { *out_plan = pl.release(); return AFSK_OK; }
         std::vector<uint8_t> h(bytes);
         if (n) {
             std::memcpy(h.data(), bit_frames_host, 4 * n);
@@ -455,11 +447,9 @@ int afsk_split_plan_create(const int32_t* stream_len_host, const int32_t* bit_fr
             std::memcpy(h.data() + o_seg, seg_stream.data(), 4 * ns);
             std::memcpy(h.data() + o_k0, seg_k0.data(), 4 * ns);
         }
-        e = hipMalloc(&pl->d, bytes);
-        if (e != hipSuccess) { pl->d = nullptr; return afsk::hip_fail(e, "afsk_split_plan_create (hipMalloc)"); }
-        e = hipMemcpy(pl->d, h.data(), bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return afsk::hip_fail(e, "afsk_split_plan_create (upload)");
-        uint8_t* d = static_cast<uint8_t*>(pl->d);
+        if (int rc = pl->state.create("afsk_split_plan_create", (int64_t)bytes, 0, h.data(), 0, (int64_t)bytes))
+            return rc;
+        uint8_t* d = pl->state.ptr();       // (null without streams: every offset is 0)
         pl->bf = reinterpret_cast<int32_t*>(d);
         pl->plen = reinterpret_cast<int32_t*>(d + o_plen);
         pl->word_off = reinterpret_cast<int64_t*>(d + o_woff);
@@ -496,8 +486,7 @@ int afsk_demod_batch_split(const afsk_split_plan* plan, const int16_t* samples, 
     if (plan->n == 0) return AFSK_OK;
     if (!samples || !stream_offset || !stream_len || o.missing() || !d_scratch)
         return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (int rc = afsk::require_device()) return rc;
-    if (int rc = afsk::plan_on_current_device(plan->device)) return rc;
+    if (int rc = plan->state.check_current()) return rc;
     afsk::SplitArgs a = o.args<afsk::SplitArgs>(samples, stream_offset, stream_len, amp_end_threshold, plan->n);
     a.bit_frames = plan->bf; a.plan_len = plan->plen; a.word_off = plan->word_off;
     a.seg_stream = plan->seg_stream; a.seg_k0 = plan->seg_k0;

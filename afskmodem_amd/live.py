@@ -47,6 +47,41 @@ def _i32_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _device_mask(mask, n_channels: int, dev):
+    """A ``reset`` mask ([n_channels] bool / uint8, host or device) as a contiguous uint8 tensor on ``dev``; None
+    stays None."""
+    if mask is None:
+        return None
+    torch = batch._torch()
+    if isinstance(mask, torch.Tensor):
+        m = mask.to(device=dev, dtype=torch.uint8).contiguous()
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
+    if m.dim() != 1 or int(m.numel()) != n_channels:
+        raise ValueError(f"mask must hold n_channels = {n_channels} entries")
+    return m
+
+
+def _check_rows(t, name: str, owner: str, n_channels: int, dev, T: int | None = None,
+                max_chunk_len: int | None = None) -> None:
+    """Check the torch tensor ``t`` as an int16 ``[n_channels, >= T]`` view on ``dev`` with contiguous rows and any
+    row stride (``T`` None: any width, at most ``max_chunk_len``)."""
+    torch = batch._torch()
+    if t.dtype != torch.int16:
+        raise TypeError(f"{name} must hold int16 samples")
+    if not t.is_cuda or t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, the {owner} on {dev}")
+    if t.dim() != 2 or t.shape[0] != n_channels or (T is not None and t.shape[1] < T):
+        width = "T" if T is None else f">= {T}"
+        raise ValueError(f"{name} must be [n_channels={n_channels}, {width}], got {list(t.shape)}")
+    if T is None:
+        T = int(t.shape[1])
+        if T > max_chunk_len:
+            raise ValueError(f"T = {T} exceeds max_chunk_len = {max_chunk_len}")
+    if T > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} rows must be contiguous (any row stride)")
+
+
 def layout(n_channels: int, max_burst_len: int, max_chunk_len: int) -> tuple[int, int]:
     """(slots per channel and push, device state bytes) of a live receiver (``afsk_live_layout``: host-only)."""
     slots, nbytes = C.c_int32(), C.c_int64()
@@ -118,29 +153,22 @@ class LiveReceiver(batch._NativePlan):
             raise ValueError("bit_frames must hold integers")
         batch.validate_bit_frames(np.asarray(rates, np.int64))
         self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
-        mixed = len(set(rates)) > 1
-        self.bit_frames = None if mixed else int(rates[0]) if rates else None
+        self.bit_frames = None if len(set(rates)) > 1 else int(rates[0]) if rates else None
         self.max_burst_len = int(max_burst_len)
         self.max_chunk_len = int(max_chunk_len)
-        self.slots, self.state_bytes = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)
-        _native.require_device()
-        batch._drain_parked_plans()
+        self.slots = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)[0]   # (before the device check)
         super().__init__(device)
         # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
         self._min_bf = int(min(rates))
         self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self._min_bf)
+        nbytes = C.c_int64()
         with torch.cuda.device(self.device):
-            if mixed:
-                _native.check(_native.lib().afsk_live_create_mixed(
-                    self.n_channels, _i32_ptr(self.channel_bit_frames), batch.threshold_gt(amp_start_threshold),
-                    batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
-                nbytes = C.c_int64()
-                _native.check(_native.lib().afsk_live_info(self.handle, None, None, C.byref(nbytes)))
-                self.state_bytes = int(nbytes.value)
-            else:
-                _native.check(_native.lib().afsk_live_create(
-                    self.n_channels, self.bit_frames, batch.threshold_gt(amp_start_threshold),
-                    batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+            # (one rate in every entry: the C entry builds the one-rate receiver)
+            _native.check(_native.lib().afsk_live_create_mixed(
+                self.n_channels, _i32_ptr(self.channel_bit_frames), batch.threshold_gt(amp_start_threshold),
+                batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+            _native.check(_native.lib().afsk_live_info(self.handle, None, None, C.byref(nbytes)))
+        self.state_bytes = int(nbytes.value)
 
     @classmethod
     def from_receivers(cls, receivers, **capacities) -> "LiveReceiver":
@@ -173,29 +201,19 @@ class LiveReceiver(batch._NativePlan):
         torch = batch._torch()
         if chunk is None:
             return torch.empty((self.n_channels, 0), dtype=torch.int16, device=self.device), False
-        uploaded = False
-        if isinstance(chunk, np.ndarray):
+        uploaded = isinstance(chunk, np.ndarray)
+        if uploaded:
             if chunk.dtype != np.int16:
                 raise TypeError("chunk must hold int16 samples")
             if chunk.ndim != 2 or chunk.shape[0] != self.n_channels:
                 raise ValueError(f"chunk must be [n_channels={self.n_channels}, T], got {list(chunk.shape)}")
             if chunk.shape[1] > self.max_chunk_len:
                 raise ValueError(f"T = {chunk.shape[1]} exceeds max_chunk_len = {self.max_chunk_len}")
-            chunk = torch.from_numpy(np.ascontiguousarray(chunk)).to(self.device)      # one copy
-            uploaded = True
+            return torch.from_numpy(np.ascontiguousarray(chunk)).to(self.device), True      # one copy
         if not isinstance(chunk, torch.Tensor):
             raise TypeError("chunk must be an int16 CUDA tensor or a numpy int16 array")
-        if chunk.dtype != torch.int16:
-            raise TypeError("chunk must hold int16 samples")
-        if not chunk.is_cuda or chunk.device != self.device:
-            raise ValueError(f"chunk is on {chunk.device}, the receiver on {self.device}")
-        if chunk.dim() != 2 or chunk.shape[0] != self.n_channels:
-            raise ValueError(f"chunk must be [n_channels={self.n_channels}, T], got {list(chunk.shape)}")
-        if chunk.shape[1] > self.max_chunk_len:
-            raise ValueError(f"T = {chunk.shape[1]} exceeds max_chunk_len = {self.max_chunk_len}")
-        if chunk.shape[1] > 1 and chunk.stride(1) != 1:
-            raise ValueError("chunk rows must be contiguous (any row stride)")
-        return chunk, uploaded
+        _check_rows(chunk, "chunk", "receiver", self.n_channels, self.device, max_chunk_len=self.max_chunk_len)
+        return chunk, False
 
     def push(self, chunk, stream=None, out: LiveResult | None = None, flush: bool = False) -> LiveResult:
         """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
@@ -241,14 +259,7 @@ class LiveReceiver(batch._NativePlan):
         uint8, host or device) is true, without reporting anything; they start new streams."""
         torch = batch._torch()
         dev = self.device
-        m = None
-        if mask is not None:
-            if isinstance(mask, torch.Tensor):
-                m = mask.to(device=dev, dtype=torch.uint8).contiguous()
-            else:
-                m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
-            if m.dim() != 1 or int(m.numel()) != self.n_channels:
-                raise ValueError(f"mask must hold n_channels = {self.n_channels} entries")
+        m = _device_mask(mask, self.n_channels, dev)
         with torch.cuda.device(dev):
             if m is not None:
                 batch._order_after_current(stream, dev)
@@ -335,7 +346,6 @@ class LiveTransmitter(batch._NativePlan):
             self.ts_cycles = Transmitter(self.baud_rate, training_time).ts_cycles  # ref:438 (negative: no cycles)
             self.channel_bit_frames = np.full(self.n_channels, self.bit_frames, np.int32)
             self.channel_ts_cycles = np.full(self.n_channels, self.ts_cycles, np.int32)
-            mixed = False
         else:
             bauds = bauds if bauds is not None else [baud_rate] * self.n_channels
             times = times if times is not None else [training_time] * self.n_channels
@@ -350,21 +360,16 @@ class LiveTransmitter(batch._NativePlan):
             self.ts_cycles = None if mixed else int(self.channel_ts_cycles[0])
         self.queue_depth = int(queue_depth)
         self.max_payload_len = int(max_payload_len)
-        self.state_bytes = tx_layout(self.n_channels, self.queue_depth, self.max_payload_len)
-        if mixed:
-            self.state_bytes = tx_state_bytes_mixed(self.n_channels, self.queue_depth, self.max_payload_len)
-        _native.require_device()
-        batch._drain_parked_plans()
+        tx_layout(self.n_channels, self.queue_depth, self.max_payload_len)              # (before the device check)
         super().__init__(device)
+        nbytes = C.c_int64()
         with torch.cuda.device(self.device):
-            if mixed:
-                _native.check(_native.lib().afsk_live_tx_create_mixed(
-                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_ts_cycles),
-                    self.queue_depth, self.max_payload_len, C.byref(self._h)))
-            else:
-                _native.check(_native.lib().afsk_live_tx_create(
-                    self.n_channels, self.bit_frames, int(self.ts_cycles), self.queue_depth, self.max_payload_len,
-                    C.byref(self._h)))
+            # (one geometry in every entry: the C entry builds the one-geometry transmitter)
+            _native.check(_native.lib().afsk_live_tx_create_mixed(
+                self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_ts_cycles),
+                self.queue_depth, self.max_payload_len, C.byref(self._h)))
+            _native.check(_native.lib().afsk_live_tx_info(self.handle, None, None, None, C.byref(nbytes)))
+        self.state_bytes = int(nbytes.value)
         # messages queued or on air per channel after the last pull (0 for channels reset since)
         self.pending = torch.zeros(self.n_channels, dtype=torch.int32, device=self.device)
 
@@ -458,14 +463,7 @@ class LiveTransmitter(batch._NativePlan):
             out = torch.empty((self.n_channels, T), dtype=torch.int16, device=dev)
         if not isinstance(out, torch.Tensor):
             raise TypeError("out must be an int16 CUDA tensor")
-        if out.dtype != torch.int16:
-            raise TypeError("out must hold int16 samples")
-        if not out.is_cuda or out.device != dev:
-            raise ValueError(f"out is on {out.device}, the transmitter on {dev}")
-        if out.dim() != 2 or out.shape[0] != self.n_channels or out.shape[1] < T:
-            raise ValueError(f"out must be [n_channels={self.n_channels}, >= {T}], got {list(out.shape)}")
-        if T > 1 and out.stride(1) != 1:
-            raise ValueError("out rows must be contiguous (any row stride)")
+        _check_rows(out, "out", "transmitter", self.n_channels, dev, T)
         if self.n_channels > 1 and T > 0 and out.stride(0) < T:
             raise ValueError(f"out row stride {out.stride(0)} is below T = {T}: the rows would overlap")
         with torch.cuda.device(dev):
@@ -482,14 +480,7 @@ class LiveTransmitter(batch._NativePlan):
         ``pending`` entries become 0."""
         torch = batch._torch()
         dev = self.device
-        m = None
-        if mask is not None:
-            if isinstance(mask, torch.Tensor):
-                m = mask.to(device=dev, dtype=torch.uint8).contiguous()
-            else:
-                m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
-            if m.dim() != 1 or int(m.numel()) != self.n_channels:
-                raise ValueError(f"mask must hold n_channels = {self.n_channels} entries")
+        m = _device_mask(mask, self.n_channels, dev)
         with torch.cuda.device(dev):
             if m is not None:
                 batch._order_after_current(stream, dev)
