@@ -78,6 +78,35 @@ def test_float_quarter_division_of_the_modulator_is_exact():
         assert np.array_equal(got, (x0.astype(np.uint32) // q)), q
 
 
+TX_BFS = tuple(bf for bf in range(4, 48001, 4) if 48000 % bf == 0)      # the live transmitter's 48 rates
+
+
+def test_float_quarter_division_of_the_live_transmitter_is_exact():
+    """afsk_live_tx.hip tone_pair / tone_words: (uint)(((float)x + 0.5f) * (1.0f / q)) == x // q for every quarter
+    width q = bf / 4 of the 48 live transmitter rates and every x the tile kernel forms: relative to the first symbol
+    of its tile, x < bf + 4096 + 16 (one symbol of lead, the tile, the odd-phase slack)."""
+    assert len(TX_BFS) == 48 and TX_BFS[0] == 4 and TX_BFS[-1] == 48000
+    for bf in TX_BFS:
+        q = bf // 4
+        x = np.arange(0, bf + 4096 + 16, dtype=np.uint32)
+        rcp = np.float32(1.0) / np.float32(q)
+        got = ((x.astype(np.float32) + np.float32(0.5)) * rcp).astype(np.uint32)
+        assert np.array_equal(got, x // np.uint32(q)), q
+
+
+def test_large_quarter_tone_words_under_the_wav_quirk():
+    """afsk_synth.hip tone_words<QUIRK=true, SMALLQ=false>: the 8 samples of a store are frames x0, x0+2, x0+4, x0+6,
+    each taken from quarter Q0 (frame offset j < c = q - r0) or Q0 + 1.  That is exact as long as offsets 0 ... 6
+    meet at most one quarter boundary: for every q >= 6, not only the q >= 8 the live transmitter's tile kernel
+    switches at (so sending q = 6 down that path changes no sample), and for no q <= 5."""
+    for q in range(1, 64):
+        r0 = np.arange(q)[:, None]
+        j = np.arange(0, 8, 2)[None, :]
+        exact = (r0 + j) // q                                  # quarter of each frame, relative to Q0
+        large = (j >= q - r0).astype(int)                      # the large-q code's choice
+        assert np.array_equal(exact, large) == (q >= 6), q
+
+
 def test_small_quarter_reciprocal_multiply_is_exact():
     """afsk_synth.hip tone_words (q < 8): ((r0 + j) * ceil(65536 / q)) >> 16 == (r0 + j) // q
     for r0 + j <= 13."""

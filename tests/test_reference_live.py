@@ -26,7 +26,7 @@ from oracle import afsk_oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_live_vectors.json")
 SEED = 20261007
-SECTIONS = ("framing", "ecc", "primitives", "decodes", "degenerate")
+SECTIONS = ("framing", "ecc", "primitives", "decodes", "degenerate", "slow_framing")
 
 
 def fp(v):
@@ -65,6 +65,22 @@ def framing_reference(ref, c):
     want = ref.Transmitter(c["baud"], c["tt"])._Transmitter__getFrames(c["data"])
     wav = np.frombuffer(ref.SoundOutput._SoundOutput__convertFrames([int(v) for v in want]), "<i2")
     return {"frames": fp(want), "wav": fp(wav)}
+
+
+def slow_framing_cases(seed):
+    """Framing below 24 baud (symbols of 2400 ... 48000 samples, longer than the live transmitter's 4096-sample
+    tile): short payloads, with and without training cycles.  A section of its own, so the framing cases above stay
+    as they were recorded."""
+    rng = np.random.default_rng(seed + 1)
+    cases = []
+    for baud, tt, n in ((20, 0.0, 3), (20, 0.3, 1), (15, 0.0, 2), (15, 0.4, 0), (12, 0.5, 2), (5, 0.0, 1),
+                        (5, 0.8, 2), (1, 0.0, 1), (1, 2.0, 0)):
+        data = rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+        cases.append({"baud": baud, "tt": tt, "data": data})
+    return cases
+
+
+slow_framing_reference = framing_reference
 
 
 def ecc_cases(seed):
@@ -188,6 +204,21 @@ def test_framing_matches_the_live_reference(recorded):
         assert fp(got_o) == want["frames"], ("oracle", baud, tt, data.hex())
         assert fp(got_p) == want["frames"], ("product", baud, tt, data.hex())
         assert fp(O.wav_convert(got_o)) == want["wav"], (baud, tt)
+
+
+def test_slow_framing_matches_the_live_reference(recorded):
+    """Below 24 baud: the frames and .wav samples of the oracle and of Transmitter.frames / wav_samples (what
+    tests/live_tx_model.py plays for the live transmitter) against the reference's."""
+    pairs = list(_pairs(recorded, "slow_framing"))
+    assert {c["baud"] for c, _ in pairs} == {20, 15, 12, 5, 1}
+    for c, want in pairs:
+        baud, tt, data = c["baud"], c["tt"], c["data"]
+        t = product.Transmitter(baud, tt)
+        got_o = O.get_frames(data, baud, tt)
+        assert fp(got_o) == want["frames"], ("oracle", baud, tt, data.hex())
+        assert fp(t.frames(data)) == want["frames"], ("product", baud, tt, data.hex())
+        assert fp(O.wav_convert(got_o)) == want["wav"], (baud, tt)
+        assert fp(t.wav_samples(data)) == want["wav"], ("product wav", baud, tt)
 
 
 def test_ecc_matches_the_live_reference(recorded):
