@@ -144,6 +144,15 @@ LIVE_MIXED_SIGNATURES = {
 }
 
 
+# The streaming live receiver (afsk_live_stream_layout, afsk_live_create_stream), bound by lib() from a table of its own
+# for the same reason.
+LIVE_STREAM_SIGNATURES = {
+    "afsk_live_stream_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i32p, _i64p]),
+    "afsk_live_create_stream": (C.c_int, [C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_void_p)]),
+}
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -154,7 +163,8 @@ def lib() -> C.CDLL:
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
-                                  *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items()):
+                                  *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items(),
+                                  *LIVE_STREAM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

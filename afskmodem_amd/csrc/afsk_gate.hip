@@ -140,3 +140,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // The live receiver (afsk_live_*: stateful chunked gate + demodulation of the bursts a push closes), for the same
 // reason.
 #include "afsk_live.hip"
+// The streaming live receiver (afsk_live_stream_layout / afsk_live_create_stream: the same gate walk, bursts
+// demodulated while they are gated), for the same reason.
+#include "afsk_live_stream.hip"

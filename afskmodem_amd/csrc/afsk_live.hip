@@ -125,48 +125,46 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
         }
 }
 
-__global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
+// The gate walk both live receivers share: one wave per channel walks the push's whole blocks through the listen state
+// machine with the next block's load in flight, and hands every event to its sink -- the stored receiver's
+// (LiveStoreSink: record rows and demodulator slots) or the streaming one's (afsk_live_stream.hip: demodulation as
+// the blocks arrive).  A sink has:
+//   init(a, c)                    the channel's state is loaded
+//   begin(a, lane, st)            before the first block
+//   overflowed(a, st)             the burst being reported is longer than the sink keeps
+//   slot(a, i, c, st, ovf)        lane 0, for every reported burst: the sink's per-slot outputs
+//   report(a, i, st, ovf, flags, lane)  every lane, for every reported burst (after slot)
+//   start(st)                     a burst opens with the current block
+//   record(a, st, cur, lane)      the current block belongs to the open burst (st.rec_len: samples before it)
+//   head(st)                      LiveChan::head for the next push (not flushed)
+//   finish(a, c, st, lane)        after the walk and the carry, before the unused slots are written
+//   clear(a, slot0, i)            unused slot slot0 + i: the sink's own outputs
+template <class Sink>
+__device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= a.n) return;
     LiveChan st = a.chan[c];
-    int16_t* row = a.rows + (int64_t)c * a.row_len;
+    sk.init(a, c);
     int16_t* carry = a.carry + (int64_t)c * kListenBlock;
     const int16_t* src = a.chunk + (int64_t)c * a.chunk_stride;
     const int64_t slot0 = (int64_t)c * a.slots;
-
-    // the open burst's stored prefix goes to the row front (it opened in the previous push behind closed bursts,
-    // so it is at most one push of blocks, and head >= 2048: copying block by block front to back never overwrites
-    // a block that is still to be read)
-    int64_t wp = 0;             // row offset of the next stored block
-    int64_t brow = 0;           // row offset of the open burst
-    if (st.mode == 2) {
-        const int64_t stored = min64(st.rec_len, a.cap);
-        if (st.head > 0)
-            for (int64_t o = 0; o < stored; o += kListenBlock) {
-                vec16 v[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[j] = *reinterpret_cast<const vec16*>(row + st.head + o + 512 * j + 8 * lane);
-#pragma unroll
-                for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + o + 512 * j + 8 * lane) = v[j];
-            }
-        wp = stored;
-    }
+    sk.begin(a, lane, st);
 
     const int cl = (int)(st.pos & (kListenBlock - 1));             // carried samples
     const int32_t nblk = (int32_t)(((int64_t)cl + a.chunk_len) / kListenBlock);
     const int64_t bpos0 = st.pos - cl;                              // stream index of block 0
     int k = 0;                                                      // slots used
     auto report = [&](int32_t flags) {
-        const bool ovf = st.rec_len > a.cap;
+        const bool ovf = sk.overflowed(a, st);
         if (k < a.slots && lane == 0) {                             // (k < slots always holds: afsk_live_layout)
             const int64_t i = slot0 + k;
             a.out_burst_start[i] = st.rec_start;
             a.out_burst_len[i] = (int32_t)min64(st.rec_len, kLiveLenMax);
             a.out_flags[i] = flags | (ovf ? AFSK_LIVE_OVERFLOW : 0);
-            a.slot_off[i] = (int64_t)c * a.row_len + brow;
-            a.slot_len[i] = ovf ? 0 : (int32_t)st.rec_len;
+            sk.slot(a, i, c, st, ovf);
         }
+        sk.report(a, slot0 + k, st, ovf, flags, lane);
         k++;
     };
     vec16 cur[4], nxt[4];
@@ -185,19 +183,14 @@ __global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
                 st.mode = 2;
                 st.rec_start = bpos0 + (int64_t)b * kListenBlock;
                 st.rec_len = 0;
-                brow = wp;
+                sk.start(st);
                 ev = 1;
             }
         } else {
             ev = amp < a.amp_end ? 2 : 1;                           // ref:316-318 (block included)
         }
         if (ev) {
-            // stored while the burst fits its capacity (and, as a guard, the row)
-            if (st.rec_len < a.cap && wp + kListenBlock <= a.row_len) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + wp + 512 * j + 8 * lane) = cur[j];
-                wp += kListenBlock;
-            }
+            sk.record(a, st, cur, lane);
             st.rec_len += kListenBlock;
             if (ev == 2) {
                 report(0);
@@ -218,19 +211,74 @@ __global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
         const int64_t base = (int64_t)nblk * kListenBlock - cl;
         for (int i = (nblk == 0 ? cl : 0) + lane; i < tail; i += 64) carry[i] = src[base + i];
         st.pos += a.chunk_len;
-        st.head = st.mode == 2 ? (int32_t)brow : 0;
+        st.head = sk.head(st);
     }
+    sk.finish(a, c, st, lane);
     for (int i = k + lane; i < a.slots; i += 64) {                  // unused slots: length 0, nothing to decode
         a.out_burst_start[slot0 + i] = 0;
         a.out_burst_len[slot0 + i] = 0;
         a.out_flags[slot0 + i] = 0;
-        a.slot_off[slot0 + i] = 0;
-        a.slot_len[slot0 + i] = 0;
+        sk.clear(a, slot0, i);
     }
     if (lane == 0) {
         a.out_n_closed[c] = k < a.slots ? k : a.slots;
         a.chan[c] = st;
     }
+}
+
+// The stored receiver's sink: recorded blocks go from registers into the channel's record row, and every burst the
+// push closes becomes a demodulator slot (row offset + length) for the push's second launch.
+struct LiveStoreSink {
+    int16_t* row;
+    int64_t wp;                 // row offset of the next stored block
+    int64_t brow;               // row offset of the open burst
+
+    // the open burst's stored prefix goes to the row front (it opened in the previous push behind closed bursts,
+    // so it is at most one push of blocks, and head >= 2048: copying block by block front to back never overwrites
+    // a block that is still to be read)
+    __device__ __forceinline__ void init(const LiveArgs& a, int c) { row = a.rows + (int64_t)c * a.row_len; }
+    __device__ __forceinline__ void begin(const LiveArgs& a, int lane, const LiveChan& st) {
+        wp = 0;
+        brow = 0;
+        if (st.mode == 2) {
+            const int64_t stored = min64(st.rec_len, a.cap);
+            if (st.head > 0)
+                for (int64_t o = 0; o < stored; o += kListenBlock) {
+                    vec16 v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) v[j] = *reinterpret_cast<const vec16*>(row + st.head + o + 512 * j + 8 * lane);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + o + 512 * j + 8 * lane) = v[j];
+                }
+            wp = stored;
+        }
+    }
+    __device__ __forceinline__ bool overflowed(const LiveArgs& a, const LiveChan& st) const { return st.rec_len > a.cap; }
+    __device__ __forceinline__ void slot(const LiveArgs& a, int64_t i, int c, const LiveChan& st, bool ovf) const {
+        a.slot_off[i] = (int64_t)c * a.row_len + brow;
+        a.slot_len[i] = ovf ? 0 : (int32_t)st.rec_len;
+    }
+    __device__ __forceinline__ void report(const LiveArgs&, int64_t, const LiveChan&, bool, int32_t, int) const {}
+    __device__ __forceinline__ void start(const LiveChan&) { brow = wp; }
+    __device__ __forceinline__ void record(const LiveArgs& a, const LiveChan& st, const vec16 (&cur)[4], int lane) {
+        // stored while the burst fits its capacity (and, as a guard, the row)
+        if (st.rec_len < a.cap && wp + kListenBlock <= a.row_len) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(row + wp + 512 * j + 8 * lane) = cur[j];
+            wp += kListenBlock;
+        }
+    }
+    __device__ __forceinline__ int32_t head(const LiveChan& st) const { return st.mode == 2 ? (int32_t)brow : 0; }
+    __device__ __forceinline__ void finish(const LiveArgs&, int, const LiveChan&, int) const {}
+    __device__ __forceinline__ void clear(const LiveArgs& a, int64_t slot0, int i) const {
+        a.slot_off[slot0 + i] = 0;
+        a.slot_len[slot0 + i] = 0;
+    }
+};
+
+__global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
+    LiveStoreSink sk;
+    live_gate_walk(a, sk);
 }
 
 __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const uint8_t* mask, int32_t n) {
@@ -245,10 +293,19 @@ struct afsk_live {
     afsk::LiveLayout L;
     int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;   // (a mixed receiver: bit_frames 0)
     afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
+    int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip; L: n and slots only)
     ~afsk_live() {
         if (plan) (void)afsk_group_plan_destroy(plan);
     }
 };
+
+namespace afsk {
+// the streaming receiver's push and reset (afsk_live_stream.hip), after afsk_live_push's / afsk_live_reset's checks
+int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
+                     int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
+                     const DemodOutputs& o, hipStream_t stream);
+int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_t stream);
+}  // namespace afsk
 
 extern "C" {
 
@@ -334,7 +391,12 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
         return afsk::fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
     if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
         return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (live->max_payload_len >= 0 && out_margins)
+        return afsk::fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
     if (int rc = live->state.check_current()) return rc;
+    if (live->max_payload_len >= 0)
+        return afsk::live_stream_push(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
+                                      out_burst_len, out_flags, o, (hipStream_t)hip_stream);
     const afsk::LiveLayout& L = live->L;
     uint8_t* d = live->state.ptr();
     afsk::LiveArgs g{};
@@ -374,6 +436,7 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
 int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_stream) {
     if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
     if (int rc = live->state.check_current()) return rc;
+    if (live->max_payload_len >= 0) return afsk::live_stream_reset(live, d_mask_or_null, (hipStream_t)hip_stream);
     hipLaunchKernelGGL(afsk::live_reset_kernel, dim3((uint32_t)((live->L.n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)hip_stream, static_cast<afsk::LiveChan*>(live->state.d), d_mask_or_null,
                        (int32_t)live->L.n);

@@ -31,6 +31,7 @@ from .modem import _text_or_bytes
 
 DEFAULT_MAX_BURST_LEN = 2 * _native.SAMPLE_RATE     # 2 s: longer bursts are reported as overflowed, not decoded
 DEFAULT_MAX_CHUNK_LEN = 8192
+DEFAULT_MAX_PAYLOAD_LEN = 256                       # the live transmitter's and the streaming receiver's default
 
 
 def _per_channel(value, n_channels: int, name: str):
@@ -90,6 +91,15 @@ def layout(n_channels: int, max_burst_len: int, max_chunk_len: int) -> tuple[int
     return int(slots.value), int(nbytes.value)
 
 
+def stream_layout(n_channels: int, max_payload_len: int, max_chunk_len: int) -> tuple[int, int]:
+    """(slots per channel and push, device state bytes) of a streaming live receiver (``afsk_live_stream_layout``:
+    host-only)."""
+    slots, nbytes = C.c_int32(), C.c_int64()
+    _native.check(_native.lib().afsk_live_stream_layout(int(n_channels), int(max_payload_len), int(max_chunk_len),
+                                                        C.byref(slots), C.byref(nbytes)))
+    return int(slots.value), int(nbytes.value)
+
+
 @dataclass
 class LiveResult:
     """Device-resident outputs of one push (torch tensors).  Slot ``(c, k)`` is the k-th burst channel c reported in
@@ -137,12 +147,21 @@ class LiveReceiver(batch._NativePlan):
     ``max_burst_len``: the longest burst that is stored and demodulated (samples, >= 4096); a longer one is still
     gated exactly, and reported with its true start and length and ``LIVE_OVERFLOW``.  ``max_chunk_len``: the
     largest T a push accepts.  Both size the device state (``layout``): per channel a record row of
-    ``(max_burst_len // 2048 + (2047 + max_chunk_len) // 2048) * 2048`` samples.  The receiver belongs to the device
-    that was current (or ``device``); ``close()`` only after its pushes have completed."""
+    ``(max_burst_len // 2048 + (2047 + max_chunk_len) // 2048) * 2048`` samples.
+
+    ``max_burst_len=None`` builds the STREAMING receiver (``afsk_live_create_stream``): the same gate, slots and
+    outputs, every burst demodulated while it is gated, with no cap on burst length (``LIVE_OVERFLOW`` only beyond
+    ``MAX_STREAM_LEN``, status BAD_LENGTH) and a state per channel that does not depend on it (``stream_layout``).
+    Its capacity is ``max_payload_len`` (0 ... 65536) bytes of payload per burst: a longer payload's row is truncated,
+    its ``nbytes`` is the full count.  It has no margins.
+
+    The receiver belongs to the device that was current (or ``device``); ``close()`` only after its pushes have
+    completed."""
     _destroy = "afsk_live_destroy"
 
     def __init__(self, n_channels: int, bit_frames: int, amp_start_threshold=18000, amp_end_threshold=14000,
-                 max_burst_len: int = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN, device=None):
+                 max_burst_len: int | None = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN,
+                 device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN):
         torch = batch._torch()
         self.n_channels = int(n_channels)
         rates = _per_channel(bit_frames, self.n_channels, "bit_frames")
@@ -154,19 +173,34 @@ class LiveReceiver(batch._NativePlan):
         batch.validate_bit_frames(np.asarray(rates, np.int64))
         self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
         self.bit_frames = None if len(set(rates)) > 1 else int(rates[0]) if rates else None
-        self.max_burst_len = int(max_burst_len)
+        self.streaming = max_burst_len is None
+        self.max_burst_len = None if self.streaming else int(max_burst_len)
+        self.max_payload_len = int(max_payload_len) if self.streaming else None
         self.max_chunk_len = int(max_chunk_len)
-        self.slots = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)[0]   # (before the device check)
+        if self.streaming:                                                            # (before the device check)
+            self.slots = stream_layout(self.n_channels, self.max_payload_len, self.max_chunk_len)[0]
+        else:
+            self.slots = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)[0]
         super().__init__(device)
-        # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
         self._min_bf = int(min(rates))
-        self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self._min_bf)
+        if self.streaming:
+            # the streaming rows hold max_payload_len bytes
+            self.out_stride = self.max_payload_len
+        else:
+            # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
+            self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self._min_bf)
         nbytes = C.c_int64()
+        start, end = batch.threshold_gt(amp_start_threshold), batch.threshold_lt(amp_end_threshold)
         with torch.cuda.device(self.device):
-            # (one rate in every entry: the C entry builds the one-rate receiver)
-            _native.check(_native.lib().afsk_live_create_mixed(
-                self.n_channels, _i32_ptr(self.channel_bit_frames), batch.threshold_gt(amp_start_threshold),
-                batch.threshold_lt(amp_end_threshold), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
+            if self.streaming:
+                _native.check(_native.lib().afsk_live_create_stream(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), start, end, self.max_payload_len,
+                    self.max_chunk_len, C.byref(self._h)))
+            else:
+                # (one rate in every entry: the C entry builds the one-rate receiver)
+                _native.check(_native.lib().afsk_live_create_mixed(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), start, end, self.max_burst_len,
+                    self.max_chunk_len, C.byref(self._h)))
             _native.check(_native.lib().afsk_live_info(self.handle, None, None, C.byref(nbytes)))
         self.state_bytes = int(nbytes.value)
 
@@ -174,7 +208,7 @@ class LiveReceiver(batch._NativePlan):
     def from_receivers(cls, receivers, **capacities) -> "LiveReceiver":
         """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  Their thresholds must agree
         (ValueError otherwise): the gate's thresholds are the receiver's.  ``capacities``: ``max_burst_len`` /
-        ``max_chunk_len`` (samples) and ``device``."""
+        ``max_chunk_len`` (samples), ``max_payload_len`` (bytes, with ``max_burst_len=None``) and ``device``."""
         receivers = list(receivers)
         if not receivers:
             raise ValueError("from_receivers needs at least one Receiver")
@@ -186,11 +220,14 @@ class LiveReceiver(batch._NativePlan):
 
     def alloc_result(self, diagnostics: bool = False, margin_stride: int | None = None) -> LiveResult:
         """Output buffers for ``push(out=...)`` (double-buffered pushes, graph capture).  ``diagnostics``: also the
-        demodulator's ``corrected`` / ``margins`` (``margin_stride`` symbols per slot, default: the longest burst)."""
+        demodulator's ``corrected`` / ``margins`` (``margin_stride`` symbols per slot, default: the longest burst);
+        a streaming receiver has ``corrected`` only (``margins`` None)."""
         torch = batch._torch()
         n, s, dev = self.n_channels, self.slots, self.device
         demod = batch.alloc_result(n * s, self.out_stride, dev)
-        if diagnostics:
+        if diagnostics and self.streaming:
+            demod.corrected = torch.zeros(n * s, dtype=torch.int32, device=dev)
+        elif diagnostics:
             ms = int(margin_stride) if margin_stride is not None else self.max_burst_len // self._min_bf + 1
             demod.corrected = torch.zeros(n * s, dtype=torch.int32, device=dev)
             demod.margins = torch.zeros((n * s, ms), dtype=torch.int32, device=dev)
@@ -234,6 +271,8 @@ class LiveReceiver(batch._NativePlan):
         soft = (None, None, 0)
         if d.corrected is not None and d.margins is not None:
             soft = (d.corrected.data_ptr(), d.margins.data_ptr(), int(d.margins.shape[1]))
+        elif d.corrected is not None and self.streaming:
+            soft = (d.corrected.data_ptr(), None, 0)
         T = int(chunk.shape[1])
         with torch.cuda.device(dev):
             if fresh or uploaded:
@@ -272,7 +311,6 @@ class LiveReceiver(batch._NativePlan):
 # ------------------------------------------------------------------------------------------------- live transmit
 
 DEFAULT_QUEUE_DEPTH = 4
-DEFAULT_MAX_PAYLOAD_LEN = 256
 
 
 def tx_layout(n_channels: int, queue_depth: int, max_payload_len: int) -> int:

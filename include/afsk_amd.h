@@ -514,6 +514,45 @@ extern int afsk_live_create_mixed(int32_t n_channels, const int32_t *bit_frames_
                                   afsk_live **out);
 
 /*
+ * The streaming live receiver (added after ABI version 2; the version is unchanged): the live receiver's gate, slots,
+ * push, flush, reset and outputs, with every burst demodulated WHILE its blocks are gated.  It stores no samples of a
+ * burst beyond the fewer than 4096 the next push needs, so a burst of any length is decoded and the state per channel
+ * does not depend on burst length.  The object is an afsk_live: push, reset, info and destroy serve it unchanged.
+ *
+ *  afsk_live_stream_layout  host-only (no device needed): the slots per channel (1 + K / 3, as afsk_live_layout) and
+ *                           the device state bytes afsk_live_create_stream would allocate:
+ *                             a256(32 n) + a256(4096 n) + a256(32 n) + a256(4 n) + a256(8192 n)
+ *                               + a256(max_payload_len * n) + 256,      a256(x) = x rounded up to a multiple of 256
+ *                           (gate state, carry, demodulator, bit_frames, sample window, payload row), i.e. at most
+ *                           16 KiB + max_payload_len + 256 bytes per channel, whatever the bursts' length.
+ *  afsk_live_create_stream  bit_frames_host: HOST array [n_channels], each as afsk_demod_batch_uniform (a bad rate in
+ *                           any channel: AFSK_E_INVALID_BAUD); amp_start / amp_end as afsk_live_create;
+ *                           0 <= max_payload_len <= 65536 (the live transmitter's range), max_chunk_len as
+ *                           afsk_live_create; n_channels < 1, a NULL array or NULL out: AFSK_E_INVALID_ARG.  Allocates
+ *                           and zeroes the state on the current device (synchronous).
+ * A push or flush of a streaming receiver gives, for any sequence of pushes:
+ *   - the out_n_closed, out_burst_start, out_burst_len, out_flags and slot layout of a stored receiver whose
+ *     max_burst_len holds every burst (AFSK_LIVE_OVERFLOW: see below);
+ *   - for every used slot, the DemodOutputs (nbytes, nbits, clock_idx, term_frame, status, corrected, byte row) of
+ *     afsk_demod_batch_uniform over the burst's recorded samples at its channel's bit_frames, except that a byte row
+ *     holds at most min(max_payload_len, out_stride) bytes (nbytes still gives the full count);
+ *   - unused slots written every push: length 0, flags 0, status AFSK_ST_TOO_SHORT, nbytes / nbits / corrected 0,
+ *     clock_idx and term_frame -1;
+ *   - AFSK_LIVE_OVERFLOW only for a burst longer than AFSK_MAX_STREAM_LEN, with status AFSK_ST_BAD_LENGTH (what the
+ *     batch entries answer for that length) and burst_len saturating at 2^31 - 2048;
+ *   - out_margins must be NULL (AFSK_E_INVALID_ARG otherwise); out_corrected is optional;
+ *   - flush reports the open burst as AFSK_LIVE_OPEN_END, demodulated over its whole blocks; reset with a mask drops
+ *     the masked channels' demodulator state too;
+ *   - ONE launch on hip_stream, nothing on the host in between: capturable into a graph.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_STREAM_SIGNATURES.)
+ */
+extern int afsk_live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32_t max_chunk_len,
+                                   int32_t *out_slots, int64_t *out_state_bytes);
+extern int afsk_live_create_stream(int32_t n_channels, const int32_t *bit_frames_host, int32_t amp_start_threshold,
+                                   int32_t amp_end_threshold, int32_t max_payload_len, int32_t max_chunk_len,
+                                   afsk_live **out);
+
+/*
  * The live transmitter (an addition: ABI version unchanged): Transmitter.transmit (:472-478) for n_channels
  * independent channels at one bit_frames and training length.  Every channel has a device-resident queue of up to
  * queue_depth messages; each pull writes the next n_samples samples of every channel's stream, the queued messages

@@ -1,0 +1,475 @@
+"""GPU parity (-m gpu) of the streaming live receiver (LiveReceiver(max_burst_len=None), afsk_live_create_stream).
+Expected values never come from a live object alone: the CPU oracle's gate (gate_stream) and demod (demod_batch) over
+the concatenated capture, the stored receiver on the same pushes (every output, corrected included), and the payloads a
+LiveTransmitter sent."""
+import numpy as np
+import pytest
+
+import afskmodem_amd as afskmodem
+from afskmodem_amd import _native
+from afskmodem_amd.live import LiveReceiver, LiveTransmitter
+from oracle import afsk_oracle as O
+from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+BLOCK = 2048
+FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
+RX_BFS = tuple(bf for bf in range(4, 2048, 4) if 48000 % bf == 0)        # 36 rates: 12000 ... 24 baud
+
+
+def collect(res, got, corrected=False):
+    """Append one push's bursts to got[c] as dicts (every field, the row up to nbytes)."""
+    nc = res.n_closed.cpu().numpy()
+    if not nc.any():
+        return
+    bs, bl, fl = (t.cpu().numpy() for t in (res.burst_start, res.burst_len, res.flags))
+    d = res.demod.cpu()
+    cor = res.demod.corrected.cpu().numpy() if corrected else None
+    s = res.slots
+    for c in np.nonzero(nc)[0].tolist():
+        for k in range(int(nc[c])):
+            j = c * s + k
+            row = dict(start=int(bs[c, k]), len=int(bl[c, k]), flags=int(fl[c, k]),
+                       bytes=d.bytes[j, : min(int(d.nbytes[j]), d.bytes.shape[1])].tobytes())
+            row.update({f: int(getattr(d, f)[j]) for f in FIELDS})
+            if corrected:
+                row["corrected"] = int(cor[j])
+            got[c].append(row)
+
+
+def sizes_for(T, total, rng):
+    if T == "random":
+        out = []
+        while sum(out) < total:
+            out.append(min(int(rng.choice([1, 7, 2047, 2048, 2049, 5000, 8192])), total - sum(out)))
+        return out
+    return [T] * (total // T) + ([total % T] if total % T else [])
+
+
+def drive(rx, d, sizes, corrected=False, flush=True):
+    got = [[] for _ in range(rx.n_channels)]
+    out = rx.alloc_result(diagnostics=corrected)
+    p = 0
+    for t in sizes:
+        collect(rx.push(d[:, p: p + t], out=out), got, corrected)
+        p += t
+    assert p == d.shape[1]
+    if flush:
+        collect(rx.flush(out=out), got, corrected)
+    return got
+
+
+def expected(cap, bf, a_start, a_end, maxp):
+    """The oracle's gate + demod of one channel's whole capture (bursts with their outputs)."""
+    want, oe = O.gate_stream(cap, a_start, a_end, 4096)
+    out = []
+    for j, (s, n) in enumerate(want):
+        r = O.demod_batch(cap[s: s + n], [0], [n], [bf], a_end, out_stride=max(maxp, 1))
+        row = dict(start=s, len=n, flags=_native.LIVE_OPEN_END if (oe and j == len(want) - 1) else 0)
+        row.update({f: int(r[f][0]) for f in FIELDS})
+        row["bytes"] = r["bytes"][0, : min(row["nbytes"], maxp)].tobytes()
+        out.append(row)
+    return out
+
+
+def same(got, want):
+    """The streaming receiver's bursts of one channel against the oracle's (every field the oracle has)."""
+    return len(got) == len(want) and all({k: g[k] for k in w} == w for g, w in zip(got, want))
+
+
+def noisy(rng, x, sigma):
+    return np.clip(x + rng.normal(0, sigma, x.size), -32768, 32767).astype(np.int16)
+
+
+def capture_of(rng, bf, payloads, gap=3 * BLOCK, sigma=2000.0, training=0.5):
+    """Messages with quiet gaps, in noise.  A message starts a random number of samples into a block, fewer than
+    the clock search covers (4096 - 2 bf offsets) from 1000 samples per symbol on: the gate cuts bursts at block
+    boundaries, so a slower message starting later in its block is not decodable, by the reference either."""
+    tr = afskmodem.Transmitter(48000 // bf, training)
+    lim = BLOCK if 4096 - 2 * bf >= BLOCK else 4096 - 2 * bf - 8
+    parts, n = [], 0
+    for p in payloads:
+        pad = (-n) % BLOCK + gap + int(rng.integers(0, lim))
+        parts += [np.zeros(pad, np.int16), tr.wav_samples(p)]
+        n += pad + parts[-1].size
+    parts.append(np.zeros(gap + int(rng.integers(0, BLOCK)), np.int16))
+    return noisy(rng, np.concatenate(parts), sigma)
+
+
+@pytest.mark.parametrize("T", [1, 7, 2047, 2048, 2049, 8192, 48000, "random"])
+def test_long_payloads_beyond_the_stored_default(torch_cuda, T):
+    """256 B at 1200 baud, 64 B at 300 baud and 8 B at 24 baud: bursts longer than the stored receiver's 2 s default
+    (there: LIVE_OVERFLOW, not decoded), every one decoded here, equal to the oracle's gate + demod."""
+    torch = torch_cuda
+    rng = np.random.default_rng(7 if T == "random" else T)
+    cases = ((40, 256), (160, 64), (2000, 8))
+    if T in (1, 7):
+        cases = cases[:1]                                   # (one push per sample or seven: the 1200-baud case only)
+    for bf, plen in cases:
+        pays = [bytes(rng.integers(0, 256, plen, dtype=np.uint8)) for _ in range(2)]
+        caps = [capture_of(rng, bf, pays[i:i + 1] + [b"short"]) for i in range(2)]
+        total = max(c.size for c in caps)
+        host = np.zeros((2, total), np.int16)
+        for i, c in enumerate(caps):
+            host[i, : c.size] = c
+        rx = LiveReceiver(2, bf, max_burst_len=None, max_payload_len=256, max_chunk_len=48000, device=DEV)
+        got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(T, total, rng))
+        for i in range(2):
+            want = expected(host[i], bf, 18000, 14000, 256)
+            assert [g["start"] for g in got[i]] == [w["start"] for w in want], (bf, i)
+            for g, w in zip(got[i], want):
+                for f in ("len", "flags", "bytes") + FIELDS:
+                    assert g[f] == w[f], (bf, i, f, g[f], w[f])
+            assert got[i][0]["len"] > 2 * 48000 and got[i][0]["bytes"] == pays[i], (bf, i)
+        rx.close()
+
+
+def stored_vs_streaming(torch, host, bfs, sizes, maxp=4096, a=(18000, 14000)):
+    """The same pushes through a stored receiver that holds every burst and a streaming one: every output equal."""
+    n, total = host.shape
+    d = torch.from_numpy(host).to(DEV)
+    st = LiveReceiver(n, bfs, a[0], a[1], max_burst_len=(total // BLOCK + 2) * BLOCK, max_chunk_len=max(sizes),
+                      device=DEV)
+    sm = LiveReceiver(n, bfs, a[0], a[1], max_burst_len=None, max_payload_len=maxp, max_chunk_len=max(sizes),
+                      device=DEV)
+    assert st.slots == sm.slots
+    g1, g2 = drive(st, d, sizes, corrected=True), drive(sm, d, sizes, corrected=True)
+    st.close()
+    sm.close()
+    assert g1 == g2
+    return g2
+
+
+@pytest.mark.parametrize("bf", RX_BFS)
+def test_every_rate_against_the_stored_receiver_and_the_oracle(torch_cuda, bf):
+    torch = torch_cuda
+    rng = np.random.default_rng(bf)
+    n = 3
+    caps = [capture_of(rng, bf, [bytes(rng.integers(0, 256, int(rng.integers(1, 6)), dtype=np.uint8))],
+                       sigma=[500.0, 4000.0, 9000.0][i], training=max(0.02, 3.0 * bf / 48000)) for i in range(n)]
+    total = max(c.size for c in caps) + 4 * BLOCK
+    host = np.zeros((n, total), np.int16)
+    for i, c in enumerate(caps):
+        host[i, : c.size] = c
+    got = stored_vs_streaming(torch, host, bf, sizes_for("random", total, rng))
+    for i in range(n):
+        want = expected(host[i], bf, 18000, 14000, 4096)
+        assert same(got[i], want), i
+
+
+def test_mixed_receiver_all_rates_interleaved(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(36)
+    bfs = list(RX_BFS) * 2
+    rng.shuffle(bfs)
+    caps = [capture_of(rng, bf, [bytes(rng.integers(0, 256, 3, dtype=np.uint8))], sigma=3000.0,
+                       training=max(0.02, 3.0 * bf / 48000)) for bf in bfs]
+    total = max(c.size for c in caps) + 2 * BLOCK
+    host = np.zeros((len(bfs), total), np.int16)
+    for i, c in enumerate(caps):
+        host[i, : c.size] = c
+    got = stored_vs_streaming(torch, host, bfs, sizes_for(8192, total, rng))
+    for i, bf in enumerate(bfs):
+        want = expected(host[i], bf, 18000, 14000, 4096)
+        assert same(got[i], want), (i, bf)
+
+
+def test_traps_boundary_short_no_terminator_partial_codewords(torch_cuda):
+    """Trap 1: bursts whose last symbol ends exactly at the last recorded sample (ci + (k + 1) * bf == len, the
+    training placed `lead` samples into the burst so that ci = lead), closed by a quiet block and by the flush, pushed
+    in blocks; trap 2: a flushed one-block burst is TOO_SHORT; trap 3: training without a terminator is NO_DATA with
+    term_frame = ci + K * bf; trap 4: bursts cut inside the data phase (partial codewords and bytes)."""
+    torch = torch_cuda
+    rng = np.random.default_rng(4)
+    total = 400 * BLOCK
+    rows, bfs, boundary = [], [], 0
+
+    def ok(lead, bf):
+        return lead < 4096 - 2 * bf - 1 and lead < BLOCK - 64
+
+    for bf in (40, 160, 480, 2000, 24, 4):
+        baud = 48000 // bf
+        tr = np.tile(O.training_cycle(baud).astype(np.int16), total // bf + 2)
+        # closed by a quiet block: blocks [4, 4 + m), the last one quiet, len = m * 2048
+        m = next(m for m in range(3, 120) if ok((m * BLOCK) % bf, bf))
+        lead = (m * BLOCK) % bf
+        row = np.zeros(total, np.int16)
+        row[4 * BLOCK + lead: (3 + m) * BLOCK] = tr[: (m - 1) * BLOCK - lead]
+        rows.append(row)
+        # closed by the flush: blocks [sb, total / 2048), loud to the end
+        sb = next(sb for sb in range(4, 300) if ok((total - sb * BLOCK) % bf, bf))
+        lead = (total - sb * BLOCK) % bf
+        row = np.zeros(total, np.int16)
+        row[sb * BLOCK + lead:] = tr[: total - sb * BLOCK - lead]
+        rows.append(row)
+        # a message cut inside its data phase, then one loud block and the flush
+        x = afskmodem.Transmitter(baud, max(0.02, 3.0 * bf / 48000)).wav_samples(b"partial codewords here")
+        x = x[: min(x.size - 4800 - 5 * bf, total - 8 * BLOCK)]
+        row = np.zeros(total, np.int16)
+        row[total - x.size - BLOCK: total - BLOCK] = x
+        row[total - BLOCK:] = 30000
+        rows.append(row)
+        bfs += [bf] * 3
+    one = np.zeros(total, np.int16)
+    one[total - BLOCK:] = 30000                               # one loud block, then the flush
+    rows.append(one)
+    bfs.append(40)
+    host = np.stack(rows)
+    got = stored_vs_streaming(torch, host, bfs, sizes_for(BLOCK, total, rng))
+    statuses = set()
+    for i, bf in enumerate(bfs):
+        want = expected(host[i], bf, 18000, 14000, 4096)
+        assert same(got[i], want), (i, bf)
+        statuses |= {g["status"] for g in got[i]}
+        for g in got[i]:
+            if g["clock_idx"] >= 0 and (g["len"] - g["clock_idx"]) % bf == 0:
+                boundary += 1
+    assert got[-1][-1]["status"] == _native.ST_TOO_SHORT and got[-1][-1]["flags"] == _native.LIVE_OPEN_END
+    assert {_native.ST_NO_DATA, _native.ST_OK, _native.ST_TOO_SHORT} <= statuses
+    assert boundary >= 6                                       # the K-rule boundary was exercised
+
+
+def test_many_bursts_in_one_push_and_one_burst_over_hundreds_of_pushes(torch_cuda):
+    """Trap 5: the slot bound filled by bursts that open and close within one push, a burst closing in a push's first
+    block, and one burst spanning hundreds of pushes."""
+    torch = torch_cuda
+    rng = np.random.default_rng(5)
+    T = 8 * BLOCK * 6
+    n = 4
+    host = np.zeros((n, 400 * 2048), np.int16)
+    # channel 0: discard / start / end blocks back to back: every push fills its slots
+    for b in range(2, host.shape[1] // BLOCK - 1, 3):
+        host[0, b * BLOCK: (b + 1) * BLOCK] = 30000
+    # channel 1: a burst that closes in the first block of each push
+    for p in range(1, host.shape[1] // T):
+        host[1, p * T - 5 * BLOCK: p * T] = 30000
+    # channel 2: one long message over the whole capture (1200 baud, 256 bytes), channel 3 noise
+    w = afskmodem.Transmitter(1200, 0.5).wav_samples(bytes(rng.integers(0, 256, 256, dtype=np.uint8)))
+    host[2, 2 * BLOCK: 2 * BLOCK + w.size] = w
+    host[3] = noisy(rng, np.zeros(host.shape[1]), 12000.0)
+    got = stored_vs_streaming(torch, host, 40, sizes_for(T, host.shape[1], rng))
+    for i in range(n):
+        want = expected(host[i], 40, 18000, 14000, 4096)
+        assert same(got[i], want), i
+    small = stored_vs_streaming(torch, host[:, :300 * BLOCK], 40, sizes_for(511, 300 * BLOCK, rng))
+    assert len(small[2]) == 1 and small[2][0]["len"] > 300 * 511 and small[2][0]["status"] == _native.ST_OK
+
+
+def test_payload_rows_truncate_at_max_payload_len(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(6)
+    data = bytes(rng.integers(0, 256, 40, dtype=np.uint8))
+    cap = capture_of(rng, 40, [data], sigma=0.0)
+    host = np.stack([cap, cap])
+    for maxp in (0, 1, 13, 39, 40):
+        rx = LiveReceiver(2, 40, max_burst_len=None, max_payload_len=maxp, device=DEV)
+        got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(8192, cap.size, rng))
+        rx.close()
+        for g in got:
+            assert g[0]["nbytes"] == 40 and g[0]["bytes"] == data[:maxp], maxp
+
+
+def test_graph_captured_push_matches_eager(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(8)
+    n, T = 64, 4096
+    bfs = [RX_BFS[i % len(RX_BFS)] for i in range(n)]
+    caps = [capture_of(rng, bf, [b"graph"], training=max(0.02, 3.0 * bf / 48000)) for bf in bfs]
+    total = -(-max(c.size for c in caps) // T) * T
+    host = np.zeros((n, total), np.int16)
+    for i, c in enumerate(caps):
+        host[i, : c.size] = c
+    d = torch.from_numpy(host).to(DEV)
+    eager = LiveReceiver(n, bfs, max_burst_len=None, max_chunk_len=T, device=DEV)
+    graphed = LiveReceiver(n, bfs, max_burst_len=None, max_chunk_len=T, device=DEV)
+    src = torch.zeros((n, T), dtype=torch.int16, device=DEV)
+    out_g = graphed.alloc_result(diagnostics=True)
+    s = torch.cuda.Stream(DEV)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            graphed.push(src, out=out_g, stream=s)
+    torch.cuda.current_stream().wait_stream(s)
+    graphed.reset()
+    got_e, got_g = [[] for _ in range(n)], [[] for _ in range(n)]
+    out_e = eager.alloc_result(diagnostics=True)
+    for p in range(0, total, T):
+        src.copy_(d[:, p: p + T])
+        g.replay()
+        collect(out_g, got_g, True)
+        collect(eager.push(d[:, p: p + T], out=out_e), got_e, True)
+    assert got_e == got_g
+    assert sum(len(x) for x in got_e) >= n // 2
+
+
+def test_flush_and_masked_reset(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(9)
+    n = 6
+    w = afskmodem.Transmitter(1200, 0.5).wav_samples(b"reset me")
+    host = np.zeros((n, 4 * BLOCK + w.size + 4 * BLOCK), np.int16)
+    host[:, 4 * BLOCK: 4 * BLOCK + w.size] = w
+    d = torch.from_numpy(host).to(DEV)
+    rx = LiveReceiver(n, 40, max_burst_len=None, max_chunk_len=host.shape[1], device=DEV)
+    half = 4 * BLOCK + w.size // 2
+    out = rx.alloc_result()
+    rx.push(d[:, :half], out=out)
+    mask = np.array([1, 0, 1, 0, 0, 1], np.uint8)
+    rx.reset(mask)
+    got = [[] for _ in range(n)]
+    collect(rx.push(d[:, half:], out=out), got)
+    collect(rx.flush(out=out), got)
+    for c in range(n):
+        # a reset channel starts a new stream at `half`: what the oracle gates in the rest of the capture
+        want = expected(host[c, half:] if mask[c] else host[c], 40, 18000, 14000, 256)
+        assert same(got[c], want), c
+    assert got[1][0]["bytes"] == b"reset me"
+    # a flush of an open burst: OPEN_END over its whole blocks
+    rx.reset()
+    got = [[] for _ in range(n)]
+    collect(rx.push(d[:, : 4 * BLOCK + w.size - 3000], out=out), got)
+    collect(rx.flush(out=out), got)
+    cut = host[0, : 4 * BLOCK + w.size - 3000]
+    want = expected(cut, 40, 18000, 14000, 256)
+    assert want[-1]["flags"] == _native.LIVE_OPEN_END
+    for c in range(n):
+        assert same(got[c], want), c
+    rx.close()
+
+
+def test_loopback_4096_mixed_channels_default_capacities(torch_cuda):
+    """A LiveTransmitter(max_payload_len=256) into a default streaming receiver: every 256-byte payload decodes."""
+    torch = torch_cuda
+    rng = np.random.default_rng(10)
+    n = 4096
+    bauds = rng.choice([1200, 2400, 4000, 6000, 1000, 600, 300], n)   # (12000 baud: the reference decodes no
+                                                                     # 256-byte message either)
+    tx = LiveTransmitter(n, bauds.tolist(), 0.1, max_payload_len=256, device=DEV)
+    rx = LiveReceiver(n, (48000 // bauds).tolist(), max_burst_len=None, device=DEV)
+    pays = [bytes(rng.integers(0, 256, 256, dtype=np.uint8)) for _ in range(n)]
+    tx.submit(np.arange(n), pays)
+    T = 8192
+    longest = int(np.max(tx.message_len(256))) + 4 * T
+    buf = torch.zeros((n, T), dtype=torch.int16, device=DEV)
+    out = rx.alloc_result()
+    got = [[] for _ in range(n)]
+    zeros = torch.zeros((n, T), dtype=torch.int16, device=DEV)
+    rx.push(zeros, out=out)                                    # (the discard block)
+    for _ in range(0, longest, T):
+        tx.pull(T, out=buf)
+        collect(rx.push(buf, out=out), got)
+    collect(rx.flush(out=out), got)
+    for c in range(n):
+        assert [g["bytes"] for g in got[c]] == [pays[c]], c
+    tx.close()
+    rx.close()
+
+
+def test_scale_65536_channels_8192(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(11)
+    n, T = 65536, 8192
+    w = afskmodem.Transmitter(1200, 0.1).wav_samples(b"65536")
+    total = 3 * T
+    row = np.zeros(total, np.int16)
+    row[T // 2: T // 2 + w.size] = w
+    shifts = rng.integers(0, 2 * BLOCK, n)
+    d = torch.from_numpy(row).to(DEV).repeat(n, 1)
+    idx = (torch.arange(total, device=DEV)[None, :] - torch.from_numpy(shifts).to(DEV)[:, None]) % total
+    d = torch.gather(d, 1, idx)
+    rx = LiveReceiver(n, 40, max_burst_len=None, max_chunk_len=T, device=DEV)
+    out = rx.alloc_result()
+    got = [[] for _ in range(n)]
+    for p in range(0, total, T):
+        collect(rx.push(d[:, p: p + T], out=out), got)
+    collect(rx.flush(out=out), got)
+    host = d.cpu().numpy()
+    for c in rng.choice(n, 64, replace=False).tolist():
+        want = expected(host[c], 40, 18000, 14000, 256)
+        assert same(got[c], want), c
+    assert all(any(g["bytes"] == b"65536" for g in got[c]) for c in range(n))
+    rx.close()
+
+
+def test_past_2_31_and_2_32_samples(torch_cuda):
+    """int64 stream positions: bursts straddling 2^31 and 2^32 decode with burst-relative ci / term_frame; a loud
+    stretch longer than AFSK_MAX_STREAM_LEN is OVERFLOW + BAD_LENGTH, burst_len saturating at 2^31 - 2048."""
+    torch = torch_cuda
+    C = 1 << 24
+    rx = LiveReceiver(2, 40, max_burst_len=None, max_chunk_len=C, device=DEV)
+    out = rx.alloc_result()
+    quiet = torch.zeros((2, C), dtype=torch.int16, device=DEV)
+    loud = quiet.clone()
+    loud[1] = 20000
+    tr = afskmodem.Transmitter(1200, 0.1)
+    got = [[], []]
+    state = {"pos": 0}
+
+    def to(target, src):
+        while state["pos"] < target:
+            t = min(C, target - state["pos"])
+            collect(rx.push(src[:, :t], out=out), got)
+            state["pos"] += t
+
+    def push_capture(cap, sizes):
+        dd = torch.from_numpy(cap).to(DEV)
+        p = 0
+        for t in sizes:
+            collect(rx.push(dd[:, p: p + t], out=out), got)
+            p += t
+        state["pos"] += p
+
+    to(C, quiet)
+    to((1 << 31) - 3 * BLOCK - 1, loud)
+    assert got == [[], []]
+    for target, msg in (((1 << 31) - 2 * BLOCK, b"straddles 2^31"), ((1 << 32) - 2 * BLOCK, b"straddles 2^32")):
+        P0 = state["pos"]
+        wa = tr.wav_samples(msg)
+        la = target + wa.size + 3 * BLOCK - P0
+        cap = np.zeros((2, la), np.int16)
+        cap[0, target - P0: target - P0 + wa.size] = wa
+        cap[1] = 20000 if target < (1 << 32) - 2 * BLOCK else 0
+        push_capture(cap, [1, 2047, 2049, 8191] + [4097] * ((la - 12288) // 4097) + [(la - 12288) % 4097])
+        b = [g for g in got[0] if g["bytes"] == msg]
+        assert len(b) == 1 and b[0]["start"] <= target < b[0]["start"] + b[0]["len"], msg
+        win = cap[0, b[0]["start"] - P0: b[0]["start"] - P0 + b[0]["len"]]
+        r = O.demod_batch(win, [0], [win.size], [40], 14000, out_stride=64)
+        assert all(b[0][f] == int(r[f][0]) for f in FIELDS), msg
+        if target < (1 << 32) - 2 * BLOCK:
+            to((1 << 32) - 3 * BLOCK - 1, loud)
+    collect(rx.flush(out=out), got)
+    ovf = [g for g in got[1] if g["flags"] & _native.LIVE_OVERFLOW]
+    assert len(ovf) == 1 and ovf[0]["status"] == _native.ST_BAD_LENGTH and ovf[0]["len"] == (1 << 31) - BLOCK
+    assert ovf[0]["clock_idx"] == -1 and ovf[0]["term_frame"] == -1 and ovf[0]["nbits"] == 0
+    rx.close()
+
+
+def test_device_argument_checks(torch_cuda):
+    torch = torch_cuda
+    import ctypes as C
+    rx = LiveReceiver(2, [40, 160], max_burst_len=None, max_chunk_len=4096, device=DEV)
+    res = rx.alloc_result(diagnostics=True)
+    assert res.demod.margins is None and res.demod.corrected is not None
+    d = res.demod
+    chunk = torch.zeros((2, 4096), dtype=torch.int16, device=DEV)
+    m = torch.zeros((2 * rx.slots, 8), dtype=torch.int32, device=DEV)
+    lib = _native.lib()
+    args = [rx.handle, chunk.data_ptr(), 4096, 4096, 0, res.n_closed.data_ptr(), res.burst_start.data_ptr(),
+            res.burst_len.data_ptr(), res.flags.data_ptr(), d.bytes.data_ptr(), int(d.bytes.shape[1]),
+            d.nbytes.data_ptr(), d.nbits.data_ptr(), d.clock_idx.data_ptr(), d.term_frame.data_ptr(),
+            d.status.data_ptr(), d.corrected.data_ptr()]
+    for ms in (8, 0):
+        assert lib.afsk_live_push(*args, m.data_ptr(), ms, None) == _native.E_INVALID_ARG
+    assert lib.afsk_live_push(*args[:3], 4097, *args[4:], None, 0, None) == _native.E_INVALID_ARG
+    assert lib.afsk_live_push(*args[:5], None, *args[6:], None, 0, None) == _native.E_INVALID_ARG
+    assert lib.afsk_live_push(*args, None, 0, None) == _native.OK
+    assert lib.afsk_live_push(*args[:16], None, None, 0, None) == _native.OK      # corrected is optional
+    n, s, b = C.c_int32(), C.c_int32(), C.c_int64()
+    assert lib.afsk_live_info(rx.handle, C.byref(n), C.byref(s), C.byref(b)) == 0
+    assert (n.value, s.value, b.value) == (2, rx.slots, rx.state_bytes)
+    assert rx.state_bytes == afskmodem.live.stream_layout(2, 256, 4096)[1]
+    assert rx.bit_frames is None and list(rx.channel_bit_frames) == [40, 160]
+    torch.cuda.synchronize()
+    rx.close()

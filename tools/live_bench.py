@@ -3,6 +3,10 @@
 
     python tools/live_bench.py [--shapes 65536x2048,65536x8192,64x48000] [--seconds 4] [--reps 3] [--json OUT]
                                [--no-verify] [--kernel-stats STATS_CSV]
+    python tools/live_bench.py --stream [--stream-cases 65536x8192@1200,...,16384x8192@long] [--json OUT]
+
+--stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
+(stream_ab below).
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -152,6 +156,99 @@ def run_shape(torch, n, T, seconds, reps, verify, seed):
     return rec
 
 
+def graphs_for(torch, rx, samples, n_push, T, out):
+    """One captured push per column window of `samples`, in stream order."""
+    graphs = []
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for p in range(n_push):
+            gph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gph, stream=side):
+                rx.push(samples[:, p * T: (p + 1) * T], out=out)
+            graphs.append(gph)
+    torch.cuda.synchronize()
+    return graphs
+
+
+def timed_pass(torch, rx, graphs):
+    rx.flush()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in graphs]
+    for g, (a, b) in zip(graphs, ev):
+        a.record()
+        g.replay()
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) * 1e3 for a, b in ev]
+
+
+def stream_ab(torch, n, T, seconds, baud, reps, seed, long_messages=False):
+    """The stored and the streaming receiver on the same pushes of one workload, timed alternately (stored pass,
+    streaming pass, ... after one warm-up pass each).  The synthetic workload is run_shape's at `baud` (stored
+    max_burst_len 1 s); long_messages: LiveTransmitter channels with 256-byte payloads back to back at 1200 baud
+    (stored max_burst_len 4 s).  The streaming receiver's algorithmic bytes: 2 B per pushed sample + its outputs
+    (gate fields and DemodOutputs per slot, the payload bytes) -- it reads no burst a second time."""
+    from afskmodem_amd.live import LiveTransmitter
+    total = int(seconds * 48000)
+    n_push = total // T
+    total = n_push * T
+    bf = 48000 // baud
+    if long_messages:
+        tx = LiveTransmitter(n, baud, 0.5, max_payload_len=256)
+        rng = np.random.default_rng(seed)
+        pays = [bytes(rng.integers(0, 256, 256, dtype=np.uint8)) for _ in range(2 * n)]
+        tx.submit(np.repeat(np.arange(n), 2), pays)
+        samples = torch.zeros((n, total), dtype=torch.int16, device="cuda")
+        samples[:, 4 * BLOCK:] = tx.pull(total - 4 * BLOCK)
+        tx.close()
+        max_burst = 4 * 48000
+    else:
+        plens = (4, 12, 24) if bf <= 160 else (1,)
+        samples, _ = synth.live_channels(n, total, baud, seed, bursts_per_channel=2 if bf <= 160 else 1,
+                                         payload_lens=plens, silent_every=8, device="cuda")
+        max_burst = 48000 if bf <= 160 else 4 * 48000
+    stored = LiveReceiver(n, bf, max_burst_len=max_burst, max_chunk_len=T)
+    streaming = LiveReceiver(n, bf, max_burst_len=None, max_payload_len=256, max_chunk_len=T)
+    # eager pass of both: equal bursts (payloads) wherever the stored receiver holds them
+    bursts = []
+    for rx in (stored, streaming):
+        got = []
+        out = rx.alloc_result()
+        for p in range(n_push):
+            got += rx.push(samples[:, p * T: (p + 1) * T], out=out, flush=p == n_push - 1).bursts()
+        bursts.append(got)
+    ovf = sum(1 for b in bursts[0] if b[3] == b"" and b[2] > max_burst)
+    same = sum(1 for a, b in zip(bursts[0], bursts[1]) if a == b)
+    decoded = sum(1 for b in bursts[1] if b[3])
+    outs = [stored.alloc_result(), streaming.alloc_result()]
+    graphs = [graphs_for(torch, rx, samples, n_push, T, o) for rx, o in zip((stored, streaming), outs)]
+    times = [[], []]
+    for r in range(reps + 1):
+        for i, rx in enumerate((stored, streaming)):
+            t = timed_pass(torch, rx, graphs[i])
+            if r:
+                times[i] += t
+    us = [float(np.mean(t)) for t in times]
+    slot_out = n * streaming.slots * (8 + 4 + 4 + 20) + n * 4
+    pay = sum(len(b[3]) for b in bursts[1])
+    alg = 2 * n * T + slot_out + pay / n_push
+    rec = dict(shape=f"{n}x{T}", baud=baud, workload="long_messages_256B" if long_messages else "synthetic",
+               pushes=n_push, stored_max_burst_len=max_burst,
+               stored_state_bytes=stored.state_bytes, streaming_state_bytes=streaming.state_bytes,
+               stored_us_mean=round(us[0], 2), streaming_us_mean=round(us[1], 2),
+               stored_us_median=round(float(np.median(times[0])), 2),
+               streaming_us_median=round(float(np.median(times[1])), 2),
+               streaming_over_stored=round(us[1] / us[0], 3),
+               streaming_alg_bytes_per_push=int(alg), streaming_share_of_peak=round(alg / (us[1] * 1e-6) / PEAK, 3),
+               bursts=len(bursts[1]), streaming_decoded=decoded, equal_to_stored=f"{same}/{len(bursts[0])}",
+               stored_overflowed=ovf)
+    del graphs, samples
+    stored.close()
+    streaming.close()
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="65536x2048,65536x8192,64x48000")
@@ -163,6 +260,11 @@ def main():
     ap.add_argument("--kernel-stats", help="rocprofv3 --stats kernel CSV of a run of this tool: adds the gate's share")
     ap.add_argument("--results", help="with --kernel-stats: the JSON of the timed run to annotate")
     ap.add_argument("--profiled-shape", help="with --kernel-stats: the one shape the profiled run timed")
+    ap.add_argument("--stream", action="store_true",
+                    help="stored vs streaming receiver, alternating, per --stream-cases entry (shape@baud, "
+                         "shape@long for the LiveTransmitter 256-byte workload)")
+    ap.add_argument("--stream-cases", default="65536x8192@1200,65536x2048@1200,65536x8192@12000,65536x8192@300,"
+                                              "16384x8192@24,16384x8192@long")
     args = ap.parse_args()
     if args.kernel_stats:
         rows = list(csv.DictReader(open(args.kernel_stats)))
@@ -184,6 +286,20 @@ def main():
         return
     import torch
     res = []
+    if args.stream:
+        for case in args.stream_cases.split(","):
+            shape, kind = case.split("@")
+            n, T = (int(x) for x in shape.split("x"))
+            long_messages = kind == "long"
+            rec = stream_ab(torch, n, T, args.seconds, 1200 if long_messages else int(kind), args.reps, args.seed,
+                            long_messages)
+            print(json.dumps(rec), flush=True)
+            res.append(rec)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(tool="tools/live_bench.py --stream", seconds=args.seconds, reps=args.reps, results=res),
+                          f, indent=1)
+        return
     for s in args.shapes.split(","):
         n, T = (int(x) for x in s.split("x"))
         rec = run_shape(torch, n, T, args.seconds, args.reps, not args.no_verify, args.seed)
