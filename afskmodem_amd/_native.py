@@ -153,6 +153,22 @@ LIVE_STREAM_SIGNATURES = {
 }
 
 
+# The live receivers with a threshold pair per channel (afsk_live_create_thresholds,
+# afsk_live_create_stream_thresholds), bound by lib() from a table of their own for the same reason.
+LIVE_THRESHOLD_SIGNATURES = {
+    "afsk_live_create_thresholds": (C.c_int, [C.c_int32, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_void_p)]),
+    "afsk_live_create_stream_thresholds": (C.c_int, [C.c_int32, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                                                     C.POINTER(C.c_void_p)]),
+}
+LIVE_MAX_SQUELCH_CLASSES = 16                # AFSK_LIVE_MAX_SQUELCH_CLASSES
+
+# The host-only view of a stored receiver's squelch classes, likewise.
+LIVE_CLASS_SIGNATURES = {
+    "afsk_live_squelch_classes": (C.c_int, [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+}
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -164,7 +180,8 @@ def lib() -> C.CDLL:
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
                                   *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items(),
-                                  *LIVE_STREAM_SIGNATURES.items()):
+                                  *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
+                                  *LIVE_CLASS_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

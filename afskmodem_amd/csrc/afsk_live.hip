@@ -14,6 +14,13 @@
 // slots with a group plan the receiver builds then (the per-stream kernel in rate-sorted order; DESIGN.md 8.2 has
 // the measurement against the per-stream kernel in slot order).
 //
+// A receiver with a threshold pair per channel (afsk_live_create_thresholds) keeps amp_start and amp_end as int32 [n]
+// behind the layout's bytes; its gate (live_gate_thr_kernel, the same walk) takes a channel's pair from there.  The
+// demod kernels take one amp_end per launch, so such a receiver launches them once per distinct amp_end -- a squelch
+// class, at most AFSK_LIVE_MAX_SQUELCH_CLASSES -- each over the list of that class's slots (DemodArgs::stream_index):
+// 1 + classes launches, still nothing on the host in between.  One class (distinct amp_start only) keeps the second
+// launch above.  SquelchClasses builds the lists at creation.
+//
 // Per channel the device keeps (LiveChan) the gate mode, the stream position, the open burst's start, length and
 // row offset, and a 2048-sample carry with the partial block at the end of the stream.  Row layout: the open
 // burst's prefix at the front, then every block recorded in this push, bursts back to back; at the start of the
@@ -129,7 +136,7 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 // machine with the next block's load in flight, and hands every event to its sink -- the stored receiver's
 // (LiveStoreSink: record rows and demodulator slots) or the streaming one's (afsk_live_stream.hip: demodulation as
 // the blocks arrive).  A sink has:
-//   init(a, c)                    the channel's state is loaded
+//   init(a, c, amp_end)           the channel's state is loaded (amp_end: the channel's squelch threshold)
 //   begin(a, lane, st)            before the first block
 //   overflowed(a, st)             the burst being reported is longer than the sink keeps
 //   slot(a, i, c, st, ovf)        lane 0, for every reported burst: the sink's per-slot outputs
@@ -139,13 +146,23 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 //   head(st)                      LiveChan::head for the next push (not flushed)
 //   finish(a, c, st, lane)        after the walk and the carry, before the unused slots are written
 //   clear(a, slot0, i)            unused slot slot0 + i: the sink's own outputs
-template <class Sink>
-__device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk) {
+// PER_CHANNEL: the thresholds are channel c's entries of thr_start / thr_end (int32 [n] in the receiver's state) instead
+// of a.amp_start / a.amp_end.  One wave walks one channel, so they are wave-uniform: two scalar loads before the block
+// loop, the values in SGPRs for the whole walk.  The instantiations without the flag are the code they were.
+template <bool PER_CHANNEL = false, class Sink>
+__device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, const int32_t* thr_start = nullptr,
+                                               const int32_t* thr_end = nullptr) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= a.n) return;
     LiveChan st = a.chan[c];
-    sk.init(a, c);
+    int32_t amp_start = a.amp_start, amp_end = a.amp_end;
+    if constexpr (PER_CHANNEL) {
+        const int cu = __builtin_amdgcn_readfirstlane(c);
+        amp_start = __builtin_amdgcn_readfirstlane(thr_start[cu]);
+        amp_end = __builtin_amdgcn_readfirstlane(thr_end[cu]);
+    }
+    sk.init(a, c, amp_end);
     int16_t* carry = a.carry + (int64_t)c * kListenBlock;
     const int16_t* src = a.chunk + (int64_t)c * a.chunk_stride;
     const int64_t slot0 = (int64_t)c * a.slots;
@@ -179,7 +196,7 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk) {
         if (st.mode == 0) {
             st.mode = 1;                                            // ref:303
         } else if (st.mode == 1) {
-            if (amp > a.amp_start) {                                // ref:306-309
+            if (amp > amp_start) {                                  // ref:306-309
                 st.mode = 2;
                 st.rec_start = bpos0 + (int64_t)b * kListenBlock;
                 st.rec_len = 0;
@@ -187,7 +204,7 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk) {
                 ev = 1;
             }
         } else {
-            ev = amp < a.amp_end ? 2 : 1;                           // ref:316-318 (block included)
+            ev = amp < amp_end ? 2 : 1;                             // ref:316-318 (block included)
         }
         if (ev) {
             sk.record(a, st, cur, lane);
@@ -236,7 +253,7 @@ struct LiveStoreSink {
     // the open burst's stored prefix goes to the row front (it opened in the previous push behind closed bursts,
     // so it is at most one push of blocks, and head >= 2048: copying block by block front to back never overwrites
     // a block that is still to be read)
-    __device__ __forceinline__ void init(const LiveArgs& a, int c) { row = a.rows + (int64_t)c * a.row_len; }
+    __device__ __forceinline__ void init(const LiveArgs& a, int c, int32_t) { row = a.rows + (int64_t)c * a.row_len; }
     __device__ __forceinline__ void begin(const LiveArgs& a, int lane, const LiveChan& st) {
         wp = 0;
         brow = 0;
@@ -281,6 +298,12 @@ __global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
     live_gate_walk(a, sk);
 }
 
+// the stored receiver with a threshold pair per channel (afsk_live_create_thresholds)
+__global__ __launch_bounds__(256) void live_gate_thr_kernel(LiveArgs a, const int32_t* thr_start, const int32_t* thr_end) {
+    LiveStoreSink sk;
+    live_gate_walk<true>(a, sk, thr_start, thr_end);
+}
+
 __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const uint8_t* mask, int32_t n) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < n && (!mask || mask[c])) chan[c] = LiveChan{};
@@ -288,15 +311,84 @@ __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const u
 
 }  // namespace afsk
 
+namespace afsk {
+
+// The stored receiver's squelch classes (afsk_live_create_thresholds).  The demod kernels take ONE amp_end per launch,
+// and a launch decodes the streams its stream_index lists: the channels are grouped by distinct amp_end (a class, in
+// order of first appearance), and a class's list holds its demodulator slots c * slots + k in ascending order -- for
+// a class of four or more rates sorted by rate inside windows of 4096 entries, the order a group plan walks a batch in
+// (neighbouring waves run one rate's code; a different order changes speed, never results).  Every slot is in
+// exactly one list, so the class launches of a push write every output row exactly once.
+struct SquelchClasses {
+    struct Class {
+        int32_t amp_end;
+        int32_t first, count;       // its part of `list`
+        int32_t uniform_bf;         // the one bit_frames of its channels, 0 when they differ
+    };
+    std::vector<Class> classes;
+    std::vector<int32_t> list;      // [n * slots], class after class
+
+    // host only; bit_frames: [n] or null with `uniform_bf` for every channel.  One pass over the channels: a channel
+    // joins the class of its amp_end or opens the next one (the caller has checked how many there are), so classes come
+    // in order of first appearance with their channels ascending.
+    void build(int32_t n, int32_t slots, const int32_t* bit_frames, int32_t uniform_bf, const int32_t* amp_end) {
+        classes.clear();
+        std::vector<std::vector<int32_t>> chans;
+        for (int32_t c = 0; c < n; c++) {
+            size_t k = 0;
+            while (k < classes.size() && classes[k].amp_end != amp_end[c]) k++;
+            if (k == classes.size()) {
+                classes.push_back({amp_end[c], 0, 0, 0});
+                chans.emplace_back();
+            }
+            chans[k].push_back(c);
+        }
+        list.clear();
+        list.reserve((size_t)n * (size_t)slots);
+        for (size_t k = 0; k < classes.size(); k++) {
+            Class& cl = classes[k];
+            cl.first = (int32_t)list.size();
+            std::vector<int32_t> rates;
+            for (int32_t c : chans[k]) {
+                const int32_t bf = bit_frames ? bit_frames[c] : uniform_bf;
+                if (std::find(rates.begin(), rates.end(), bf) == rates.end()) rates.push_back(bf);
+                for (int32_t j = 0; j < slots; j++) list.push_back(c * slots + j);
+            }
+            cl.count = (int32_t)list.size() - cl.first;
+            cl.uniform_bf = rates.size() == 1 ? rates[0] : 0;
+            if (rates.size() >= 4)      // (windows counted from the class's first entry)
+                for (int32_t w0 = cl.first; w0 < cl.first + cl.count; w0 += 4096)
+                    std::stable_sort(list.begin() + w0, list.begin() + std::min(w0 + 4096, cl.first + cl.count),
+                                     [&](int32_t x, int32_t y) { return bit_frames[x / slots] < bit_frames[y / slots]; });
+        }
+    }
+
+    static int32_t count_distinct(const int32_t* amp_end, int32_t n) {
+        std::vector<int32_t> v(amp_end, amp_end + n);
+        std::sort(v.begin(), v.end());
+        return (int32_t)(std::unique(v.begin(), v.end()) - v.begin());
+    }
+};
+
+}  // namespace afsk
+
 struct afsk_live {
-    afsk::DeviceState state;            // the layout's L.bytes
+    afsk::DeviceState state;            // the layout's L.bytes (+ the per-channel part of a thresholds receiver)
     afsk::LiveLayout L;
     int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;   // (a mixed receiver: bit_frames 0)
     afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
     int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip; L: n and slots only)
+    // a threshold pair per channel (afsk_live_create_thresholds / _stream_thresholds): amp_start int32 [n] at o_thr,
+    // amp_end int32 [n] behind it; a stored receiver of two or more squelch classes also the classes' slot lists
+    // (o_list: int32 [n * slots]) and, with mixed rates, every slot's bit_frames (o_slot_bf: int32 [n * slots])
+    bool per_channel = false;
+    int64_t o_thr = 0, o_list = 0, o_slot_bf = 0;
+    std::vector<afsk::SquelchClasses::Class> classes;     // (one class: today's demod launch, no list)
     ~afsk_live() {
         if (plan) (void)afsk_group_plan_destroy(plan);
     }
+    const int32_t* thr_start() const { return reinterpret_cast<const int32_t*>(state.ptr() + o_thr); }
+    const int32_t* thr_end() const { return thr_start() + L.n; }
 };
 
 namespace afsk {
@@ -305,6 +397,24 @@ int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_st
                      int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
                      const DemodOutputs& o, hipStream_t stream);
 int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_t stream);
+
+// What a create entry asks for, after its own argument checks.  bit_frames: [n] when `mixed`, else bit_frames[0] for
+// every channel; amp_start / amp_end: [n] when `per_channel`, else [0] for every channel.  `streaming`: the
+// streaming receiver with max_payload_len (else the stored one with max_burst_len).
+struct LiveSpec {
+    const char* entry;
+    int32_t n_channels;
+    const int32_t* bit_frames;
+    bool mixed;
+    const int32_t* amp_start;
+    const int32_t* amp_end;
+    bool per_channel;
+    bool streaming;
+    int32_t max_burst_len, max_payload_len, max_chunk_len;
+};
+
+// the streaming receiver's layout and state (afsk_live_stream.hip), inside live_create
+int live_stream_state(const LiveSpec& sp, afsk_live& lv);
 }  // namespace afsk
 
 extern "C" {
@@ -320,27 +430,84 @@ int afsk_live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chun
 
 namespace {
 
-// Both create entries, after their own argument checks: bit_frames[c] per channel when `mixed`, else bit_frames[0]
-// for every channel (the uniform receiver).
-int live_create(int32_t n_channels, const int32_t* bit_frames, bool mixed, int32_t amp_start_threshold,
-                int32_t amp_end_threshold, int32_t max_burst_len, int32_t max_chunk_len, afsk_live** out) {
+// the stored receiver's layout and state
+int live_stored_state(const afsk::LiveSpec& sp, afsk_live& lv) {
+    const afsk::LiveLayout& L = lv.L;
+    if (int rc = afsk::live_layout(sp.n_channels, sp.max_burst_len, sp.max_chunk_len, lv.L)) return rc;
+    lv.bit_frames = sp.mixed ? 0 : sp.bit_frames[0];
+    const int64_t n_slots = L.n * L.slots;
+    bool plan = sp.mixed;
+    int64_t bytes = L.bytes;
+    std::vector<int32_t> tail;                  // what follows the layout's bytes, as int32
+    if (sp.per_channel) {
+        afsk::SquelchClasses sc;
+        sc.build(sp.n_channels, (int32_t)L.slots, sp.mixed ? sp.bit_frames : nullptr, sp.bit_frames[0], sp.amp_end);
+        const int64_t thr = afsk::align256(4 * L.n) / 4;
+        const int64_t per_slot = afsk::align256(4 * n_slots) / 4;
+        const bool lists = sc.classes.size() > 1;
+        lv.o_thr = L.bytes;
+        tail.assign((size_t)(2 * thr + (lists ? per_slot : 0) + (lists && sp.mixed ? per_slot : 0)), 0);
+        // (amp_end directly behind amp_start: afsk_live::thr_end)
+        std::copy(sp.amp_start, sp.amp_start + L.n, tail.begin());
+        std::copy(sp.amp_end, sp.amp_end + L.n, tail.begin() + L.n);
+        if (lists) {
+            lv.o_list = lv.o_thr + 8 * thr;
+            std::copy(sc.list.begin(), sc.list.end(), tail.begin() + 2 * thr);
+            if (sp.mixed) {
+                lv.o_slot_bf = lv.o_list + 4 * per_slot;
+                for (int64_t s = 0; s < n_slots; s++) tail[(size_t)(2 * thr + per_slot + s)] = sp.bit_frames[s / L.slots];
+            }
+            lv.classes = sc.classes;
+            plan = false;                       // the class launches walk their own lists
+        } else {
+            lv.amp_end = sc.classes[0].amp_end;
+        }
+        bytes += 4 * (int64_t)tail.size();
+    }
+    // only the channel states need a value: the carry, slots and rows are written before they are read
+    if (int rc = lv.state.create(sp.entry, bytes, L.o_carry, tail.empty() ? nullptr : tail.data(), lv.o_thr,
+                                 4 * (int64_t)tail.size()))
+        return rc;
+    if (plan) {
+        std::vector<int32_t> slot_bf((size_t)n_slots);
+        for (size_t s = 0; s < slot_bf.size(); s++) slot_bf[s] = sp.bit_frames[(int64_t)s / L.slots];
+        if (int rc = afsk_group_plan_create(slot_bf.data(), (int32_t)slot_bf.size(), &lv.plan)) return rc;
+    }
+    return AFSK_OK;
+}
+
+// Every create entry, after its own argument checks: the one owner of a receiver's host fields and device state.
+int live_create(const afsk::LiveSpec& sp, afsk_live** out) {
     return afsk::no_throw([&] {
         std::unique_ptr<afsk_live> lv(new afsk_live());
-        const afsk::LiveLayout& L = lv->L;
-        if (int rc = afsk::live_layout(n_channels, max_burst_len, max_chunk_len, lv->L)) return rc;
-        std::vector<int32_t> slot_bf(mixed ? (size_t)(L.n * L.slots) : 0);
-        for (size_t s = 0; s < slot_bf.size(); s++) slot_bf[s] = bit_frames[(int64_t)s / L.slots];
-        lv->bit_frames = mixed ? 0 : bit_frames[0];
-        lv->amp_start = amp_start_threshold;
-        lv->amp_end = amp_end_threshold;
-        lv->max_chunk_len = max_chunk_len;
-        // only the channel states need a value: the carry, slots and rows are written before they are read
-        if (int rc = lv->state.create("afsk_live_create", L.bytes, L.o_carry)) return rc;
-        if (mixed)
-            if (int rc = afsk_group_plan_create(slot_bf.data(), (int32_t)slot_bf.size(), &lv->plan)) return rc;
+        lv->amp_start = sp.amp_start[0];
+        lv->amp_end = sp.amp_end[0];
+        lv->per_channel = sp.per_channel;
+        lv->max_chunk_len = sp.max_chunk_len;
+        if (int rc = sp.streaming ? afsk::live_stream_state(sp, *lv) : live_stored_state(sp, *lv)) return rc;
         *out = lv.release();
         return AFSK_OK;
     });
+}
+
+// The checks the array entries share; `same`: every channel at one rate.
+int live_check_rates(int32_t n_channels, const int32_t* bit_frames_host, afsk_live** out, bool& same) {
+    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    *out = nullptr;
+    if (n_channels < 1) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
+    if (!bit_frames_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    same = true;
+    for (int32_t c = 0; c < n_channels; c++) {
+        if (!afsk::bf_valid(bit_frames_host[c])) return afsk::fail_bit_frames();
+        same = same && bit_frames_host[c] == bit_frames_host[0];
+    }
+    return AFSK_OK;
+}
+
+bool all_equal(const int32_t* v, int32_t n) {
+    for (int32_t c = 1; c < n; c++)
+        if (v[c] != v[0]) return false;
+    return true;
 }
 
 }  // namespace
@@ -350,24 +517,59 @@ int afsk_live_create(int32_t n_channels, int32_t bit_frames, int32_t amp_start_t
     if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
     *out = nullptr;
     if (!afsk::bf_valid(bit_frames)) return afsk::fail_bit_frames();
-    return live_create(n_channels, &bit_frames, false, amp_start_threshold, amp_end_threshold, max_burst_len,
-                       max_chunk_len, out);
+    return live_create({"afsk_live_create", n_channels, &bit_frames, false, &amp_start_threshold, &amp_end_threshold,
+                        false, false, max_burst_len, -1, max_chunk_len}, out);
 }
 
 int afsk_live_create_mixed(int32_t n_channels, const int32_t* bit_frames_host, int32_t amp_start_threshold,
                            int32_t amp_end_threshold, int32_t max_burst_len, int32_t max_chunk_len, afsk_live** out) {
-    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    *out = nullptr;
-    if (n_channels < 1) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
-    if (!bit_frames_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    bool same = true;
-    for (int32_t c = 0; c < n_channels; c++) {
-        if (!afsk::bf_valid(bit_frames_host[c])) return afsk::fail_bit_frames();
-        same = same && bit_frames_host[c] == bit_frames_host[0];
-    }
+    bool same;
+    if (int rc = live_check_rates(n_channels, bit_frames_host, out, same)) return rc;
     // one rate for every channel: the uniform receiver (its launches, its state bytes)
-    return live_create(n_channels, bit_frames_host, !same, amp_start_threshold, amp_end_threshold, max_burst_len,
-                       max_chunk_len, out);
+    return live_create({"afsk_live_create", n_channels, bit_frames_host, !same, &amp_start_threshold,
+                        &amp_end_threshold, false, false, max_burst_len, -1, max_chunk_len}, out);
+}
+
+int afsk_live_create_thresholds(int32_t n_channels, const int32_t* bit_frames_host, const int32_t* amp_start_host,
+                                const int32_t* amp_end_host, int32_t max_burst_len, int32_t max_chunk_len,
+                                afsk_live** out) {
+    bool same;
+    if (int rc = live_check_rates(n_channels, bit_frames_host, out, same)) return rc;
+    if (!amp_start_host || !amp_end_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    return afsk::no_throw([&] {
+        if (afsk::SquelchClasses::count_distinct(amp_end_host, n_channels) > AFSK_LIVE_MAX_SQUELCH_CLASSES)
+            return afsk::fail(AFSK_E_INVALID_ARG,
+                              "more than AFSK_LIVE_MAX_SQUELCH_CLASSES (16) distinct amp_end thresholds on a stored live "
+                              "receiver (one demod launch each): the streaming receiver, "
+                              "afsk_live_create_stream_thresholds, has no such limit");
+        // one pair for every channel: the receiver afsk_live_create_mixed builds
+        const bool per_channel = !all_equal(amp_start_host, n_channels) || !all_equal(amp_end_host, n_channels);
+        return live_create({"afsk_live_create_thresholds", n_channels, bit_frames_host, !same, amp_start_host,
+                            amp_end_host, per_channel, false, max_burst_len, -1, max_chunk_len}, out);
+    });
+}
+
+int afsk_live_squelch_classes(int32_t n_channels, int32_t slots, const int32_t* bit_frames_host,
+                              const int32_t* amp_end_host, int32_t* out_n_classes, int32_t* out_class_amp_end,
+                              int32_t* out_class_count, int32_t* out_class_uniform_bf, int32_t* out_slot_list) {
+    if (n_channels < 1 || slots < 1 || (int64_t)n_channels * slots > 0x7fffffffll)
+        return afsk::fail(AFSK_E_INVALID_ARG, "n_channels and slots must be at least 1, their product an int32");
+    if (!bit_frames_host || !amp_end_host || !out_n_classes) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    return afsk::no_throw([&] {
+        const int32_t nd = afsk::SquelchClasses::count_distinct(amp_end_host, n_channels);
+        *out_n_classes = nd;
+        if (nd > AFSK_LIVE_MAX_SQUELCH_CLASSES)
+            return afsk::fail(AFSK_E_INVALID_ARG, "more than AFSK_LIVE_MAX_SQUELCH_CLASSES (16) distinct amp_end thresholds");
+        afsk::SquelchClasses sc;
+        sc.build(n_channels, slots, bit_frames_host, 0, amp_end_host);
+        for (size_t k = 0; k < sc.classes.size(); k++) {
+            if (out_class_amp_end) out_class_amp_end[k] = sc.classes[k].amp_end;
+            if (out_class_count) out_class_count[k] = sc.classes[k].count;
+            if (out_class_uniform_bf) out_class_uniform_bf[k] = sc.classes[k].uniform_bf;
+        }
+        if (out_slot_list) std::copy(sc.list.begin(), sc.list.end(), out_slot_list);
+        return AFSK_OK;
+    });
 }
 
 int afsk_live_info(const afsk_live* live, int32_t* out_n_channels, int32_t* out_slots, int64_t* out_state_bytes) {
@@ -420,9 +622,28 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
     g.out_burst_len = out_burst_len;
     g.out_flags = out_flags;
     const hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(afsk::live_gate_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g);
+    if (live->per_channel)
+        hipLaunchKernelGGL(afsk::live_gate_thr_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g,
+                           live->thr_start(), live->thr_end());
+    else
+        hipLaunchKernelGGL(afsk::live_gate_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return afsk::hip_fail(e, "launch live_gate_kernel");
+    if (e != hipSuccess)
+        return afsk::hip_fail(e, live->per_channel ? "launch live_gate_thr_kernel" : "launch live_gate_kernel");
+    // two or more squelch classes: the demod kernels once per class, each over its own list of slots
+    for (const afsk::SquelchClasses::Class& k : live->classes) {
+        afsk::DemodArgs a = o.args<afsk::DemodArgs>(g.rows, g.slot_off, g.slot_len, k.amp_end, k.count);
+        a.stream_index = reinterpret_cast<const int32_t*>(d + live->o_list) + k.first;
+        if (k.uniform_bf) {
+            a.uniform_bit_frames = k.uniform_bf;
+            e = afsk::launch_demod_uniform(a, st);
+        } else {
+            a.bit_frames = reinterpret_cast<const int32_t*>(d + live->o_slot_bf);
+            e = afsk::launch_demod(a, st);
+        }
+        if (e != hipSuccess) return afsk::hip_fail(e, "launch the demod kernel (live slots of one squelch class)");
+    }
+    if (!live->classes.empty()) return AFSK_OK;
     if (live->plan)
         return afsk_demod_batch_grouped(live->plan, g.rows, g.slot_off, g.slot_len, live->amp_end, o.bytes, o.stride,
                                         o.nbytes, o.nbits, o.clock_idx, o.term_frame, o.status, o.corrected,

@@ -23,6 +23,10 @@
 // 4096-sample window image and a payload row of max_payload_len bytes.  A reported burst's outputs come from
 // StreamDemod and the payload row (bytes [0, min(nbytes, max_payload_len, out_stride)) are copied into its row).
 //
+// A receiver with a threshold pair per channel (afsk_live_create_stream_thresholds) keeps amp_start and amp_end as
+// int32 [n] behind bit_frames; live_stream_thr_kernel (the same walk and sink) gates with the channel's pair and sets
+// the sink's per-symbol squelch from the channel's amp_end -- any number of distinct pairs, still one launch.
+//
 // This file is compiled as part of afsk_gate.hip's translation unit (see the #include at its end), after afsk_split.hip
 // (the demod helpers) and afsk_live.hip (the gate walk, LiveChan, LiveArgs).
 
@@ -51,8 +55,10 @@ struct LiveStreamLayout {
 };
 
 // LiveChan [n] | carry int16 [n, 2048] | StreamDemod [n] | bit_frames int32 [n] | window int16 [n, 4096] | payload
-// uint8 [n, max_payload_len] | 256 spare bytes; every part 256-byte aligned
-inline int live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32_t max_chunk_len, LiveStreamLayout& L) {
+// uint8 [n, max_payload_len] | 256 spare bytes; every part 256-byte aligned.  `per_channel` (a threshold pair per
+// channel, afsk_live_create_stream_thresholds): the bit_frames part holds int32 [3, n] -- bit_frames, amp_start, amp_end.
+inline int live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32_t max_chunk_len, LiveStreamLayout& L,
+                              bool per_channel = false) {
     if (n_channels < 1) return fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
     if (max_payload_len < 0 || max_payload_len > 65536)
         return fail(AFSK_E_INVALID_ARG, "max_payload_len must lie in 0 ... 65536");
@@ -67,7 +73,7 @@ inline int live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32
     L.o_carry = align256(32 * L.n);
     L.o_demod = L.o_carry + align256(2 * kListenBlock * L.n);
     L.o_bf = L.o_demod + align256(32 * L.n);
-    L.o_win = L.o_bf + align256(4 * L.n);
+    L.o_win = L.o_bf + align256((per_channel ? 12 : 4) * L.n);
     L.o_pay = L.o_win + align256(2 * kStreamWin * L.n);
     L.bytes = L.o_pay + align256(L.max_payload * L.n) + 256;
     return AFSK_OK;
@@ -133,13 +139,14 @@ struct LiveStreamSink {
     int16_t* gwin;              // the channel's window image
     uint8_t* pay;               // the channel's payload row
 
-    __device__ __forceinline__ void init(const LiveArgs&, int c) {
+    // amp_end: the channel's squelch threshold (the per-symbol squelch of ref:375)
+    __device__ __forceinline__ void init(const LiveArgs&, int c, int32_t amp_end) {
         ds = A.dm[c];
         bf = A.bit_frames[c];
         int l = 0;
         while ((2 << l) * 32 <= bf) l++;                         // lps = largest power of two <= bf / 32
         lsh = l;
-        amp_thr = split_amp_thr(A.g.amp_end, bf);
+        amp_thr = split_amp_thr(amp_end, bf);
         gwin = A.win + (int64_t)c * kStreamWin;
         pay = A.pay + (int64_t)c * A.max_payload;
     }
@@ -317,6 +324,14 @@ __global__ __launch_bounds__(256) void live_stream_kernel(LiveStreamArgs a) {
     live_gate_walk(a.g, sk);
 }
 
+// the streaming receiver with a threshold pair per channel (afsk_live_create_stream_thresholds)
+__global__ __launch_bounds__(256) void live_stream_thr_kernel(LiveStreamArgs a, const int32_t* thr_start,
+                                                              const int32_t* thr_end) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kStreamWinLds];
+    LiveStreamSink sk{a, reinterpret_cast<int16_t*>(lds + (threadIdx.x >> 6) * kStreamWinLds)};
+    live_gate_walk<true>(a.g, sk, thr_start, thr_end);
+}
+
 __global__ __launch_bounds__(256) void live_stream_reset_kernel(LiveChan* chan, StreamDemod* dm, const uint8_t* mask,
                                                                 int32_t n) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -334,7 +349,8 @@ int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_st
                      int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
                      const DemodOutputs& o, hipStream_t stream) {
     LiveStreamLayout L;
-    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L)) return rc;
+    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L, live->per_channel))
+        return rc;
     uint8_t* d = live->state.ptr();
     LiveStreamArgs a{};
     a.g.chan = reinterpret_cast<LiveChan*>(d);
@@ -364,20 +380,45 @@ int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_st
     a.out_term_frame = o.term_frame;
     a.out_status = o.status;
     a.out_corrected = o.corrected;
-    hipLaunchKernelGGL(live_stream_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, stream, a);
+    if (live->per_channel)
+        hipLaunchKernelGGL(live_stream_thr_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, stream, a,
+                           live->thr_start(), live->thr_end());
+    else
+        hipLaunchKernelGGL(live_stream_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch live_stream_kernel");
+    return e == hipSuccess ? AFSK_OK
+                           : hip_fail(e, live->per_channel ? "launch live_stream_thr_kernel" : "launch live_stream_kernel");
 }
 
 int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_t stream) {
     LiveStreamLayout L;
-    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L)) return rc;
+    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L, live->per_channel))
+        return rc;
     uint8_t* d = live->state.ptr();
     hipLaunchKernelGGL(live_stream_reset_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<LiveChan*>(d), reinterpret_cast<StreamDemod*>(d + L.o_demod), d_mask_or_null,
                        (int32_t)L.n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch live_stream_reset_kernel");
+}
+
+// the streaming receiver's part of live_create (afsk_live.hip): the layout, the host fields that depend on it, the state
+int live_stream_state(const LiveSpec& sp, afsk_live& lv) {
+    LiveStreamLayout L;
+    if (int rc = live_stream_layout(sp.n_channels, sp.max_payload_len, sp.max_chunk_len, L, sp.per_channel)) return rc;
+    lv.L.n = L.n;
+    lv.L.slots = L.slots;
+    lv.bit_frames = 0;
+    lv.max_payload_len = sp.max_payload_len;
+    // the channel states, carries (never read before written) and demodulators zeroed, the rates (and the channels'
+    // thresholds behind them) uploaded
+    std::vector<int32_t> up(sp.bit_frames, sp.bit_frames + L.n);
+    if (sp.per_channel) {
+        lv.o_thr = L.o_bf + 4 * L.n;
+        up.insert(up.end(), sp.amp_start, sp.amp_start + L.n);
+        up.insert(up.end(), sp.amp_end, sp.amp_end + L.n);
+    }
+    return lv.state.create(sp.entry, L.bytes, L.o_bf, up.data(), L.o_bf, 4 * (int64_t)up.size());
 }
 
 }  // namespace afsk
@@ -395,29 +436,22 @@ int afsk_live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32_t
 
 int afsk_live_create_stream(int32_t n_channels, const int32_t* bit_frames_host, int32_t amp_start_threshold,
                             int32_t amp_end_threshold, int32_t max_payload_len, int32_t max_chunk_len, afsk_live** out) {
-    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    *out = nullptr;
-    if (n_channels < 1) return afsk::fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
-    if (!bit_frames_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    for (int32_t c = 0; c < n_channels; c++)
-        if (!afsk::bf_valid(bit_frames_host[c])) return afsk::fail_bit_frames();
-    return afsk::no_throw([&] {
-        afsk::LiveStreamLayout L;
-        if (int rc = afsk::live_stream_layout(n_channels, max_payload_len, max_chunk_len, L)) return rc;
-        std::unique_ptr<afsk_live> lv(new afsk_live());
-        lv->L.n = L.n;
-        lv->L.slots = L.slots;
-        lv->bit_frames = 0;
-        lv->amp_start = amp_start_threshold;
-        lv->amp_end = amp_end_threshold;
-        lv->max_chunk_len = max_chunk_len;
-        lv->max_payload_len = max_payload_len;
-        // the channel states, carries (never read before written) and demodulators zeroed, the rates uploaded
-        if (int rc = lv->state.create("afsk_live_create_stream", L.bytes, L.o_bf, bit_frames_host, L.o_bf, 4 * L.n))
-            return rc;
-        *out = lv.release();
-        return AFSK_OK;
-    });
+    bool same;
+    if (int rc = live_check_rates(n_channels, bit_frames_host, out, same)) return rc;
+    return live_create({"afsk_live_create_stream", n_channels, bit_frames_host, true, &amp_start_threshold,
+                        &amp_end_threshold, false, true, 0, max_payload_len, max_chunk_len}, out);
+}
+
+int afsk_live_create_stream_thresholds(int32_t n_channels, const int32_t* bit_frames_host, const int32_t* amp_start_host,
+                                       const int32_t* amp_end_host, int32_t max_payload_len, int32_t max_chunk_len,
+                                       afsk_live** out) {
+    bool same;
+    if (int rc = live_check_rates(n_channels, bit_frames_host, out, same)) return rc;
+    if (!amp_start_host || !amp_end_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    // one pair for every channel: the receiver afsk_live_create_stream builds
+    const bool per_channel = !all_equal(amp_start_host, n_channels) || !all_equal(amp_end_host, n_channels);
+    return live_create({"afsk_live_create_stream_thresholds", n_channels, bit_frames_host, true, amp_start_host,
+                        amp_end_host, per_channel, true, 0, max_payload_len, max_chunk_len}, out);
 }
 
 }  // extern "C"

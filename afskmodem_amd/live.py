@@ -44,6 +44,37 @@ def _per_channel(value, n_channels: int, name: str):
     return v
 
 
+def _channel_thresholds(value, n_channels: int, name: str, rule) -> np.ndarray:
+    """``value`` (one threshold or a sequence of n_channels) as int32 [n_channels], every entry through ``rule``
+    (``batch.threshold_gt`` / ``threshold_lt``: float, inf and nan entries behave as the scalar does)."""
+    v = _per_channel(value, n_channels, name)
+    if v is None:
+        v = [value] * max(n_channels, 0)
+    return np.asarray([rule(x) for x in v], np.int32).reshape(-1)
+
+
+def squelch_classes(bit_frames, amp_end, slots: int):
+    """The squelch classes a stored receiver of these channels builds (``afsk_live_squelch_classes``: host-only):
+    a list of ``(amp_end, uniform bit_frames or 0, slot list)`` per distinct ``amp_end`` in order of first appearance;
+    a slot list holds the demodulator slots ``c * slots + k`` one demod launch decodes with that threshold."""
+    bf = np.ascontiguousarray(bit_frames, np.int32)
+    end = np.ascontiguousarray(amp_end, np.int32)
+    if bf.ndim != 1 or bf.shape != end.shape:
+        raise ValueError("bit_frames and amp_end must be sequences of one length")
+    n, cap = int(bf.size), _native.LIVE_MAX_SQUELCH_CLASSES
+    k = C.c_int32()
+    c_end, c_count, c_bf = (np.zeros(cap, np.int32) for _ in range(3))
+    lst = np.zeros(max(n * int(slots), 1), np.int32)
+    _native.check(_native.lib().afsk_live_squelch_classes(n, int(slots), _i32_ptr(bf), _i32_ptr(end), C.byref(k),
+                                                          _i32_ptr(c_end), _i32_ptr(c_count), _i32_ptr(c_bf),
+                                                          _i32_ptr(lst)))
+    out, at = [], 0
+    for i in range(int(k.value)):
+        out.append((int(c_end[i]), int(c_bf[i]), lst[at:at + int(c_count[i])].copy()))
+        at += int(c_count[i])
+    return out
+
+
 def _i32_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
@@ -139,8 +170,12 @@ class LiveResult:
 class LiveReceiver(batch._NativePlan):
     """A live receiver of ``n_channels`` independent channels at one baud rate (``bit_frames`` = 48000 / baud) or one
     per channel (``bit_frames`` a sequence of n_channels, in any order), with the thresholds of ``Receiver``
-    (``threshold_gt`` / ``threshold_lt`` rules, as ``gate_batch``) shared by all channels.  Channel c then reports
-    what a one-rate receiver at its rate reports for it.  ``bit_frames`` stays the int of a one-rate receiver (also
+    (``threshold_gt`` / ``threshold_lt`` rules, as ``gate_batch``): one pair for all channels, or each a sequence of
+    n_channels.  Channel c then reports what a one-rate receiver at its rate and with its pair reports for it.
+    ``amp_start_threshold`` / ``amp_end_threshold`` read as the int when all channels agree, else None;
+    ``channel_amp_start`` / ``channel_amp_end`` (int32 [n_channels]) hold every channel's.  A stored receiver
+    decodes with one demod launch per distinct ``amp_end`` (at most ``LIVE_MAX_SQUELCH_CLASSES`` = 16 of them); the
+    streaming receiver takes any number in its one launch.  ``bit_frames`` stays the int of a one-rate receiver (also
     when every entry of a sequence is equal: that is the one-rate receiver) and is None for a mixed one;
     ``channel_bit_frames`` (int32 [n_channels]) holds every channel's.
 
@@ -173,6 +208,12 @@ class LiveReceiver(batch._NativePlan):
         batch.validate_bit_frames(np.asarray(rates, np.int64))
         self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
         self.bit_frames = None if len(set(rates)) > 1 else int(rates[0]) if rates else None
+        self.channel_amp_start = _channel_thresholds(amp_start_threshold, self.n_channels, "amp_start_threshold",
+                                                     batch.threshold_gt)
+        self.channel_amp_end = _channel_thresholds(amp_end_threshold, self.n_channels, "amp_end_threshold",
+                                                   batch.threshold_lt)
+        one = lambda a: int(a[0]) if a.size and bool(np.all(a == a[0])) else None  # noqa: E731
+        self.amp_start_threshold, self.amp_end_threshold = one(self.channel_amp_start), one(self.channel_amp_end)
         self.streaming = max_burst_len is None
         self.max_burst_len = None if self.streaming else int(max_burst_len)
         self.max_payload_len = int(max_payload_len) if self.streaming else None
@@ -190,28 +231,34 @@ class LiveReceiver(batch._NativePlan):
             # the demodulator rows: one byte per 14 symbols of the longest stored burst never truncates
             self.out_stride = batch.out_stride_for(self.max_burst_len // 2048 * 2048, self._min_bf)
         nbytes = C.c_int64()
-        start, end = batch.threshold_gt(amp_start_threshold), batch.threshold_lt(amp_end_threshold)
         with torch.cuda.device(self.device):
+            # (one rate / one threshold pair in every entry: the C entries build the one-rate / one-pair receiver)
             if self.streaming:
-                _native.check(_native.lib().afsk_live_create_stream(
-                    self.n_channels, _i32_ptr(self.channel_bit_frames), start, end, self.max_payload_len,
-                    self.max_chunk_len, C.byref(self._h)))
+                _native.check(_native.lib().afsk_live_create_stream_thresholds(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_amp_start),
+                    _i32_ptr(self.channel_amp_end), self.max_payload_len, self.max_chunk_len, C.byref(self._h)))
             else:
-                # (one rate in every entry: the C entry builds the one-rate receiver)
-                _native.check(_native.lib().afsk_live_create_mixed(
-                    self.n_channels, _i32_ptr(self.channel_bit_frames), start, end, self.max_burst_len,
-                    self.max_chunk_len, C.byref(self._h)))
+                _native.check(_native.lib().afsk_live_create_thresholds(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_amp_start),
+                    _i32_ptr(self.channel_amp_end), self.max_burst_len, self.max_chunk_len, C.byref(self._h)))
             _native.check(_native.lib().afsk_live_info(self.handle, None, None, C.byref(nbytes)))
         self.state_bytes = int(nbytes.value)
 
     @classmethod
-    def from_receivers(cls, receivers, **capacities) -> "LiveReceiver":
-        """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  Their thresholds must agree
-        (ValueError otherwise): the gate's thresholds are the receiver's.  ``capacities``: ``max_burst_len`` /
-        ``max_chunk_len`` (samples), ``max_payload_len`` (bytes, with ``max_burst_len=None``) and ``device``."""
+    def from_receivers(cls, receivers, thresholds: str = "shared", **capacities) -> "LiveReceiver":
+        """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  ``thresholds="shared"``: their
+        thresholds must agree (ValueError otherwise) and are the receiver's one pair; ``"per_channel"``: channel c
+        gets ``receivers[c]``'s pair.  ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples),
+        ``max_payload_len`` (bytes, with ``max_burst_len=None``) and ``device``."""
         receivers = list(receivers)
         if not receivers:
             raise ValueError("from_receivers needs at least one Receiver")
+        if thresholds not in ("shared", "per_channel"):
+            raise ValueError(f"thresholds must be 'shared' or 'per_channel', got {thresholds!r}")
+        if thresholds == "per_channel":
+            return cls(len(receivers), [r.bit_frames for r in receivers],
+                       [r.amp_start_threshold for r in receivers], [r.amp_end_threshold for r in receivers],
+                       **capacities)
         th = {(r.amp_start_threshold, r.amp_end_threshold) for r in receivers}
         if len(th) != 1:
             raise ValueError(f"the receivers' thresholds differ: {sorted(th)}")

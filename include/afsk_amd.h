@@ -553,6 +553,55 @@ extern int afsk_live_create_stream(int32_t n_channels, const int32_t *bit_frames
                                    afsk_live **out);
 
 /*
+ * Live receivers with a gate and squelch threshold pair per channel (added after ABI version 2; the version is
+ * unchanged).  Channel c gates with amp_start_host[c] / amp_end_host[c] and is demodulated with amp_end_host[c] at
+ * bit_frames_host[c]: it reports, field for field, what a receiver of the same kind created with that one pair (and
+ * rate) reports for its samples.  The objects are afsk_live: push, reset (which leaves the thresholds in place), info
+ * and destroy serve them unchanged.
+ *
+ *  afsk_live_create_thresholds         the stored receiver (afsk_live_create_mixed's capacities and rates).
+ *  afsk_live_create_stream_thresholds  the streaming receiver (afsk_live_create_stream's capacities and rates).
+ *                           bit_frames_host, amp_start_host, amp_end_host: HOST int32 arrays [n_channels]; a NULL array,
+ *                           NULL out or n_channels < 1: AFSK_E_INVALID_ARG, a bad rate AFSK_E_INVALID_BAUD, all
+ *                           returned before any device is needed.  Every channel with the same pair: exactly the
+ *                           receiver afsk_live_create_mixed / afsk_live_create_stream builds (its launches, its state
+ *                           bytes).  Otherwise the state also holds amp_start and amp_end as int32 [n_channels] each
+ *                           (afsk_live_info reports the larger state), and the gate reads a channel's pair once per push.
+ * The streaming receiver's demodulator takes a channel's amp_end from the same array: any number of distinct values,
+ * still one launch per push.  The stored receiver decodes with the batch demodulator, whose launches take one amp_end:
+ * the channels are grouped by distinct amp_end into squelch classes, each with the list of its demodulator slots
+ * c * slots + k on the device (int32 [n_channels * slots] in all; with mixed rates also every slot's bit_frames, another
+ * int32 [n_channels * slots]), and a push is the gate launch plus ONE demod launch per class over that class's slots
+ * -- every slot is in exactly one class, every output row is written once per push, nothing runs on the host in
+ * between, so the push stays capturable.  amp_start may take any number of distinct values; distinct amp_end values
+ * on a stored receiver are limited to AFSK_LIVE_MAX_SQUELCH_CLASSES (a push is at most 17 launches): more is
+ * AFSK_E_INVALID_ARG (use the streaming receiver, which has no limit).  One class needs no list: the demod launch is
+ * afsk_live_create_mixed's.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_THRESHOLD_SIGNATURES.)
+ */
+#define AFSK_LIVE_MAX_SQUELCH_CLASSES 16
+
+extern int afsk_live_create_thresholds(int32_t n_channels, const int32_t *bit_frames_host, const int32_t *amp_start_host,
+                                       const int32_t *amp_end_host, int32_t max_burst_len, int32_t max_chunk_len,
+                                       afsk_live **out);
+extern int afsk_live_create_stream_thresholds(int32_t n_channels, const int32_t *bit_frames_host,
+                                              const int32_t *amp_start_host, const int32_t *amp_end_host,
+                                              int32_t max_payload_len, int32_t max_chunk_len, afsk_live **out);
+
+/*
+ * Host-only (no device needed): the squelch classes afsk_live_create_thresholds would build for these channels and
+ * `slots` slots per channel, for inspection and tests.  Classes in order of their first channel; out_slot_list
+ * (int32 [n_channels * slots], optional) holds the classes' slot lists back to back, out_class_count their lengths,
+ * out_class_uniform_bf the one bit_frames of a class's channels or 0 when they differ (arrays of
+ * AFSK_LIVE_MAX_SQUELCH_CLASSES entries, optional).  *out_n_classes is the number of distinct amp_end values; above
+ * the limit the call returns AFSK_E_INVALID_ARG with nothing else written.
+ * (Declared `extern int`: bound from a table of its own, LIVE_CLASS_SIGNATURES.)
+ */
+extern int afsk_live_squelch_classes(int32_t n_channels, int32_t slots, const int32_t *bit_frames_host,
+                                     const int32_t *amp_end_host, int32_t *out_n_classes, int32_t *out_class_amp_end,
+                                     int32_t *out_class_count, int32_t *out_class_uniform_bf, int32_t *out_slot_list);
+
+/*
  * The live transmitter (an addition: ABI version unchanged): Transmitter.transmit (:472-478) for n_channels
  * independent channels at one bit_frames and training length.  Every channel has a device-resident queue of up to
  * queue_depth messages; each pull writes the next n_samples samples of every channel's stream, the queued messages
