@@ -168,6 +168,20 @@ LIVE_CLASS_SIGNATURES = {
     "afsk_live_squelch_classes": (C.c_int, [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
 }
 
+# The streaming receiver's payload tap (afsk_live_tap_layout, afsk_live_create_stream_tap, afsk_live_push_tap),
+# likewise.
+LIVE_TAP_SIGNATURES = {
+    "afsk_live_tap_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32p]),
+    "afsk_live_create_stream_tap": (C.c_int, [C.c_int32, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_void_p)]),
+    # afsk_live_push's arguments, the five tap outputs in front of the stream
+    "afsk_live_push_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -181,7 +195,7 @@ def lib() -> C.CDLL:
         for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
                                   *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items(),
                                   *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
-                                  *LIVE_CLASS_SIGNATURES.items()):
+                                  *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -143,3 +143,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // The streaming live receiver (afsk_live_stream_layout / afsk_live_create_stream: the same gate walk, bursts
 // demodulated while they are gated), for the same reason.
 #include "afsk_live_stream.hip"
+// The streaming receiver's payload tap (afsk_live_tap_layout / afsk_live_create_stream_tap / afsk_live_push_tap: the
+// tapped instantiations of the streaming kernels), for the same reason.
+#include "afsk_live_tap.hip"

@@ -378,6 +378,7 @@ struct afsk_live {
     int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;   // (a mixed receiver: bit_frames 0)
     afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
     int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip; L: n and slots only)
+    int32_t tap_cap = 0;                // > 0: a tapped streaming receiver (afsk_live_tap.hip): bytes per tap row
     // a threshold pair per channel (afsk_live_create_thresholds / _stream_thresholds): amp_start int32 [n] at o_thr,
     // amp_end int32 [n] behind it; a stored receiver of two or more squelch classes also the classes' slot lists
     // (o_list: int32 [n * slots]) and, with mixed rates, every slot's bit_frames (o_slot_bf: int32 [n * slots])

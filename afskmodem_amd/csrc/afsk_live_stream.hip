@@ -27,6 +27,10 @@
 // int32 [n] behind bit_frames; live_stream_thr_kernel (the same walk and sink) gates with the channel's pair and sets
 // the sink's per-symbol squelch from the channel's amp_end -- any number of distinct pairs, still one launch.
 //
+// A tapped receiver (afsk_live_tap.hip: afsk_live_create_stream_tap, afsk_live_push_tap) is this receiver with the same
+// state; its push runs the sink's tapped instantiation (LiveStreamSinkT<true>), which also hands out every payload
+// byte in the push that commits it.  The kernels of this file are the untapped instantiation.
+//
 // This file is compiled as part of afsk_gate.hip's translation unit (see the #include at its end), after afsk_split.hip
 // (the demod helpers) and afsk_live.hip (the gate walk, LiveChan, LiveArgs).
 
@@ -130,7 +134,27 @@ __device__ __forceinline__ void stream_symbols(const int16_t* win, int lane, int
     loud = __ballot(lane < n && (r & 2));
 }
 
-struct LiveStreamSink {
+// The payload tap (afsk_live_tap.hip: afsk_live_push_tap).  The tapped instantiation of the sink appends every byte it
+// commits to the channel's tap row and counts them per reported burst; the untapped one holds and does none of it.
+struct LiveTapArgs {
+    uint8_t* bytes;             // uint8 [n, cap]: the bytes committed during this push, in time order
+    int32_t cap;
+    int32_t* n;                 // int32 [n]: how many
+    int32_t* len;               // int32 [n, slots]: how many of them belong to the burst of slot (c, k)
+    int64_t* open_start;        // int64 [n]: rec_start of the burst still recording, or -1
+    int32_t* open_nbytes;       // int32 [n]: its payload bytes committed so far
+};
+template <bool TAP>
+struct LiveTapState {};
+template <>
+struct LiveTapState<true> {
+    LiveTapArgs T;
+    uint8_t* row;               // the channel's tap row
+    int32_t n, mark;            // bytes committed in this push; n at the last report
+};
+
+template <bool TAP>
+struct LiveStreamSinkT {
     const LiveStreamArgs& A;
     int16_t* lwin;              // the wave's LDS window
     StreamDemod ds;
@@ -138,6 +162,7 @@ struct LiveStreamSink {
     uint32_t amp_thr;
     int16_t* gwin;              // the channel's window image
     uint8_t* pay;               // the channel's payload row
+    LiveTapState<TAP> tp;
 
     // amp_end: the channel's squelch threshold (the per-symbol squelch of ref:375)
     __device__ __forceinline__ void init(const LiveArgs&, int c, int32_t amp_end) {
@@ -149,6 +174,11 @@ struct LiveStreamSink {
         amp_thr = split_amp_thr(amp_end, bf);
         gwin = A.win + (int64_t)c * kStreamWin;
         pay = A.pay + (int64_t)c * A.max_payload;
+        if constexpr (TAP) {
+            tp.row = tp.T.bytes + (int64_t)c * tp.T.cap;
+            tp.n = 0;
+            tp.mark = 0;
+        }
     }
     // samples [from, to) of the open burst (positions in the burst) between the window image and the LDS window
     __device__ __forceinline__ void copy_tail(bool out, int64_t from, int64_t to, int lane) {
@@ -203,6 +233,11 @@ struct LiveStreamSink {
             uint8_t* row = A.out_bytes + i * A.out_stride;
             for (int b = lane; b < nb; b += 64) row[b] = pay[b];
         }
+        if constexpr (TAP) {
+            if (ovf) tp.n = tp.mark;                              // not decoded: this push's bytes of it are withdrawn
+            if (lane == 0) tp.T.len[i] = tp.n - tp.mark;
+            tp.mark = tp.n;
+        }
     }
     __device__ __forceinline__ void start(const LiveChan&) { ds = StreamDemod{}; }
 
@@ -250,6 +285,10 @@ struct LiveStreamSink {
             if (cw_index & 1) {
                 const int32_t b = cw_index >> 1;
                 if (b < A.max_payload && lane == 0) pay[b] = (uint8_t)((hi << 4) | nib);
+                if constexpr (TAP) {                              // (never past the row, whatever the input)
+                    if (tp.n < tp.T.cap && lane == 0) tp.row[tp.n] = (uint8_t)((hi << 4) | nib);
+                    tp.n++;
+                }
             } else {
                 hi = nib;
             }
@@ -306,6 +345,14 @@ struct LiveStreamSink {
         wave_lds_sync();
         if (live_demod(st)) copy_tail(true, tail_from(st), st.rec_len, lane);
         if (lane == 0) A.dm[c] = ds;
+        if constexpr (TAP) {
+            if (lane == 0) {
+                const bool open = st.mode == 2;                     // (a flush has reported it: nothing is open)
+                tp.T.n[c] = tp.n;
+                tp.T.open_start[c] = open ? st.rec_start : -1;
+                tp.T.open_nbytes[c] = open && ds.phase >= 2 ? (ds.nbits / 7) >> 1 : 0;
+            }
+        }
     }
     __device__ __forceinline__ void clear(const LiveArgs&, int64_t slot0, int i) const {
         const int64_t s = slot0 + i;
@@ -315,8 +362,10 @@ struct LiveStreamSink {
         A.out_term_frame[s] = -1;
         A.out_status[s] = AFSK_ST_TOO_SHORT;
         if (A.out_corrected) A.out_corrected[s] = 0;
+        if constexpr (TAP) tp.T.len[s] = 0;
     }
 };
+using LiveStreamSink = LiveStreamSinkT<false>;
 
 __global__ __launch_bounds__(256) void live_stream_kernel(LiveStreamArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kStreamWinLds];
@@ -345,14 +394,15 @@ __global__ __launch_bounds__(256) void live_stream_reset_kernel(LiveChan* chan, 
 
 namespace afsk {
 
-int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
+// the kernel arguments of a push (live_stream_push below, live_stream_push_tap in afsk_live_tap.hip)
+int live_stream_args(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
                      int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                     const DemodOutputs& o, hipStream_t stream) {
+                     const DemodOutputs& o, LiveStreamArgs& a) {
     LiveStreamLayout L;
     if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L, live->per_channel))
         return rc;
     uint8_t* d = live->state.ptr();
-    LiveStreamArgs a{};
+    a = LiveStreamArgs{};
     a.g.chan = reinterpret_cast<LiveChan*>(d);
     a.g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
     a.g.chunk = chunk_len > 0 ? chunk : a.g.carry;       // (T = 0: never read)
@@ -380,11 +430,22 @@ int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_st
     a.out_term_frame = o.term_frame;
     a.out_status = o.status;
     a.out_corrected = o.corrected;
+    return AFSK_OK;
+}
+
+int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
+                     int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
+                     const DemodOutputs& o, hipStream_t stream) {
+    LiveStreamArgs a;
+    if (int rc = live_stream_args(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
+                                  out_burst_len, out_flags, o, a))
+        return rc;
+    const uint32_t grid = (uint32_t)((live->L.n + 3) / 4);
     if (live->per_channel)
-        hipLaunchKernelGGL(live_stream_thr_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, stream, a,
-                           live->thr_start(), live->thr_end());
+        hipLaunchKernelGGL(live_stream_thr_kernel, dim3(grid), dim3(256), 0, stream, a, live->thr_start(),
+                           live->thr_end());
     else
-        hipLaunchKernelGGL(live_stream_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(live_stream_kernel, dim3(grid), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK
                            : hip_fail(e, live->per_channel ? "launch live_stream_thr_kernel" : "launch live_stream_kernel");

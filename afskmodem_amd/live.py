@@ -7,7 +7,9 @@ A ``LiveReceiver`` keeps, on the device, every channel's gate state, stream posi
 returns the bursts that closed during those T samples, already demodulated -- two asynchronous launches
 (``afsk_live_push``), no host synchronisation, so one push of a fixed T can be captured into a graph and replayed
 for every chunk.  ``flush`` ends every stream (a burst still recording is reported as open-ended); ``reset`` drops
-channels without reporting.  Any sequence of pushes followed by a flush reports what ``gate_batch`` +
+channels without reporting.  A ``progressive`` streaming receiver also returns, push by push, the payload bytes decoded
+during each push (``LiveResult.partials``, ``PayloadAssembler``).
+Any sequence of pushes followed by a flush reports what ``gate_batch`` +
 ``Receiver.decode_captures`` report on the concatenated capture.
 
 Transmit: a ``LiveTransmitter`` keeps a queue of messages per channel on the device; each ``pull`` writes the next T
@@ -131,6 +133,33 @@ def stream_layout(n_channels: int, max_payload_len: int, max_chunk_len: int) -> 
     return int(slots.value), int(nbytes.value)
 
 
+def tap_layout(n_channels: int, max_payload_len: int, max_chunk_len: int, min_bit_frames: int) -> int:
+    """``tap_cap``, the bytes of one tap row of a progressive streaming receiver whose smallest ``bit_frames`` is
+    ``min_bit_frames`` (``afsk_live_tap_layout``: host-only): an upper bound on what one channel commits in one push,
+    ``((K + 1) * 2048 // min_bit_frames) // 14 + 1`` with ``K = (2047 + max_chunk_len) // 2048``."""
+    cap = C.c_int32()
+    _native.check(_native.lib().afsk_live_tap_layout(int(n_channels), int(max_payload_len), int(max_chunk_len),
+                                                     int(min_bit_frames), C.byref(cap)))
+    return int(cap.value)
+
+
+def _host(t) -> np.ndarray:
+    """A torch tensor or a numpy array as a numpy array on the host."""
+    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+
+
+@dataclass
+class LiveTap:
+    """The payload tap of one progressive push (``afsk_live_push_tap``): row c of ``bytes`` holds the ``n[c]`` payload
+    bytes channel c committed during the push, in time order -- the shares of the bursts reported in slots 0, 1, ...
+    (``len[c, k]`` bytes each), then the share of the burst still recording."""
+    bytes: "object"          # uint8 [n_channels, tap_cap]
+    n: "object"              # int32 [n_channels]
+    len: "object"            # int32 [n_channels, slots]
+    open_start: "object"     # int64 [n_channels] first sample of the burst still recording, or -1
+    open_nbytes: "object"    # int32 [n_channels] its payload bytes committed so far
+
+
 @dataclass
 class LiveResult:
     """Device-resident outputs of one push (torch tensors).  Slot ``(c, k)`` is the k-th burst channel c reported in
@@ -141,10 +170,39 @@ class LiveResult:
     burst_len: "object"      # int32 [n_channels, slots] multiple of 2048
     flags: "object"          # int32 [n_channels, slots] LIVE_OPEN_END | LIVE_OVERFLOW
     demod: batch.DemodResult
+    tap: "LiveTap | None" = None     # a progressive receiver's push only
 
     @property
     def slots(self) -> int:
         return int(self.burst_len.shape[1])
+
+    def partials(self) -> list[tuple[int, int, int, bytes, bool]]:
+        """Synchronise and return ``(channel, burst_start, offset, data, final)`` per payload segment of this push,
+        channel by channel and in time order: ``data`` are the bytes ``[offset, offset + len(data))`` of the payload
+        of the burst that starts at stream sample ``burst_start`` of the channel, decoded during this push.  ``final``
+        segments come with their burst's slot, one per reported burst -- with ``data == b""`` when the burst closed
+        without new bytes (also: decoded nothing, or overflowed, which withdraws it).  A burst that is still recording
+        gives a segment only when the push decoded bytes of it.  Needs a push of a ``progressive`` receiver."""
+        if self.tap is None:
+            raise ValueError("partials() needs the result of a progressive receiver's push (LiveReceiver(..., "
+                             "progressive=True))")
+        if hasattr(self.n_closed, "is_cuda") and self.n_closed.is_cuda:
+            batch._torch().cuda.synchronize(self.n_closed.device)
+        nc, bs, nbytes = _host(self.n_closed), _host(self.burst_start), _host(self.demod.nbytes)
+        tap = self.tap
+        tb, tn, tl, os_, on = (_host(t) for t in (tap.bytes, tap.n, tap.len, tap.open_start, tap.open_nbytes))
+        s = self.slots
+        out = []
+        for c in np.nonzero((nc > 0) | (tn > 0))[0].tolist():
+            at = 0
+            for k in range(int(nc[c])):
+                ln = int(tl[c, k])
+                out.append((c, int(bs[c, k]), int(nbytes[c * s + k]) - ln, tb[c, at:at + ln].tobytes(), True))
+                at += ln
+            rest = int(tn[c]) - at
+            if rest > 0 and os_[c] >= 0:
+                out.append((c, int(os_[c]), int(on[c]) - rest, tb[c, at:at + rest].tobytes(), False))
+        return out
 
     def bursts(self, string: bool = False) -> list[tuple[int, int, int, "bytes | str"]]:
         """Synchronise and return ``(channel, start, length, payload)`` per reported burst, channel by channel and in
@@ -165,6 +223,64 @@ class LiveResult:
                 data = b"" if fl[c, k] & _native.LIVE_OVERFLOW else _text_or_bytes(payloads[c * s + k], string)
                 out.append((c, int(bs[c, k]), int(bl[c, k]), data))
         return out
+
+
+class PayloadAssembler:
+    """Puts the payload segments of a progressive receiver's pushes back together (host only).  ``feed(result)`` takes
+    the ``LiveResult`` of every push, in order, and returns ``(channel, start, length, payload)`` for the bursts that
+    push reported -- what ``LiveResult.bursts()`` returns, with the WHOLE payload whatever ``max_payload_len`` is
+    (b"" for an overflowed burst, as there).  ``pending()`` shows the payloads of the bursts still recording."""
+
+    def __init__(self, string: bool = False):
+        self.string = string
+        self._open: dict[int, tuple[int, bytearray]] = {}      # channel -> (burst_start, payload so far)
+
+    def feed(self, result: LiveResult) -> list[tuple[int, int, int, "bytes | str"]]:
+        events = result.partials()
+        nc, bs, bl, fl = (_host(t) for t in (result.n_closed, result.burst_start, result.burst_len, result.flags))
+        used = {c: 0 for c in np.nonzero(nc)[0].tolist()}
+        out = []
+        for c, start, offset, data, final in events:
+            held = self._open.get(c)
+            if held is None or held[0] != start:                    # a new burst (a reset dropped the one held)
+                held = (start, bytearray())
+                self._open[c] = held
+            if final:
+                k = used[c]
+                used[c] = k + 1
+                del self._open[c]
+                if fl[c, k] & _native.LIVE_OVERFLOW:
+                    payload = b""
+                else:
+                    if offset != len(held[1]):
+                        raise ValueError(f"channel {c}, burst at {start}: a segment at offset {offset} follows "
+                                         f"{len(held[1])} bytes -- a push is missing or out of order")
+                    payload = bytes(held[1] + data)
+                out.append((c, start, int(bl[c, k]), _text_or_bytes(payload, self.string)))
+            else:
+                if offset != len(held[1]):
+                    raise ValueError(f"channel {c}, burst at {start}: a segment at offset {offset} follows "
+                                     f"{len(held[1])} bytes -- a push is missing or out of order")
+                held[1].extend(data)
+        # a burst that is held but no longer recording was dropped by a reset
+        open_start = _host(result.tap.open_start)
+        for c in [c for c, (start, _) in self._open.items() if open_start[c] != start]:
+            del self._open[c]
+        return out
+
+    def pending(self) -> dict[int, tuple[int, bytes]]:
+        """``{channel: (burst_start, payload so far)}`` of the bursts still recording that have decoded bytes."""
+        return {c: (start, bytes(data)) for c, (start, data) in self._open.items()}
+
+    def drop(self, mask=None) -> None:
+        """Forget the open bursts of every channel (``mask`` None) or of the channels where ``mask`` is true, as
+        ``LiveReceiver.reset`` does on the device."""
+        if mask is None:
+            self._open.clear()
+            return
+        m = np.asarray(_host(mask)).astype(bool)
+        for c in [c for c in self._open if m[c]]:
+            del self._open[c]
 
 
 class LiveReceiver(batch._NativePlan):
@@ -190,13 +306,20 @@ class LiveReceiver(batch._NativePlan):
     Its capacity is ``max_payload_len`` (0 ... 65536) bytes of payload per burst: a longer payload's row is truncated,
     its ``nbytes`` is the full count.  It has no margins.
 
+    ``progressive=True`` (streaming only, ValueError otherwise) builds it with the payload tap
+    (``afsk_live_create_stream_tap``): every push also returns, in ``LiveResult.tap``, the payload bytes each channel
+    decoded DURING that push -- ``LiveResult.partials()`` lists them per burst, ``assembler()`` puts them together --
+    so bytes arrive while a burst is still recording and a payload of any length is received; ``max_payload_len=0``
+    then keeps 16 KiB of state per channel.  ``tap_cap`` is the bytes of a tap row (``tap_layout``; None otherwise).
+    The state, the slots and every other output are the streaming receiver's.
+
     The receiver belongs to the device that was current (or ``device``); ``close()`` only after its pushes have
     completed."""
     _destroy = "afsk_live_destroy"
 
     def __init__(self, n_channels: int, bit_frames: int, amp_start_threshold=18000, amp_end_threshold=14000,
                  max_burst_len: int | None = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN,
-                 device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN):
+                 device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, progressive: bool = False):
         torch = batch._torch()
         self.n_channels = int(n_channels)
         rates = _per_channel(bit_frames, self.n_channels, "bit_frames")
@@ -218,8 +341,15 @@ class LiveReceiver(batch._NativePlan):
         self.max_burst_len = None if self.streaming else int(max_burst_len)
         self.max_payload_len = int(max_payload_len) if self.streaming else None
         self.max_chunk_len = int(max_chunk_len)
+        self.progressive = bool(progressive)
+        if self.progressive and not self.streaming:
+            raise ValueError("progressive=True needs the streaming receiver (max_burst_len=None): a stored receiver "
+                             "demodulates a burst only when it closes")
+        self.tap_cap = None
         if self.streaming:                                                            # (before the device check)
             self.slots = stream_layout(self.n_channels, self.max_payload_len, self.max_chunk_len)[0]
+            if self.progressive:
+                self.tap_cap = tap_layout(self.n_channels, self.max_payload_len, self.max_chunk_len, min(rates))
         else:
             self.slots = layout(self.n_channels, self.max_burst_len, self.max_chunk_len)[0]
         super().__init__(device)
@@ -233,7 +363,11 @@ class LiveReceiver(batch._NativePlan):
         nbytes = C.c_int64()
         with torch.cuda.device(self.device):
             # (one rate / one threshold pair in every entry: the C entries build the one-rate / one-pair receiver)
-            if self.streaming:
+            if self.progressive:
+                _native.check(_native.lib().afsk_live_create_stream_tap(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_amp_start),
+                    _i32_ptr(self.channel_amp_end), self.max_payload_len, self.max_chunk_len, C.byref(self._h)))
+            elif self.streaming:
                 _native.check(_native.lib().afsk_live_create_stream_thresholds(
                     self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_amp_start),
                     _i32_ptr(self.channel_amp_end), self.max_payload_len, self.max_chunk_len, C.byref(self._h)))
@@ -249,7 +383,7 @@ class LiveReceiver(batch._NativePlan):
         """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  ``thresholds="shared"``: their
         thresholds must agree (ValueError otherwise) and are the receiver's one pair; ``"per_channel"``: channel c
         gets ``receivers[c]``'s pair.  ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples),
-        ``max_payload_len`` (bytes, with ``max_burst_len=None``) and ``device``."""
+        ``max_payload_len`` (bytes, with ``max_burst_len=None``), ``progressive`` (likewise) and ``device``."""
         receivers = list(receivers)
         if not receivers:
             raise ValueError("from_receivers needs at least one Receiver")
@@ -268,7 +402,8 @@ class LiveReceiver(batch._NativePlan):
     def alloc_result(self, diagnostics: bool = False, margin_stride: int | None = None) -> LiveResult:
         """Output buffers for ``push(out=...)`` (double-buffered pushes, graph capture).  ``diagnostics``: also the
         demodulator's ``corrected`` / ``margins`` (``margin_stride`` symbols per slot, default: the longest burst);
-        a streaming receiver has ``corrected`` only (``margins`` None)."""
+        a streaming receiver has ``corrected`` only (``margins`` None).  A progressive receiver's result also holds the
+        tap tensors (``LiveResult.tap``)."""
         torch = batch._torch()
         n, s, dev = self.n_channels, self.slots, self.device
         demod = batch.alloc_result(n * s, self.out_stride, dev)
@@ -279,7 +414,18 @@ class LiveReceiver(batch._NativePlan):
             demod.corrected = torch.zeros(n * s, dtype=torch.int32, device=dev)
             demod.margins = torch.zeros((n * s, ms), dtype=torch.int32, device=dev)
         z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod)
+        tap = None
+        if self.progressive:
+            tap = LiveTap(z(torch.uint8, n, self.tap_cap), z(torch.int32, n), z(torch.int32, n, s),
+                          torch.full((n,), -1, dtype=torch.int64, device=dev), z(torch.int32, n))
+        return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod,
+                          tap)
+
+    def assembler(self, string: bool = False) -> PayloadAssembler:
+        """A ``PayloadAssembler`` for this (progressive) receiver's pushes."""
+        if not self.progressive:
+            raise ValueError("assembler() needs a progressive receiver (LiveReceiver(..., progressive=True))")
+        return PayloadAssembler(string)
 
     def _chunk(self, chunk):
         torch = batch._torch()
@@ -314,6 +460,8 @@ class LiveReceiver(batch._NativePlan):
         elif (tuple(out.burst_len.shape) != (self.n_channels, self.slots) or out.burst_len.device != dev
               or int(out.demod.nbytes.numel()) != self.n_channels * self.slots):
             raise ValueError("out= was not allocated by this receiver's alloc_result")
+        if self.progressive and (out.tap is None or tuple(out.tap.bytes.shape) != (self.n_channels, self.tap_cap)):
+            raise ValueError("out= was not allocated by this progressive receiver's alloc_result")
         d = out.demod
         soft = (None, None, 0)
         if d.corrected is not None and d.margins is not None:
@@ -326,12 +474,17 @@ class LiveReceiver(batch._NativePlan):
                 batch._order_after_current(stream, dev)
             if uploaded and stream is not None:
                 chunk.record_stream(stream)
-            _native.check(_native.lib().afsk_live_push(
-                self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T, int(bool(flush)),
-                out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
-                d.bytes.data_ptr(), int(d.bytes.shape[1]), d.nbytes.data_ptr(), d.nbits.data_ptr(),
-                d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(), *soft,
-                batch._stream_ptr(stream, dev)))
+            args = (self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T, int(bool(flush)),
+                    out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
+                    d.bytes.data_ptr(), int(d.bytes.shape[1]), d.nbytes.data_ptr(), d.nbits.data_ptr(),
+                    d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(), *soft)
+            if self.progressive:
+                t = out.tap
+                _native.check(_native.lib().afsk_live_push_tap(
+                    *args, t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
+                    t.open_nbytes.data_ptr(), batch._stream_ptr(stream, dev)))
+            else:
+                _native.check(_native.lib().afsk_live_push(*args, batch._stream_ptr(stream, dev)))
         out._chunk_keepalive = chunk  # type: ignore[attr-defined]
         return out
 

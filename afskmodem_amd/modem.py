@@ -436,7 +436,8 @@ class Receiver:
     def live(self, n_channels: int, **capacities):
         """A ``live.LiveReceiver`` of ``n_channels`` channels with this Receiver's baud rate and thresholds: the gate of
         ``receive`` (ref:299-319) fed chunk by chunk, every burst demodulated in the push that closes it.
-        ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples) and ``device``."""
+        ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples), ``device``, and for the streaming receiver
+        (``max_burst_len=None``) ``max_payload_len`` and ``progressive`` (payload bytes push by push)."""
         from .live import LiveReceiver
         return LiveReceiver(n_channels, self.__bit_frames, self.__amp_start_threshold, self.__amp_end_threshold,
                             **capacities)

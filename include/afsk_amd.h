@@ -602,6 +602,65 @@ extern int afsk_live_squelch_classes(int32_t n_channels, int32_t slots, const in
                                      int32_t *out_class_count, int32_t *out_class_uniform_bf, int32_t *out_slot_list);
 
 /*
+ * The payload tap of the streaming live receiver (added after ABI version 2; the version is unchanged): a tapped push
+ * also hands out, per channel, the payload bytes the demodulator committed DURING that push, with what it takes to
+ * attribute each byte to its burst and to its offset in that burst's payload.  A byte decoded in the first second of a
+ * long burst reaches the caller with the push that decoded it, not when the gate closes, and the tap never truncates:
+ * with max_payload_len 0 a receiver keeps afsk_live_stream_layout's 16 KiB per channel and receives payloads of any
+ * length.  A tapped receiver is an afsk_live with the state of afsk_live_create_stream_thresholds (afsk_live_stream_layout's
+ * bytes, the thresholds behind them when they differ): info, reset and destroy serve it unchanged, and afsk_live_push
+ * serves it as the streaming receiver it is -- such a push hands out nothing, its bytes are only in the payload rows.
+ *
+ *  afsk_live_tap_layout  host-only (no device needed): tap_cap, the bytes of one tap row -- an upper bound on what one
+ *                        channel commits in one push, AFSK_LIVE_TAP_CAP(max_chunk_len, min_bit_frames) with
+ *                        min_bit_frames the smallest bit_frames of the receiver:
+ *                          ((K + 1) * 2048 / min_bit_frames) / 14 + 1,     K = (2047 + max_chunk_len) / 2048
+ *                        (a push walks K blocks and may commit symbols of the one block before them, which waited for the
+ *                        clock search: at most (K + 1) * 2048 / bf symbols; 14 symbols per byte; one byte more, begun in
+ *                        an earlier push).  Refuses what afsk_live_stream_layout refuses (AFSK_E_INVALID_ARG) and a bad
+ *                        min_bit_frames (AFSK_E_INVALID_BAUD).
+ *  afsk_live_create_stream_tap  arguments, checks, state and gate of afsk_live_create_stream_thresholds; the receiver
+ *                        also accepts afsk_live_push_tap.  Its tap_cap is afsk_live_tap_layout's for its smallest rate.
+ *  afsk_live_push_tap    afsk_live_push (arguments, checks, outputs: field for field those of the untapped push) and,
+ *                        DEVICE arrays written by every push:
+ *                          tap_bytes    uint8 [n_channels, tap_cap]  the bytes committed during this push, in time order
+ *                          tap_n        int32 [n_channels]           how many (<= tap_cap); the row beyond is not written
+ *                          tap_len      int32 [n_channels, slots]    how many of them belong to the burst reported in
+ *                                                                    slot (c, k) of this push; 0 for unused slots
+ *                          open_start   int64 [n_channels]           first stream sample of the burst still recording
+ *                                                                    after this push (its later out_burst_start), or -1
+ *                          open_nbytes  int32 [n_channels]           payload bytes of that burst committed so far, this
+ *                                                                    push's included; 0 when nothing is recording
+ *                        A row reads [slot 0][slot 1] ... [open burst]: slot k's bytes start at the sum of tap_len[c, :k],
+ *                        the open burst's share is tap_n - sum of tap_len[c, :n_closed].  For a burst reported with
+ *                        nbytes = N, its bytes in the reporting push are payload bytes [N - tap_len, N), and its shares
+ *                        of all pushes, in order, are the N bytes afsk_demod_batch_uniform decodes from its recorded
+ *                        samples -- max_payload_len truncates the payload row, never the tap.  A burst that decodes
+ *                        nothing hands out nothing.  A burst longer than AFSK_MAX_STREAM_LEN (AFSK_LIVE_OVERFLOW,
+ *                        nbytes 0) reports tap_len 0; what earlier pushes handed out of it stays handed out.  After a
+ *                        flush nothing is open (open_start -1).  A channel dropped by afsk_live_reset hands out nothing
+ *                        more of its open burst, and its open_start is -1 until a new burst opens.  A receiver that was
+ *                        not created by afsk_live_create_stream_tap: AFSK_E_INVALID_ARG.  ONE launch on hip_stream,
+ *                        nothing on the host in between: capturable into a graph.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_TAP_SIGNATURES.)
+ */
+#define AFSK_LIVE_TAP_CAP(max_chunk_len, min_bit_frames) \
+    ((int32_t)((((2047 + (int64_t)(max_chunk_len)) / 2048 + 1) * 2048 / (min_bit_frames)) / 14 + 1))
+
+extern int afsk_live_tap_layout(int32_t n_channels, int32_t max_payload_len, int32_t max_chunk_len,
+                                int32_t min_bit_frames, int32_t *out_tap_cap);
+extern int afsk_live_create_stream_tap(int32_t n_channels, const int32_t *bit_frames_host, const int32_t *amp_start_host,
+                                       const int32_t *amp_end_host, int32_t max_payload_len, int32_t max_chunk_len,
+                                       afsk_live **out);
+extern int afsk_live_push_tap(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                              int32_t flush, int32_t *out_n_closed, int64_t *out_burst_start, int32_t *out_burst_len,
+                              int32_t *out_flags, uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes,
+                              int32_t *out_nbits, int32_t *out_clock_idx, int32_t *out_term_frame, int32_t *out_status,
+                              int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride, uint8_t *tap_bytes,
+                              int32_t *tap_n, int32_t *tap_len, int64_t *open_start, int32_t *open_nbytes,
+                              void *hip_stream);
+
+/*
  * The live transmitter (an addition: ABI version unchanged): Transmitter.transmit (:472-478) for n_channels
  * independent channels at one bit_frames and training length.  Every channel has a device-resident queue of up to
  * queue_depth messages; each pull writes the next n_samples samples of every channel's stream, the queued messages

@@ -4,9 +4,12 @@
     python tools/live_bench.py [--shapes 65536x2048,65536x8192,64x48000] [--seconds 4] [--reps 3] [--json OUT]
                                [--no-verify] [--kernel-stats STATS_CSV]
     python tools/live_bench.py --stream [--stream-cases 65536x8192@1200,...,16384x8192@long] [--json OUT]
+    python tools/live_bench.py --tap [--parent PARENT.so] [--tap-cases 65536x8192@1200,...] [--json OUT] [--txt OUT]
 
 --stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
-(stream_ab below).
+(stream_ab below).  --tap times the streaming receiver's push with and without the payload tap (progressive=True) on the
+same pushes, alternately, and -- with --parent, a libafsk_amd.so of the parent commit -- against that build's
+streaming push in the same run (tap_ab below).
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -23,6 +26,7 @@ same streams, and every channel's payloads against the transmitted ones.
 """
 import argparse
 import csv
+import ctypes as C
 import json
 import os
 import sys
@@ -32,7 +36,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import afskmodem_amd as afskmodem  # noqa: E402
-from afskmodem_amd import batch, synth  # noqa: E402
+from afskmodem_amd import _native, batch, synth  # noqa: E402
 from afskmodem_amd.live import LiveReceiver  # noqa: E402
 
 PEAK = 8.0e12
@@ -188,25 +192,9 @@ def stream_ab(torch, n, T, seconds, baud, reps, seed, long_messages=False):
     max_burst_len 1 s); long_messages: LiveTransmitter channels with 256-byte payloads back to back at 1200 baud
     (stored max_burst_len 4 s).  The streaming receiver's algorithmic bytes: 2 B per pushed sample + its outputs
     (gate fields and DemodOutputs per slot, the payload bytes) -- it reads no burst a second time."""
-    from afskmodem_amd.live import LiveTransmitter
-    total = int(seconds * 48000)
-    n_push = total // T
-    total = n_push * T
+    samples, n_push = stream_workload(torch, n, T, seconds, baud, seed, long_messages)
     bf = 48000 // baud
-    if long_messages:
-        tx = LiveTransmitter(n, baud, 0.5, max_payload_len=256)
-        rng = np.random.default_rng(seed)
-        pays = [bytes(rng.integers(0, 256, 256, dtype=np.uint8)) for _ in range(2 * n)]
-        tx.submit(np.repeat(np.arange(n), 2), pays)
-        samples = torch.zeros((n, total), dtype=torch.int16, device="cuda")
-        samples[:, 4 * BLOCK:] = tx.pull(total - 4 * BLOCK)
-        tx.close()
-        max_burst = 4 * 48000
-    else:
-        plens = (4, 12, 24) if bf <= 160 else (1,)
-        samples, _ = synth.live_channels(n, total, baud, seed, bursts_per_channel=2 if bf <= 160 else 1,
-                                         payload_lens=plens, silent_every=8, device="cuda")
-        max_burst = 48000 if bf <= 160 else 4 * 48000
+    max_burst = 4 * 48000 if long_messages or bf > 160 else 48000
     stored = LiveReceiver(n, bf, max_burst_len=max_burst, max_chunk_len=T)
     streaming = LiveReceiver(n, bf, max_burst_len=None, max_payload_len=256, max_chunk_len=T)
     # eager pass of both: equal bursts (payloads) wherever the stored receiver holds them
@@ -249,6 +237,117 @@ def stream_ab(torch, n, T, seconds, baud, reps, seed, long_messages=False):
     return rec
 
 
+def stream_workload(torch, n, T, seconds, baud, seed, long_messages):
+    """stream_ab's workload: (samples [n, n_push * T] on the device, n_push)."""
+    from afskmodem_amd.live import LiveTransmitter
+    total = int(seconds * 48000)
+    n_push = total // T
+    total = n_push * T
+    bf = 48000 // baud
+    if long_messages:
+        tx = LiveTransmitter(n, baud, 0.5, max_payload_len=256)
+        rng = np.random.default_rng(seed)
+        pays = [bytes(rng.integers(0, 256, 256, dtype=np.uint8)) for _ in range(2 * n)]
+        tx.submit(np.repeat(np.arange(n), 2), pays)
+        samples = torch.zeros((n, total), dtype=torch.int16, device="cuda")
+        samples[:, 4 * BLOCK:] = tx.pull(total - 4 * BLOCK)
+        tx.close()
+    else:
+        plens = (4, 12, 24) if bf <= 160 else (1,)
+        samples, _ = synth.live_channels(n, total, baud, seed, bursts_per_channel=2 if bf <= 160 else 1,
+                                         payload_lens=plens, silent_every=8, device="cuda")
+    return samples, n_push
+
+
+def load_build(path):
+    """Another build of the library (the parent commit's), bound like _native.lib() for the entries it has."""
+    L = C.CDLL(path)
+    for table in (getattr(_native, t) for t in dir(_native) if t.endswith("SIGNATURES")):
+        for name, (res, args) in table.items():
+            if hasattr(L, name):
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = res, args
+    return L
+
+
+class using:
+    """Route the package's native calls to one build for the duration."""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def __enter__(self):
+        self.saved = _native._lib
+        if self.lib is not None:
+            _native._lib = self.lib
+
+    def __exit__(self, *exc):
+        _native._lib = self.saved
+
+
+def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
+    """The streaming push of the parent build (`parent`, a loaded library or None), this build's untapped push and
+    this build's tapped push (payload rows of 256 and of 0 bytes) on the same pushes of stream_ab's workload: one
+    graph per column window, replayed in stream order with HIP events around each replay; the variants take turns
+    pass by pass (after one warm-up pass each), so drift hits all alike.  Per variant: the mean us per push of every
+    pass, their mean, and the spread (max - min) / mean of the passes."""
+    samples, n_push = stream_workload(torch, n, T, seconds, baud, seed, long_messages)
+    bf = 48000 // baud
+    variants = ([("parent", parent, {})] if parent is not None else []) + [
+        ("untapped", None, {}), ("tapped", None, dict(progressive=True)),
+        ("tapped_rows0", None, dict(progressive=True, max_payload_len=0))]
+    runs = []
+    for name, lib, kw in variants:
+        with using(lib):
+            rx = LiveReceiver(n, bf, max_burst_len=None, max_chunk_len=T, **{"max_payload_len": 256, **kw})
+            out = rx.alloc_result()
+            # eager pass: what the pushes decode (and, tapped, hand out)
+            nbytes = tapped = 0
+            for p in range(n_push):
+                rx.push(samples[:, p * T: (p + 1) * T], out=out, flush=p == n_push - 1)
+                nbytes += int(torch.where(out.burst_len.reshape(-1) > 0, out.demod.nbytes, 0).sum())
+                tapped += int(out.tap.n.sum()) if out.tap is not None else 0
+            graphs = graphs_for(torch, rx, samples, n_push, T, out)
+        # (the graphs write into `out`: it lives as long as they do)
+        runs.append(dict(name=name, lib=lib, rx=rx, graphs=graphs, out=out, passes=[], nbytes=nbytes, tapped=tapped,
+                         tap_cap=rx.tap_cap, state_bytes=rx.state_bytes))
+    for r in range(reps + 1):
+        for v in runs:
+            with using(v["lib"]):
+                t = timed_pass(torch, v["rx"], v["graphs"])
+            if r:
+                v["passes"].append(float(np.mean(t)))
+    rec = dict(shape=f"{n}x{T}", baud=baud, workload="long_messages_256B" if long_messages else "synthetic",
+               pushes=n_push, reps=reps, variants={})
+    for v in runs:
+        m = float(np.mean(v["passes"]))
+        rec["variants"][v["name"]] = dict(us_mean=round(m, 2), us_passes=[round(x, 2) for x in v["passes"]],
+                                          spread=round((max(v["passes"]) - min(v["passes"])) / m, 4),
+                                          payload_bytes=v["nbytes"], tap_bytes=v["tapped"], tap_cap=v["tap_cap"],
+                                          state_bytes=v["state_bytes"])
+    base = rec["variants"].get("parent") or rec["variants"]["untapped"]
+    rec["baseline"] = "parent" if "parent" in rec["variants"] else "untapped"
+    for name, v in rec["variants"].items():
+        v["over_baseline"] = round(v["us_mean"] / base["us_mean"], 4)
+    assert len({v["nbytes"] for v in runs}) == 1, "the variants decoded different payloads"
+    assert all(v["tapped"] == v["nbytes"] for v in runs if v["tap_cap"]), "the tap byte count is not the sum of nbytes"
+    torch.cuda.synchronize()
+    for v in runs:
+        del v["graphs"], v["out"]
+        with using(v["lib"]):
+            v["rx"].close()
+    del samples
+    torch.cuda.empty_cache()
+    return rec
+
+
+def tap_line(rec):
+    head = f"{rec['shape']:>11s} @{rec['baud']:<5d} {rec['workload']:19s}"
+    cells = [f"{k} {v['us_mean']:8.1f} us x{v['over_baseline']:.4f} (spread {100 * v['spread']:.2f} %)"
+             for k, v in rec["variants"].items()]
+    return head + "  ".join(cells) + f"   baseline: {rec['baseline']}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="65536x2048,65536x8192,64x48000")
@@ -265,6 +364,11 @@ def main():
                          "shape@long for the LiveTransmitter 256-byte workload)")
     ap.add_argument("--stream-cases", default="65536x8192@1200,65536x2048@1200,65536x8192@12000,65536x8192@300,"
                                               "16384x8192@24,16384x8192@long")
+    ap.add_argument("--tap", action="store_true",
+                    help="the streaming push with and without the payload tap, alternating, per --tap-cases entry")
+    ap.add_argument("--tap-cases", default="65536x8192@1200,65536x2048@1200,16384x8192@long")
+    ap.add_argument("--parent", help="with --tap: libafsk_amd.so of the parent commit, timed in the same run")
+    ap.add_argument("--txt", help="with --tap: the table as text")
     args = ap.parse_args()
     if args.kernel_stats:
         rows = list(csv.DictReader(open(args.kernel_stats)))
@@ -286,6 +390,26 @@ def main():
         return
     import torch
     res = []
+    if args.tap:
+        parent = load_build(args.parent) if args.parent else None
+        lines = []
+        for case in args.tap_cases.split(","):
+            shape, kind = case.split("@")
+            n, T = (int(x) for x in shape.split("x"))
+            rec = tap_ab(torch, n, T, args.seconds, 1200 if kind == "long" else int(kind), args.reps, args.seed,
+                         kind == "long", parent)
+            print(json.dumps(rec), flush=True)
+            lines.append(tap_line(rec))
+            res.append(rec)
+        print("\n".join(lines))
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(tool="tools/live_bench.py --tap", parent=bool(args.parent), seconds=args.seconds,
+                               reps=args.reps, results=res), f, indent=1)
+        if args.txt:
+            with open(args.txt, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.stream:
         for case in args.stream_cases.split(","):
             shape, kind = case.split("@")
