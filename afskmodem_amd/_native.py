@@ -181,6 +181,18 @@ LIVE_TAP_SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The ragged push and pull (afsk_live_push_ragged, afsk_live_tx_pull_ragged: a sample count per channel), likewise.
+LIVE_RAGGED_SIGNATURES = {
+    # afsk_live_push_tap's arguments, the DEVICE lens behind chunk_len and the DEVICE flush mask behind flush
+    "afsk_live_push_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    # afsk_live_tx_pull's arguments, the DEVICE lens behind n_samples
+    "afsk_live_tx_pull_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+}
 
 
 def lib() -> C.CDLL:
@@ -195,7 +207,8 @@ def lib() -> C.CDLL:
         for name, (res, args) in (*SIGNATURES.items(), *SPLIT_SIGNATURES.items(), *LIVE_SIGNATURES.items(),
                                   *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items(),
                                   *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
-                                  *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items()):
+                                  *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
+                                  *LIVE_RAGGED_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -146,3 +146,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // The streaming receiver's payload tap (afsk_live_tap_layout / afsk_live_create_stream_tap / afsk_live_push_tap: the
 // tapped instantiations of the streaming kernels), for the same reason.
 #include "afsk_live_tap.hip"
+// The ragged push of the live receivers (afsk_live_push_ragged: a sample count and a flush bit per channel, the ragged
+// instantiations of the six gate kernels), for the same reason.
+#include "afsk_live_ragged.hip"

@@ -149,9 +149,14 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 // PER_CHANNEL: the thresholds are channel c's entries of thr_start / thr_end (int32 [n] in the receiver's state) instead
 // of a.amp_start / a.amp_end.  One wave walks one channel, so they are wave-uniform: two scalar loads before the block
 // loop, the values in SGPRs for the whole walk.  The instantiations without the flag are the code they were.
-template <bool PER_CHANNEL = false, class Sink>
+// RAGGED (afsk_live_ragged.hip): the channel takes len = clamp(chunk_lens[c], 0, a.chunk_len) samples of its row (a null
+// chunk_lens: a.chunk_len) and flushes when a.flush or flush_mask[c] is set (a null flush_mask: a.flush alone) -- two
+// more wave-uniform scalar loads, walked with in place of a.chunk_len and a.flush.  Nothing at or beyond column len
+// of the row is read.  The instantiations without the flag are the code they were.
+template <bool PER_CHANNEL = false, bool RAGGED = false, class Sink>
 __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, const int32_t* thr_start = nullptr,
-                                               const int32_t* thr_end = nullptr) {
+                                               const int32_t* thr_end = nullptr, const int32_t* chunk_lens = nullptr,
+                                               const uint8_t* flush_mask = nullptr) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= a.n) return;
@@ -162,6 +167,26 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
         amp_start = __builtin_amdgcn_readfirstlane(thr_start[cu]);
         amp_end = __builtin_amdgcn_readfirstlane(thr_end[cu]);
     }
+    int32_t rag_len = 0, rag_flush = 0;                            // RAGGED: the channel's own length and flush bit
+    if constexpr (RAGGED) {
+        const int cu = __builtin_amdgcn_readfirstlane(c);
+        rag_len = a.chunk_len;
+        if (chunk_lens) {
+            const int32_t l = __builtin_amdgcn_readfirstlane(chunk_lens[cu]);
+            rag_len = l < 0 ? 0 : (l > a.chunk_len ? a.chunk_len : l);
+        }
+        rag_flush = a.flush;
+        if (flush_mask) rag_flush |= __builtin_amdgcn_readfirstlane((int32_t)flush_mask[cu]);
+    }
+    // (the plain form reads LiveArgs where it always did)
+    auto len = [&]() -> int32_t {
+        if constexpr (RAGGED) return rag_len;
+        else return a.chunk_len;
+    };
+    auto flush = [&]() -> int32_t {
+        if constexpr (RAGGED) return rag_flush;
+        else return a.flush;
+    };
     sk.init(a, c, amp_end);
     int16_t* carry = a.carry + (int64_t)c * kListenBlock;
     const int16_t* src = a.chunk + (int64_t)c * a.chunk_stride;
@@ -169,7 +194,7 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
     sk.begin(a, lane, st);
 
     const int cl = (int)(st.pos & (kListenBlock - 1));             // carried samples
-    const int32_t nblk = (int32_t)(((int64_t)cl + a.chunk_len) / kListenBlock);
+    const int32_t nblk = (int32_t)(((int64_t)cl + len()) / kListenBlock);
     const int64_t bpos0 = st.pos - cl;                              // stream index of block 0
     int k = 0;                                                      // slots used
     auto report = [&](int32_t flags) {
@@ -218,16 +243,16 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
         for (int j = 0; j < 4; j++) cur[j] = nxt[j];
     }
 
-    if (a.flush) {
+    if (flush()) {
         if (st.mode == 2) report(AFSK_LIVE_OPEN_END);               // gate_scan_kernel's open-ended burst
         st = LiveChan{};                                            // a new stream; the partial block is dropped
     } else {
         // the tail (< 2048 samples) to the carry: carry[i] = stream sample nblk * 2048 + i for i < tail; without a
         // whole block in this push only [cl, tail) is new
-        const int32_t tail = (int32_t)(((int64_t)cl + a.chunk_len) & (kListenBlock - 1));
+        const int32_t tail = (int32_t)(((int64_t)cl + len()) & (kListenBlock - 1));
         const int64_t base = (int64_t)nblk * kListenBlock - cl;
         for (int i = (nblk == 0 ? cl : 0) + lane; i < tail; i += 64) carry[i] = src[base + i];
-        st.pos += a.chunk_len;
+        st.pos += len();
         st.head = sk.head(st);
     }
     sk.finish(a, c, st, lane);
@@ -418,6 +443,81 @@ struct LiveSpec {
 int live_stream_state(const LiveSpec& sp, afsk_live& lv);
 }  // namespace afsk
 
+namespace afsk {
+
+// The checks afsk_live_push and afsk_live_push_ragged share, after the null-handle check and before any device work.
+int live_push_checks(const afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                     const int32_t* out_n_closed, const int64_t* out_burst_start, const int32_t* out_burst_len,
+                     const int32_t* out_flags, const DemodOutputs& o) {
+    if (chunk_len < 0 || chunk_row_stride < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
+    if (chunk_len > live->max_chunk_len)
+        return fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
+    if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
+        return fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (live->max_payload_len >= 0 && o.margins)
+        return fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
+    return AFSK_OK;
+}
+
+// the stored receiver's gate arguments of a push
+void live_stored_args(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
+                      int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
+                      LiveArgs& g) {
+    const LiveLayout& L = live->L;
+    uint8_t* d = live->state.ptr();
+    g = LiveArgs{};
+    g.chan = reinterpret_cast<LiveChan*>(d);
+    g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
+    g.slot_off = reinterpret_cast<int64_t*>(d + L.o_slot_off);
+    g.slot_len = reinterpret_cast<int32_t*>(d + L.o_slot_len);
+    g.rows = reinterpret_cast<int16_t*>(d + L.o_rows);
+    g.chunk = chunk_len > 0 ? chunk : g.rows;        // (T = 0: never read)
+    g.chunk_stride = chunk_len > 0 ? chunk_row_stride : 0;
+    g.row_len = L.row_len;
+    g.cap = L.cap_blocks * kListenBlock;
+    g.chunk_len = chunk_len;
+    g.flush = flush != 0;
+    g.n = (int32_t)L.n;
+    g.slots = (int32_t)L.slots;
+    g.amp_start = live->amp_start;
+    g.amp_end = live->amp_end;
+    g.out_n_closed = out_n_closed;
+    g.out_burst_start = out_burst_start;
+    g.out_burst_len = out_burst_len;
+    g.out_flags = out_flags;
+}
+
+// the stored receiver's second launch (or launches, one per squelch class): the demodulator over the slots
+int live_stored_demod(afsk_live* live, const LiveArgs& g, const DemodOutputs& o, hipStream_t st) {
+    const LiveLayout& L = live->L;
+    uint8_t* d = live->state.ptr();
+    hipError_t e;
+    // two or more squelch classes: the demod kernels once per class, each over its own list of slots
+    for (const SquelchClasses::Class& k : live->classes) {
+        DemodArgs a = o.args<DemodArgs>(g.rows, g.slot_off, g.slot_len, k.amp_end, k.count);
+        a.stream_index = reinterpret_cast<const int32_t*>(d + live->o_list) + k.first;
+        if (k.uniform_bf) {
+            a.uniform_bit_frames = k.uniform_bf;
+            e = launch_demod_uniform(a, st);
+        } else {
+            a.bit_frames = reinterpret_cast<const int32_t*>(d + live->o_slot_bf);
+            e = launch_demod(a, st);
+        }
+        if (e != hipSuccess) return hip_fail(e, "launch the demod kernel (live slots of one squelch class)");
+    }
+    if (!live->classes.empty()) return AFSK_OK;
+    if (live->plan)
+        return afsk_demod_batch_grouped(live->plan, g.rows, g.slot_off, g.slot_len, live->amp_end, o.bytes, o.stride,
+                                        o.nbytes, o.nbits, o.clock_idx, o.term_frame, o.status, o.corrected,
+                                        o.margins, o.margin_stride, st);
+    DemodArgs a = o.args<DemodArgs>(g.rows, g.slot_off, g.slot_len, live->amp_end, (int32_t)(L.n * L.slots));
+    a.uniform_bit_frames = live->bit_frames;
+    e = launch_demod_uniform(a, st);
+    return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_uniform_kernel (live slots)");
+}
+
+}  // namespace afsk
+
 extern "C" {
 
 int afsk_live_layout(int32_t n_channels, int32_t max_burst_len, int32_t max_chunk_len, int32_t* out_slots,
@@ -589,39 +689,17 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
     const afsk::DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
                                out_corrected, out_margins, margin_stride};
     if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
-    if (chunk_len < 0 || chunk_row_stride < 0 || o.negative()) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
-    if (chunk_len > live->max_chunk_len)
-        return afsk::fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
-    if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
-        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (live->max_payload_len >= 0 && out_margins)
-        return afsk::fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
+    if (int rc = afsk::live_push_checks(live, chunk, chunk_row_stride, chunk_len, out_n_closed, out_burst_start,
+                                        out_burst_len, out_flags, o))
+        return rc;
     if (int rc = live->state.check_current()) return rc;
     if (live->max_payload_len >= 0)
         return afsk::live_stream_push(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
                                       out_burst_len, out_flags, o, (hipStream_t)hip_stream);
     const afsk::LiveLayout& L = live->L;
-    uint8_t* d = live->state.ptr();
-    afsk::LiveArgs g{};
-    g.chan = reinterpret_cast<afsk::LiveChan*>(d);
-    g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
-    g.slot_off = reinterpret_cast<int64_t*>(d + L.o_slot_off);
-    g.slot_len = reinterpret_cast<int32_t*>(d + L.o_slot_len);
-    g.rows = reinterpret_cast<int16_t*>(d + L.o_rows);
-    g.chunk = chunk_len > 0 ? chunk : g.rows;        // (T = 0: never read)
-    g.chunk_stride = chunk_len > 0 ? chunk_row_stride : 0;
-    g.row_len = L.row_len;
-    g.cap = L.cap_blocks * afsk::kListenBlock;
-    g.chunk_len = chunk_len;
-    g.flush = flush != 0;
-    g.n = (int32_t)L.n;
-    g.slots = (int32_t)L.slots;
-    g.amp_start = live->amp_start;
-    g.amp_end = live->amp_end;
-    g.out_n_closed = out_n_closed;
-    g.out_burst_start = out_burst_start;
-    g.out_burst_len = out_burst_len;
-    g.out_flags = out_flags;
+    afsk::LiveArgs g;
+    afsk::live_stored_args(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
+                           out_burst_len, out_flags, g);
     const hipStream_t st = (hipStream_t)hip_stream;
     if (live->per_channel)
         hipLaunchKernelGGL(afsk::live_gate_thr_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g,
@@ -631,28 +709,7 @@ int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stri
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return afsk::hip_fail(e, live->per_channel ? "launch live_gate_thr_kernel" : "launch live_gate_kernel");
-    // two or more squelch classes: the demod kernels once per class, each over its own list of slots
-    for (const afsk::SquelchClasses::Class& k : live->classes) {
-        afsk::DemodArgs a = o.args<afsk::DemodArgs>(g.rows, g.slot_off, g.slot_len, k.amp_end, k.count);
-        a.stream_index = reinterpret_cast<const int32_t*>(d + live->o_list) + k.first;
-        if (k.uniform_bf) {
-            a.uniform_bit_frames = k.uniform_bf;
-            e = afsk::launch_demod_uniform(a, st);
-        } else {
-            a.bit_frames = reinterpret_cast<const int32_t*>(d + live->o_slot_bf);
-            e = afsk::launch_demod(a, st);
-        }
-        if (e != hipSuccess) return afsk::hip_fail(e, "launch the demod kernel (live slots of one squelch class)");
-    }
-    if (!live->classes.empty()) return AFSK_OK;
-    if (live->plan)
-        return afsk_demod_batch_grouped(live->plan, g.rows, g.slot_off, g.slot_len, live->amp_end, o.bytes, o.stride,
-                                        o.nbytes, o.nbits, o.clock_idx, o.term_frame, o.status, o.corrected,
-                                        o.margins, o.margin_stride, st);
-    afsk::DemodArgs a = o.args<afsk::DemodArgs>(g.rows, g.slot_off, g.slot_len, live->amp_end, (int32_t)(L.n * L.slots));
-    a.uniform_bit_frames = live->bit_frames;
-    e = afsk::launch_demod_uniform(a, st);
-    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch demod_uniform_kernel (live slots)");
+    return afsk::live_stored_demod(live, g, o, st);
 }
 
 int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_stream) {

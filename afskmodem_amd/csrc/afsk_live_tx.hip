@@ -14,6 +14,11 @@
 //                         16-byte store; reads the channel state, writes only the caller's buffer
 //   live_tx_commit_kernel one thread per channel: advances pos, retires the messages that have ended, writes pending
 //
+// A ragged pull (afsk_live_tx_pull_ragged) is the same two launches in their RAGGED form: channel c renders and advances
+// by len_c = clamp(lens[c], 0, T) samples, lens a DEVICE int32 [n] array read by the kernels.  A block renders tiles of
+// one channel, so len_c is one block-uniform scalar load; tiles at or past len_c do nothing, the tile that straddles
+// it is cut there (tx_store's partial store), and columns [len_c, T) of the row are not written.
+//
 // A mixed transmitter (afsk_live_tx_create_mixed) keeps each channel's bit_frames and training symbols in a TxGeom
 // array past the uniform layout; submit and live_tx_tile_kernel_mixed read them per channel, and the tile kernel picks
 // the small- or large-q tone code per wave (a wave renders tiles of one channel, so the branch is wave-uniform).
@@ -248,9 +253,10 @@ __device__ __forceinline__ void tx_render(int16_t* dst0, uint32_t len, int32_t x
 }
 
 // KIND 0 / 1: a uniform transmitter whose q = bf / 4 is >= 8 / < 8 (a.bf, a.n_train_sym); KIND 2: a mixed one, the
-// channel's geometry from geom[c] and the tone code chosen per wave
-template <int KIND>
-__device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom) {
+// channel's geometry from geom[c] and the tone code chosen per wave.  RAGGED: the channel's samples end at
+// clamp(lens[c], 0, a.T) instead of a.T (a null lens: a.T); the instantiations without the flag are the code they were.
+template <int KIND, bool RAGGED = false>
+__device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, const int32_t* lens = nullptr) {
     __shared__ uint8_t win[kWinBytes];
     __shared__ unsigned long long kinds[kTxTile / 4 / 64 + 2];
     __shared__ uint32_t qbits[q_words(kTxTile)];
@@ -260,6 +266,14 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom) {
     const int b = bid - c * a.blocks_per_row;
     uint32_t bf = a.bf;
     uint32_t n_train_sym = a.n_train_sym;
+    uint32_t T = (uint32_t)a.T;                                        // samples of the channel in this pull
+    if constexpr (RAGGED) {
+        if (lens) {
+            const int32_t l = lens[c];
+            T = l < 0 ? 0u : min((uint32_t)l, T);
+        }
+        if ((uint32_t)(b * a.tiles_per_block) * kTxTile >= T) return;  // block-uniform: nothing of the channel here
+    }
     // the channel state (and geometry) and its whole descriptor ring, loaded at once (no address depends on another
     // of these loads)
     const TxChan ch = a.chan[c];
@@ -279,7 +293,10 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom) {
         if (t >= a.tiles) break;                                       // block-uniform
         if (k > 0) __syncthreads();                                    // the previous tile's qbits / win are read
         const uint32_t t0 = (uint32_t)t * kTxTile;
-        const uint32_t len = min((uint32_t)kTxTile, (uint32_t)a.T - t0);   // samples of this tile
+        if constexpr (RAGGED) {
+            if (t0 >= T) break;                                        // block-uniform
+        }
+        const uint32_t len = min((uint32_t)kTxTile, T - t0);          // samples of this tile
         int16_t* dst0 = a.out + (int64_t)c * a.out_stride + t0;
         const int64_t p0 = ch.pos + t0;
 
@@ -375,10 +392,9 @@ __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     live_tx_tile<2>(a, geom);
 }
 
-__global__ __launch_bounds__(256) void live_tx_commit_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
-                                                             int32_t depth, int32_t T, int32_t* pending) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n) return;
+// channel c advances by T samples: the messages that have ended are retired, pending is what is left
+__device__ __forceinline__ void live_tx_commit(TxChan* chan, const TxDesc* desc, int c, int32_t depth, int32_t T,
+                                               int32_t* pending) {
     TxChan st = chan[c];
     st.pos += T;
     while (st.count > 0) {
@@ -389,6 +405,37 @@ __global__ __launch_bounds__(256) void live_tx_commit_kernel(TxChan* chan, const
     }
     chan[c] = st;
     pending[c] = st.count;
+}
+
+__global__ __launch_bounds__(256) void live_tx_commit_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
+                                                             int32_t depth, int32_t T, int32_t* pending) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    live_tx_commit(chan, desc, c, depth, T, pending);
+}
+
+// The ragged pull's kernels (afsk_live_tx_pull_ragged): channel c ends at clamp(lens[c], 0, T), lens a DEVICE array.
+template <bool SMALLQ>
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_ragged_kernel(
+    TxPullArgs a, const int32_t* lens) {
+    live_tx_tile<SMALLQ ? 1 : 0, true>(a, nullptr, lens);
+}
+
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_ragged_kernel_mixed(
+    TxPullArgs a, const TxGeom* geom, const int32_t* lens) {
+    live_tx_tile<2, true>(a, geom, lens);
+}
+
+__global__ __launch_bounds__(256) void live_tx_commit_ragged_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
+                                                                    int32_t depth, int32_t T, const int32_t* lens,
+                                                                    int32_t* pending) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    if (lens) {
+        const int32_t l = lens[c];
+        T = l < 0 ? 0 : (l < T ? l : T);
+    }
+    live_tx_commit(chan, desc, c, depth, T, pending);
 }
 
 __global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const uint8_t* mask, int32_t* pending,
@@ -545,8 +592,11 @@ int afsk_live_tx_submit(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_submit_kernel");
 }
 
-int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, int32_t* out_pending,
-                      void* hip_stream) {
+namespace {
+
+// afsk_live_tx_pull and afsk_live_tx_pull_ragged (`ragged`: the ragged kernels, lens a DEVICE array or NULL)
+int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, bool ragged, const int32_t* lens,
+            int32_t* out_pending, void* hip_stream) {
     if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
     if (n_samples < 0 || out_row_stride < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_samples > AFSK_MAX_STREAM_LEN) return afsk::fail(AFSK_E_INVALID_ARG, "n_samples exceeds AFSK_MAX_STREAM_LEN");
@@ -581,7 +631,14 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
         a.bf = (uint32_t)tx->bit_frames;
         a.n_train_sym = (uint32_t)tx->n_train_sym;
         const dim3 grid((uint32_t)(a.blocks_per_row * L.n));
-        if (tx->o_geom)
+        if (ragged && tx->o_geom)
+            hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel_mixed, grid, dim3(afsk::kTxThreads), 0, st, a,
+                               reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom), lens);
+        else if (ragged && tx->bit_frames / 4 >= 8)
+            hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a, lens);
+        else if (ragged)
+            hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel<true>, grid, dim3(afsk::kTxThreads), 0, st, a, lens);
+        else if (tx->o_geom)
             hipLaunchKernelGGL(afsk::live_tx_tile_kernel_mixed, grid, dim3(afsk::kTxThreads), 0, st, a,
                                reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom));
         else if (tx->bit_frames / 4 >= 8) hipLaunchKernelGGL(afsk::live_tx_tile_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a);
@@ -589,10 +646,26 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
         e = hipGetLastError();
         if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_tile_kernel");
     }
-    hipLaunchKernelGGL(afsk::live_tx_commit_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st, chan, desc,
-                       (int32_t)L.n, (int32_t)L.depth, n_samples, out_pending);
+    if (ragged)
+        hipLaunchKernelGGL(afsk::live_tx_commit_ragged_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st,
+                           chan, desc, (int32_t)L.n, (int32_t)L.depth, n_samples, lens, out_pending);
+    else
+        hipLaunchKernelGGL(afsk::live_tx_commit_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st, chan, desc,
+                           (int32_t)L.n, (int32_t)L.depth, n_samples, out_pending);
     e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_commit_kernel");
+}
+
+}  // namespace
+
+int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, int32_t* out_pending,
+                      void* hip_stream) {
+    return tx_pull(tx, out, out_row_stride, n_samples, false, nullptr, out_pending, hip_stream);
+}
+
+int afsk_live_tx_pull_ragged(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples,
+                             const int32_t* d_lens_or_null, int32_t* out_pending, void* hip_stream) {
+    return tx_pull(tx, out, out_row_stride, n_samples, true, d_lens_or_null, out_pending, hip_stream);
 }
 
 int afsk_live_tx_reset(afsk_live_tx* tx, const uint8_t* d_mask_or_null, int32_t* out_pending_or_null,

@@ -96,6 +96,43 @@ def _device_mask(mask, n_channels: int, dev):
     return m
 
 
+def _device_lengths(lengths, n_channels: int, dev, owner: str):
+    """The per-channel sample counts of a ragged push or pull as ``(int32 [n_channels] tensor on dev, uploaded)``: an
+    int32 CUDA tensor on ``dev`` is used in place (no copy, no synchronisation), a host sequence or numpy array of
+    integers is uploaded with one copy."""
+    torch = batch._torch()
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype != torch.int32:
+            raise TypeError("lengths must hold int32 sample counts")
+        if not lengths.is_cuda or lengths.device != dev:
+            raise ValueError(f"lengths is on {lengths.device}, the {owner} on {dev}")
+        if lengths.dim() != 1 or int(lengths.numel()) != n_channels or not lengths.is_contiguous():
+            raise ValueError(f"lengths must be a contiguous [n_channels={n_channels}], got {list(lengths.shape)}")
+        return lengths, False
+    v = np.asarray(lengths)
+    if v.dtype.kind not in "iu":
+        raise TypeError("lengths must hold integer sample counts")
+    if v.ndim != 1 or v.size != n_channels:
+        raise ValueError(f"lengths must be [n_channels={n_channels}], got {list(v.shape)}")
+    v = np.clip(v.astype(np.int64), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)     # (the kernels clamp to 0 ... T)
+    return torch.from_numpy(np.ascontiguousarray(v)).to(dev), True
+
+
+def _flush_mask(flush, n_channels: int, dev):
+    """A per-channel ``flush`` ([n_channels] bool / uint8, host or device) as ``(uint8 tensor on dev, the caller's own
+    tensor)`` through ``_device_mask``; a tensor or array of another dtype is a TypeError."""
+    torch = batch._torch()
+    if isinstance(flush, torch.Tensor):
+        if flush.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("a flush mask must hold bool or uint8 entries")
+        if flush.is_cuda and flush.device != dev:
+            raise ValueError(f"the flush mask is on {flush.device}, the receiver on {dev}")
+    elif np.asarray(flush).dtype.kind not in "biu":
+        raise TypeError("a flush mask must hold bool or integer entries")
+    m = _device_mask(flush, n_channels, dev)
+    return m, m is flush
+
+
 def _check_rows(t, name: str, owner: str, n_channels: int, dev, T: int | None = None,
                 max_chunk_len: int | None = None) -> None:
     """Check the torch tensor ``t`` as an int16 ``[n_channels, >= T]`` view on ``dev`` with contiguous rows and any
@@ -445,15 +482,33 @@ class LiveReceiver(batch._NativePlan):
         _check_rows(chunk, "chunk", "receiver", self.n_channels, self.device, max_chunk_len=self.max_chunk_len)
         return chunk, False
 
-    def push(self, chunk, stream=None, out: LiveResult | None = None, flush: bool = False) -> LiveResult:
+    def push(self, chunk, stream=None, out: LiveResult | None = None, flush=False, lengths=None) -> LiveResult:
         """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
         column window of a [channels, time] buffer, no copy -- or a numpy array, uploaded with one copy; None = T 0)
         to every channel's stream and return the bursts that closed, demodulated.  ``flush``: then end every stream
         (``flush()``).  Asynchronous on ``stream`` (default: torch's current stream); ``out`` reuses buffers of
-        ``alloc_result``."""
+        ``alloc_result``.
+
+        Ragged pushes (``afsk_live_push_ragged``): with ``lengths`` ([n_channels]) channel c appends only the first
+        ``clamp(lengths[c], 0, T)`` samples of its row, and nothing of the row beyond them is read -- an int32 CUDA
+        tensor on the receiver's device is used in place (no copy, no synchronisation: the kernels read it when they
+        run, so a captured push replays with new lengths), a host sequence or numpy array is uploaded with one copy.
+        ``flush`` may be an [n_channels] bool / uint8 mask (host or device): only those channels' streams end.  A
+        channel with length 0 and no flush keeps its state.  Without ``lengths`` and with a bool ``flush`` the push is
+        the plain one."""
         torch = batch._torch()
         chunk, uploaded = self._chunk(chunk)
         dev = self.device
+        lens = mask = None
+        own = True                                   # every per-channel array is the caller's own device tensor
+        if lengths is not None:
+            lens, up = _device_lengths(lengths, self.n_channels, dev, "receiver")
+            own = own and not up
+        if isinstance(flush, torch.Tensor) or np.ndim(flush) > 0:
+            mask, mine = _flush_mask(flush, self.n_channels, dev)
+            own = own and mine
+            flush = False
+        ragged = lens is not None or mask is not None
         fresh = out is None
         if fresh:
             out = self.alloc_result()
@@ -470,28 +525,38 @@ class LiveReceiver(batch._NativePlan):
             soft = (d.corrected.data_ptr(), None, 0)
         T = int(chunk.shape[1])
         with torch.cuda.device(dev):
-            if fresh or uploaded:
+            if fresh or uploaded or not own:
                 batch._order_after_current(stream, dev)
-            if uploaded and stream is not None:
-                chunk.record_stream(stream)
-            args = (self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T, int(bool(flush)),
-                    out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
+            if stream is not None:                   # what this call uploaded is used on `stream`
+                for t in ([chunk] if uploaded else []) + ([] if own else [x for x in (lens, mask) if x is not None]):
+                    t.record_stream(stream)
+            head = (self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T)
+            outs = (out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
                     d.bytes.data_ptr(), int(d.bytes.shape[1]), d.nbytes.data_ptr(), d.nbits.data_ptr(),
                     d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(), *soft)
+            taps = (None,) * 5
             if self.progressive:
                 t = out.tap
-                _native.check(_native.lib().afsk_live_push_tap(
-                    *args, t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
-                    t.open_nbytes.data_ptr(), batch._stream_ptr(stream, dev)))
+                taps = (t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
+                        t.open_nbytes.data_ptr())
+            if ragged:
+                _native.check(_native.lib().afsk_live_push_ragged(
+                    *head, None if lens is None else lens.data_ptr(), int(bool(flush)),
+                    None if mask is None else mask.data_ptr(), *outs, *taps, batch._stream_ptr(stream, dev)))
+            elif self.progressive:
+                _native.check(_native.lib().afsk_live_push_tap(*head, int(bool(flush)), *outs, *taps,
+                                                               batch._stream_ptr(stream, dev)))
             else:
-                _native.check(_native.lib().afsk_live_push(*args, batch._stream_ptr(stream, dev)))
-        out._chunk_keepalive = chunk  # type: ignore[attr-defined]
+                _native.check(_native.lib().afsk_live_push(*head, int(bool(flush)), *outs,
+                                                           batch._stream_ptr(stream, dev)))
+        out._chunk_keepalive = (chunk, lens, mask)  # type: ignore[attr-defined]
         return out
 
-    def flush(self, chunk=None, stream=None, out: LiveResult | None = None) -> LiveResult:
+    def flush(self, chunk=None, stream=None, out: LiveResult | None = None, mask=None, lengths=None) -> LiveResult:
         """``push(chunk, flush=True)``: end every channel's stream.  A burst still recording is reported (whole blocks,
-        ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0."""
-        return self.push(chunk, stream=stream, out=out, flush=True)
+        ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0.  ``mask``
+        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths``: as ``push``."""
+        return self.push(chunk, stream=stream, out=out, flush=True if mask is None else mask, lengths=lengths)
 
     def reset(self, mask=None, stream=None) -> None:
         """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /
@@ -683,12 +748,17 @@ class LiveTransmitter(batch._NativePlan):
         out._keepalive = d  # type: ignore[attr-defined]
         return out
 
-    def pull(self, T: int, out=None, stream=None):
+    def pull(self, T: int, out=None, stream=None, lengths=None):
         """Write samples ``[pos, pos + T)`` of every channel into ``out`` ([n_channels, >= T] int16 CUDA tensor with
         contiguous rows and any row stride -- e.g. a column window of a [channels, time] buffer; None: a new [n, T]
         tensor) and return ``out[:, :T]``.  Nothing of ``out`` outside those T columns is written.  Then every
         channel advances by T, the messages that ended are retired and ``pending`` is updated.  Asynchronous on
-        ``stream`` (default: torch's current stream)."""
+        ``stream`` (default: torch's current stream).
+
+        A ragged pull (``afsk_live_tx_pull_ragged``): with ``lengths`` ([n_channels]: an int32 CUDA tensor on the
+        transmitter's device, used in place, or a host sequence, uploaded with one copy) channel c writes only columns
+        ``[0, len_c)`` with ``len_c = clamp(lengths[c], 0, T)``, leaves the columns from ``len_c`` on as they were
+        (a new ``out`` is zeroed first) and advances by ``len_c``."""
         torch = batch._torch()
         T = int(T)
         if T < 0:
@@ -697,19 +767,28 @@ class LiveTransmitter(batch._NativePlan):
             raise ValueError(f"T = {T} exceeds AFSK_MAX_STREAM_LEN")
         dev = self.device
         fresh = out is None
+        lens, lens_up = (None, False) if lengths is None else _device_lengths(lengths, self.n_channels, dev,
+                                                                             "transmitter")
         if fresh:
-            out = torch.empty((self.n_channels, T), dtype=torch.int16, device=dev)
+            out = (torch.empty if lens is None else torch.zeros)((self.n_channels, T), dtype=torch.int16, device=dev)
         if not isinstance(out, torch.Tensor):
             raise TypeError("out must be an int16 CUDA tensor")
         _check_rows(out, "out", "transmitter", self.n_channels, dev, T)
         if self.n_channels > 1 and T > 0 and out.stride(0) < T:
             raise ValueError(f"out row stride {out.stride(0)} is below T = {T}: the rows would overlap")
         with torch.cuda.device(dev):
-            if fresh:
+            if fresh or lens_up:
                 batch._order_after_current(stream, dev)
-            _native.check(_native.lib().afsk_live_tx_pull(
-                self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T, self.pending.data_ptr(),
-                batch._stream_ptr(stream, dev)))
+            if lens_up and stream is not None:
+                lens.record_stream(stream)
+            if lens is not None:
+                _native.check(_native.lib().afsk_live_tx_pull_ragged(
+                    self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T, lens.data_ptr(),
+                    self.pending.data_ptr(), batch._stream_ptr(stream, dev)))
+            else:
+                _native.check(_native.lib().afsk_live_tx_pull(
+                    self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T,
+                    self.pending.data_ptr(), batch._stream_ptr(stream, dev)))
         return out[:, :T]
 
     def reset(self, mask=None, stream=None) -> None:

@@ -727,6 +727,50 @@ extern int afsk_live_tx_state_bytes_mixed(int32_t n_channels, int32_t queue_dept
                                           int64_t *out_state_bytes);
 
 /*
+ * Ragged pushes and pulls (added after ABI version 2; the version is unchanged): every channel of a live receiver or
+ * transmitter takes its own number of samples per call, and every receiver channel has its own flush bit -- sources that
+ * run on their own clocks, one source that disconnects while the others go on.  chunk_len / n_samples is the number of
+ * COLUMNS of the buffer and bounds every channel's count; every host check of afsk_live_push / afsk_live_tx_pull
+ * applies to it (max_chunk_len, the row stride, AFSK_MAX_STREAM_LEN).  The per-channel values are DEVICE arrays that
+ * only the kernels read, never the host: a value below 0 counts as 0, a value above chunk_len / n_samples as
+ * chunk_len / n_samples.  They are read when the launches RUN, so ONE captured graph of a fixed chunk_len / n_samples
+ * serves ticks of any size up to it: rewrite the arrays (and the buffer) between replays.  The state is that of the
+ * plain entries, and plain and ragged calls on one object may alternate.
+ *
+ *  afsk_live_push_ragged     afsk_live_push where channel c appends the first len_c = clamp(d_chunk_lens_or_null[c], 0,
+ *                            chunk_len) samples of its row (int32 [n_channels]; NULL: chunk_len for every channel) and
+ *                            its stream ends when flush != 0 or d_flush_mask_or_null[c] != 0 (uint8 [n_channels]; NULL:
+ *                            flush alone decides).  No sample at or beyond column len_c of a row is read.  A channel that
+ *                            is flushed reports its open burst (AFSK_LIVE_OPEN_END), drops its partial block and starts
+ *                            a new stream at sample 0; the others are not touched by it.  A channel with len_c = 0 and no
+ *                            flush keeps its state exactly -- carry, gate mode, open burst, streaming window -- and
+ *                            reports n_closed 0 (and with the tap outputs tap_n 0, open_start / open_nbytes of the burst
+ *                            still open).  Outputs: every output of afsk_live_push_tap, in its order.  The five tap
+ *                            pointers are all NULL or all given (some of them: AFSK_E_INVALID_ARG).  All NULL: the
+ *                            untapped push, also on a tapped receiver (as afsk_live_push there).  All given: the tapped
+ *                            push; a receiver that was not created by afsk_live_create_stream_tap: AFSK_E_INVALID_ARG.
+ *                            The launches are afsk_live_push's: two for a stored receiver (one more per further squelch
+ *                            class), ONE for a streaming or tapped one, nothing on the host in between: capturable into a
+ *                            graph.
+ *  afsk_live_tx_pull_ragged  afsk_live_tx_pull where channel c writes samples [pos_c, pos_c + len_c) to columns
+ *                            [0, len_c) of its row, len_c = clamp(d_lens_or_null[c], 0, n_samples) (int32 [n_channels];
+ *                            NULL: n_samples for every channel), writes nothing to columns [len_c, n_samples), then
+ *                            advances pos_c by len_c, retires the messages that have ended by then and writes
+ *                            out_pending[c].  Two launches in order on hip_stream, capturable into a graph.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_RAGGED_SIGNATURES.)
+ */
+extern int afsk_live_push_ragged(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                                 const int32_t *d_chunk_lens_or_null, int32_t flush, const uint8_t *d_flush_mask_or_null,
+                                 int32_t *out_n_closed, int64_t *out_burst_start, int32_t *out_burst_len,
+                                 int32_t *out_flags, uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes,
+                                 int32_t *out_nbits, int32_t *out_clock_idx, int32_t *out_term_frame,
+                                 int32_t *out_status, int32_t *out_corrected, int32_t *out_margins,
+                                 int32_t margin_stride, uint8_t *tap_bytes, int32_t *tap_n, int32_t *tap_len,
+                                 int64_t *open_start, int32_t *open_nbytes, void *hip_stream);
+extern int afsk_live_tx_pull_ragged(afsk_live_tx *tx, int16_t *out, int64_t out_row_stride, int32_t n_samples,
+                                    const int32_t *d_lens_or_null, int32_t *out_pending, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,

@@ -1,0 +1,542 @@
+"""GPU parity (-m gpu) of the ragged push and pull (``LiveReceiver.push(lengths=, flush=mask)``,
+``LiveTransmitter.pull(lengths=)``; afsk_live_push_ragged, afsk_live_tx_pull_ragged): every channel takes its own number
+of samples per call and has its own flush bit.
+
+Expected values never come from a live call, ragged or not: they are the CPU oracle's gate (``gate_stream``) and
+demodulator over each channel's whole capture, the reference's own listen vectors (the golden ``listen_cases``),
+``batch.demod_batch`` over the uploaded whole capture, the tap model (tests/live_tap_model.py) fed the channel's own
+chunks, and ``Transmitter.wav_samples``.  Every pushed row holds the channel's samples and, from its length on, a
+full-scale square wave: a kernel that read past a channel's length would open a false gate.
+
+The golden ``no_burst`` case is a channel of the receiver tests like the other closed cases; the oracle gates no burst
+in it, so "at least one burst was compared" is asserted on every other channel, and on that one that none was
+reported."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+import afskmodem_amd as afskmodem
+from afskmodem_amd import _native, batch, live
+from afskmodem_amd.live import LiveReceiver, LiveTransmitter
+from oracle import afsk_oracle as O
+from tests.golden_inputs import build_capture
+from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_tap_model import TapChannelModel
+from tests.test_gpu_live import FIELDS, collect, oracle_bursts
+from tests.test_gpu_live_tap import capture_of, expected
+from tests.test_live_ragged_host import LENGTHS, schedule
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+BLOCK = 2048
+T = 6144                    # max_chunk_len: three blocks, two slots
+POISON = np.where(np.arange(T) % 2 == 0, 32767, -32767).astype(np.int16)
+SENTINEL = 0x5A5A
+
+
+# ------------------------------------------------------------------------------------------------- channels, schedules
+
+def channel(cap, bf, a_start=18000, a_end=14000, case=None):
+    cap = np.ascontiguousarray(cap, np.int16)
+    return dict(cap=cap, bf=bf, a_start=a_start, a_end=a_end, case=case, want=expected(cap, bf, a_start, a_end))
+
+
+@functools.lru_cache(maxsize=None)
+def golden_channels(a_start):
+    """The seven closed listen cases of the reference at one threshold pair (1200 baud)."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_vectors.json")) as f:
+        cases = [c for c in json.load(f)["listen_cases"] if c["amp_start"] == a_start and not c["open_end"]]
+    assert len(cases) == 7
+    return tuple(channel(build_capture(c["recipe"]), 40, c["amp_start"], c["amp_end"], c) for c in cases)
+
+
+def extra(seed, bf, a_start=18000, a_end=14000, nbytes=(6, 11)):
+    rng = np.random.default_rng(seed)
+    pays = [bytes(rng.integers(0, 256, k, dtype=np.uint8)) for k in nbytes]
+    cap = capture_of(rng, bf, pays, sigma=1500.0, training=max(0.05, 3.0 * bf / 48000))
+    ch = channel(cap, bf, a_start, a_end)
+    # (the oracle decides what the noisy capture holds; it must hold something to compare)
+    assert len(ch["want"]) == len(pays) and any(w[3] for w in ch["want"]), (seed, bf)
+    return ch
+
+
+@functools.lru_cache(maxsize=None)
+def channels(kind):
+    a, b = golden_channels(18000), golden_channels(9000)
+    if kind == "uniform":
+        return a + (extra(1, 40),)
+    if kind == "two_pairs":                                     # one rate, two squelch classes
+        return a + b
+    if kind == "mixed":
+        return a + (extra(2, 20), extra(3, 160, nbytes=(4, 5)), extra(4, 8, nbytes=(30, 200)), extra(5, 80))
+    assert kind == "mixed_pairs"
+    return a + b + (extra(6, 160, 12000, 8000, nbytes=(4, 5)), extra(7, 8, 20000, 6000, nbytes=(30, 200)))
+
+
+def schedule_facts(sched, chans):
+    """What a schedule exercises, from the oracle's bursts alone."""
+    n = len(chans)
+    bursts = [[(w[0], w[1]) for w in ch["want"]] for ch in chans]
+    pos = [0] * n
+    facts = dict(two_lengths=False, idle_while_open=False, flush_with_0=False, flush_with_samples=False)
+
+    def records(c, p0, p1):                                     # the push walks a block of one of c's bursts
+        return any(s <= b * BLOCK < s + ln for b in range(p0 // BLOCK, p1 // BLOCK) for s, ln in bursts[c])
+
+    def is_open(c, p0):                                         # a burst of c is recording when the push begins
+        w = p0 // BLOCK * BLOCK
+        return any(s + BLOCK <= w < s + ln for s, ln in bursts[c])
+
+    for lens, mask in sched:
+        after = [p + int(x) for p, x in zip(pos, lens)]
+        if len({int(x) for x in lens if x > 0}) > 1:
+            facts["two_lengths"] = True
+        busy = [records(c, pos[c], after[c]) for c in range(n)]
+        for c in range(n):
+            if lens[c] == 0 and not mask[c] and is_open(c, pos[c]) and any(busy[d] for d in range(n) if d != c):
+                facts["idle_while_open"] = True
+            if mask[c]:
+                facts["flush_with_0" if lens[c] == 0 else "flush_with_samples"] = True
+        pos = after
+    assert pos == [len(ch["cap"]) for ch in chans]
+    return facts
+
+
+@functools.lru_cache(maxsize=None)
+def plan(kind):
+    """(channels, schedule, push buffers [P, n, T]) of a channel set: the first seeded schedule that is ragged in
+    every way the tests rely on (checked here, on the CPU)."""
+    chans = channels(kind)
+    for seed in range(100):
+        sched = schedule(np.random.default_rng(1000 + seed), [len(ch["cap"]) for ch in chans], T)
+        if all(schedule_facts(sched, chans).values()):
+            break
+    else:
+        raise AssertionError("no seed gives a schedule with every property")
+    return chans, sched, push_buffers([ch["cap"] for ch in chans], sched)
+
+
+def push_buffers(caps, sched):
+    """[P, n, T]: row c of push p holds channel c's next lens[c] samples and the poison from there on."""
+    host = np.empty((len(sched), len(caps), T), np.int16)
+    host[:] = POISON
+    pos = [0] * len(caps)
+    for p, (lens, _) in enumerate(sched):
+        for c, cap in enumerate(caps):
+            k = int(lens[c])
+            host[p, c, :k] = cap[pos[c]: pos[c] + k]
+            pos[c] += k
+    assert pos == [len(c) for c in caps]
+    return host
+
+
+def receiver(chans, kind, **kw):
+    bfs, starts, ends = ([ch[k] for ch in chans] for k in ("bf", "a_start", "a_end"))
+    one = lambda v: v[0] if len(set(v)) == 1 else v  # noqa: E731
+    if kind == "stored":
+        return LiveReceiver(len(chans), one(bfs), one(starts), one(ends), max_burst_len=65536, max_chunk_len=T,
+                            device=DEV, **kw)
+    return LiveReceiver(len(chans), one(bfs), one(starts), one(ends), max_burst_len=None, max_payload_len=256,
+                        max_chunk_len=T, device=DEV, progressive=kind == "tapped", **kw)
+
+
+def drive(torch, rx, host, sched, each=None):
+    """Push the buffers with their lengths and masks -- host arrays and device tensors in turn -- and return the
+    bursts per channel."""
+    dev = torch.from_numpy(host).to(DEV)
+    got = [[] for _ in range(host.shape[1])]
+    for p, (lens, mask) in enumerate(sched):
+        ln = torch.from_numpy(lens).to(DEV) if p % 2 else lens
+        fl = (torch.from_numpy(mask).to(DEV) if p % 3 == 0 else mask.astype(bool)) if mask.any() else False
+        res = rx.push(dev[p], lengths=ln, flush=fl)
+        collect(res, got)
+        if each:
+            each(p, res)
+    return got
+
+
+def check_against_oracle(chans, got):
+    compared = []
+    for c, ch in enumerate(chans):
+        spans = [(g["start"], g["len"], g["flags"]) for g in got[c]]
+        assert spans == oracle_bursts(ch["cap"], ch["a_start"], ch["a_end"]), c
+        assert spans == [w[:3] for w in ch["want"]], c
+        assert [g["bytes"] for g in got[c]] == [w[3] for w in ch["want"]], c
+        if ch["case"] is not None:
+            case = ch["case"]
+            assert [(s, n) for s, n, _ in spans] == [(b["start"], b["len"]) for b in case["bursts"]], case["name"]
+            for g, b in zip(got[c], case["bursts"]):
+                if b["len"] == b["ref_len"]:
+                    assert g["bytes"].hex() == b["bytes_hex"], case["name"]
+        compared.append(len(got[c]))
+        if ch["case"] is not None and ch["case"]["name"] == "no_burst":
+            assert compared[-1] == 0
+        else:
+            assert compared[-1] > 0, c
+    return compared
+
+
+def check_demod_against_batch(torch, chans, got, stride):
+    """Every burst's demod fields equal demod_batch over that burst of the uploaded whole capture (one call per
+    squelch threshold, the channels' rates per stream)."""
+    width = max(len(ch["cap"]) for ch in chans)
+    host = np.zeros((len(chans), width), np.int16)
+    for c, ch in enumerate(chans):
+        host[c, : len(ch["cap"])] = ch["cap"]
+    flat = torch.from_numpy(host).to(DEV).reshape(-1)
+    total = 0
+    for a_end in sorted({ch["a_end"] for ch in chans}):
+        rows = [(c, g) for c, ch in enumerate(chans) if ch["a_end"] == a_end for g in got[c]]
+        if not rows:
+            continue
+        offs = torch.tensor([c * width + g["start"] for c, g in rows], dtype=torch.int64, device=DEV)
+        lens = torch.tensor([g["len"] for _, g in rows], dtype=torch.int32, device=DEV)
+        bfs = [chans[c]["bf"] for c, _ in rows]
+        res = batch.demod_batch(flat, offs, lens, bfs[0] if len(set(bfs)) == 1 else bfs, a_end, out_stride=stride).cpu()
+        pay = res.payloads()
+        for j, (c, g) in enumerate(rows):
+            for f in FIELDS:
+                assert g[f] == int(getattr(res, f)[j]), (c, j, f)
+            assert g["bytes"] == pay[j], (c, j)
+        total += len(rows)
+    return total
+
+
+# ------------------------------------------------------------- 1. ragged schedules reproduce the whole-capture result
+
+KINDS = {"stored": ("stored", "uniform"), "stored_thr": ("stored", "two_pairs"), "stored_mixed": ("stored", "mixed"),
+         "stream": ("stream", "mixed"), "stream_thr": ("stream", "mixed_pairs"), "tapped": ("tapped", "mixed")}
+
+
+@pytest.mark.parametrize("name", list(KINDS))
+def test_ragged_schedules_reproduce_the_whole_capture_result(torch_cuda, name):
+    torch = torch_cuda
+    kind, chan_set = KINDS[name]
+    chans, sched, host = plan(chan_set)
+    facts = schedule_facts(sched, chans)
+    assert facts == dict(two_lengths=True, idle_while_open=True, flush_with_0=True, flush_with_samples=True)
+    assert len({int(np.nonzero(np.array([m[c] for _, m in sched]))[0][0]) for c in range(len(chans))}) > 1
+    rx = receiver(chans, kind)
+    if name == "stored_thr":
+        assert rx.bit_frames == 40 and rx.amp_end_threshold is None
+        assert len(live.squelch_classes(rx.channel_bit_frames, rx.channel_amp_end, rx.slots)) == 2
+    if name in ("stored_mixed", "stream", "tapped"):
+        assert rx.bit_frames is None and rx.amp_end_threshold == 14000
+    if name == "stream_thr":
+        assert rx.bit_frames is None and rx.amp_end_threshold is None
+    assert rx.slots == 2
+    got = drive(torch, rx, host, sched)
+    compared = check_against_oracle(chans, got)
+    assert check_demod_against_batch(torch, chans, got, rx.out_stride) == sum(compared)
+    rx.close()
+
+
+# ------------------------------------------------------------------------------------------------ 2. tapped contract
+
+@functools.lru_cache(maxsize=None)
+def tap_plan():
+    rng = np.random.default_rng(42)
+    long_pay = bytes(rng.integers(0, 256, 205, dtype=np.uint8))
+    long_cap = capture_of(rng, 160, [long_pay], sigma=1500.0, training=0.5)      # 160 * (150 + 4 + 14 * 205) samples
+    chans = (channel(long_cap, 160),) + golden_channels(18000)[:3] + (
+        extra(12, 8, nbytes=(60, 300)), extra(13, 20), extra(14, 80), extra(15, 160, 12000, 8000, nbytes=(4, 5)))
+    assert chans[0]["want"][0][3] == long_pay and chans[0]["want"][0][1] >= 10 * 48000
+    sched = schedule(np.random.default_rng(7), [len(ch["cap"]) for ch in chans], T)
+    return chans, sched, push_buffers([ch["cap"] for ch in chans], sched)
+
+
+def test_tapped_outputs_follow_the_tap_model_push_by_push(torch_cuda):
+    torch = torch_cuda
+    chans, sched, host = tap_plan()
+    n = len(chans)
+    rx = receiver(chans, "tapped")
+    models = [TapChannelModel(ch["bf"], ch["a_start"], ch["a_end"], 0) for ch in chans]
+    asm = rx.assembler()
+    done, pos = [], [0] * n
+    open_pushes = idle_open_pushes = 0
+
+    def each(p, res):
+        nonlocal open_pushes, idle_open_pushes
+        lens, mask = sched[p]
+        tp = res.tap
+        tn, tl, os_, on, tb, nc = (t.cpu().numpy() for t in (tp.n, tp.len, tp.open_start, tp.open_nbytes, tp.bytes,
+                                                             res.n_closed))
+        for c in range(n):
+            k = int(lens[c])
+            r = models[c].push(chans[c]["cap"][pos[c]: pos[c] + k], flush=bool(mask[c]))
+            pos[c] += k
+            assert int(tn[c]) == len(r["tap"]) and tb[c, : len(r["tap"])].tobytes() == r["tap"], (p, c)
+            assert int(nc[c]) == len(r["bursts"]) and tl[c, : int(nc[c])].tolist() == r["tap_len"], (p, c)
+            assert not tl[c, int(nc[c]):].any(), (p, c)
+            assert (int(os_[c]), int(on[c])) == (r["open_start"], r["open_nbytes"]), (p, c)
+            if k == 0 and not mask[c]:
+                assert int(tn[c]) == 0 and int(nc[c]) == 0, (p, c)
+        if os_[0] >= 0:
+            open_pushes += 1
+            idle_open_pushes += int(lens[0] == 0)
+        done.extend(asm.feed(res))
+
+    drive(torch, rx, host, sched, each)
+    # the 10 s burst at 300 baud stayed open across many pushes, zero-length ones among them
+    assert open_pushes >= 50 and idle_open_pushes >= 3
+    for c, ch in enumerate(chans):
+        assert [b[1:] for b in done if b[0] == c] == [(w[0], w[1], w[3]) for w in ch["want"]], c
+        assert ch["want"], c
+    assert asm.pending() == {}
+    rx.close()
+
+
+# ------------------------------------------------------------------------------------------ 3. clamping and defaults
+
+@functools.lru_cache(maxsize=None)
+def two_segments():
+    """A capture whose first burst is cut, at a multiple of T, into two segments."""
+    rng = np.random.default_rng(31)
+    cap = capture_of(rng, 40, [b"first segment", b"second one"], sigma=1500.0, training=0.1)
+    cap = np.concatenate([cap, np.zeros(-len(cap) % T, np.int16)])
+    s, n = O.gate_stream(cap, 18000, 14000, 16)[0][0]
+    cut = (s + n // 2) // T * T
+    assert s + BLOCK <= cut < s + n - BLOCK
+    return cap, cut
+
+
+def spans(rows):
+    return [(g["start"], g["len"], g["flags"]) for g in rows]
+
+
+@pytest.mark.parametrize("kind", ["stored", "stream"])
+def test_clamped_lengths_and_the_defaults(torch_cuda, kind):
+    torch = torch_cuda
+    cap, cut = two_segments()
+    seg = [oracle_bursts(cap[:cut], 18000, 14000), oracle_bursts(cap[cut:], 18000, 14000)]
+    assert seg[0][-1][2] == _native.LIVE_OPEN_END and seg[1]
+    chans = [dict(bf=40, a_start=18000, a_end=14000)] * 4
+    dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(cap, (4, len(cap))))).to(DEV)
+    # lengths of -5 and T + 100 behave as 0 and T; `lengths` with flush=True ends every stream
+    rx = receiver(chans, kind)
+    got = [[] for _ in range(4)]
+    lens = [-5, T + 100, T, 0]
+    for p in range(0, len(cap), T):
+        last = p + T in (cut, len(cap))
+        collect(rx.push(dev[:, p: p + T], lengths=lens if p % (2 * T) else torch.tensor(lens, dtype=torch.int32,
+                                                                                         device=DEV), flush=last), got)
+    assert got[0] == [] and got[3] == []
+    for c in (1, 2):
+        assert spans(got[c]) == seg[0] + seg[1], c
+    assert got[1] == got[2]
+    rx.close()
+    # lengths=None with a mask flush: channels 0 and 2 end their streams at the cut, 1 and 3 go on
+    rx = receiver(chans, kind)
+    got = [[] for _ in range(4)]
+    mask = np.array([1, 0, 1, 0], np.uint8)
+    for p in range(0, len(cap), T):
+        fl = mask if p + T == cut else (torch.ones(4, dtype=torch.bool, device=DEV) if p + T == len(cap) else False)
+        collect(rx.push(dev[:, p: p + T], flush=fl), got)
+    whole = oracle_bursts(cap, 18000, 14000)
+    for c in range(4):
+        assert spans(got[c]) == (seg[0] + seg[1] if mask[c] else whole), c
+    # flush(mask=) on an empty chunk reports nothing more: every stream has ended
+    assert not rx.flush(mask=np.ones(4, bool)).n_closed.cpu().numpy().any()
+    rx.close()
+
+
+# ------------------------------------------------------------------------------------- 4. flush of one channel only
+
+@functools.lru_cache(maxsize=None)
+def one_flush_plan():
+    """Four 1200-baud channels; A (channel 0) is flushed by the mask at `cut`, inside its first burst, while B
+    (channel 1) records too: (captures, cut, start of A's burst, schedule, push buffers)."""
+    rng = np.random.default_rng(41)
+    caps = [capture_of(np.random.default_rng(50 + c), 40, [b"interrupted burst", b"after"], sigma=1500.0, training=0.1)
+            for c in range(4)]
+    (s, n) = O.gate_stream(caps[0], 18000, 14000, 16)[0][0]
+    (sb, nb) = O.gate_stream(caps[1], 18000, 14000, 16)[0][0]
+    cut = s + n // 2 + 123                                      # A's stream ends here, inside a block of its burst
+    assert s + BLOCK < cut < s + n - BLOCK and sb + BLOCK < cut < sb + nb - BLOCK        # B records there too
+    # A (channel 0) and B (channel 1) take the same lengths up to the cut, then each its own; 2 and 3 their own
+    totals = [len(c) for c in caps]
+    sched, pos, flushed_a = [], [0] * 4, False
+    while any(pos[c] < totals[c] for c in range(4)):
+        lens, mask = np.zeros(4, np.int32), np.zeros(4, np.uint8)
+        for c in range(4):
+            k = int(rng.choice(LENGTHS))
+            if c == 1 and not flushed_a:
+                k = int(lens[0])
+            if c == 0 and not flushed_a:
+                k = min(k, cut - pos[0])
+            lens[c] = min(k, totals[c] - pos[c])
+            pos[c] += int(lens[c])
+        if not flushed_a and pos[0] == cut:
+            mask[0], flushed_a = 1, True
+        sched.append((lens, mask))
+    sched.append((np.zeros(4, np.int32), np.ones(4, np.uint8)))             # the end of every stream
+    assert any(m[0] and x[0] > 0 and x[1] == x[0] for x, m in sched)
+    return caps, cut, s, sched, push_buffers(caps, sched)
+
+
+@pytest.mark.parametrize("kind", ["stored", "stream"])
+def test_a_mask_flushes_one_recording_channel_and_leaves_the_other(torch_cuda, kind):
+    torch = torch_cuda
+    caps, cut, s, sched, host = one_flush_plan()
+    chans = [dict(bf=40, a_start=18000, a_end=14000)] * 4
+    rx = receiver(chans, kind)
+    got = drive(torch, rx, host, sched)
+    first, second = oracle_bursts(caps[0][:cut], 18000, 14000), oracle_bursts(caps[0][cut:], 18000, 14000)
+    assert first[-1] == (s, (cut - s) // BLOCK * BLOCK, _native.LIVE_OPEN_END) and second
+    assert spans(got[0]) == first + second                      # the second segment counted from 0 of its new stream
+    for c in (1, 2, 3):
+        assert spans(got[c]) == oracle_bursts(caps[c], 18000, 14000), c
+    for c in (1, 2, 3):
+        assert [g["bytes"] for g in got[c]] == [w[3] for w in expected(caps[c], 40)], c
+    assert got[1][0]["bytes"] == b"interrupted burst"
+    rx.close()
+
+
+# -------------------------------------------------------------------------------------- 5. one graph, many tick sizes
+
+@pytest.mark.parametrize("kind,chan_set", [("stored", "uniform"), ("stream", "mixed")])
+def test_one_captured_graph_serves_ticks_of_any_size(torch_cuda, kind, chan_set):
+    torch = torch_cuda
+    chans, sched, host = plan(chan_set)
+    n = len(chans)
+    assert len({int(x) for lens, _ in sched for x in lens}) >= 6             # the per-tick sizes vary
+    rx = receiver(chans, kind)
+    dev = torch.from_numpy(host).to(DEV)
+    buf = torch.zeros((n, T), dtype=torch.int16, device=DEV)
+    lens_dev = torch.zeros(n, dtype=torch.int32, device=DEV)
+    mask_dev = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    res = rx.alloc_result()
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            rx.push(buf, out=res, lengths=lens_dev, flush=mask_dev)
+    torch.cuda.synchronize()
+    got = [[] for _ in range(n)]
+    for p, (lens, mask) in enumerate(sched):
+        buf.copy_(dev[p])
+        lens_dev.copy_(torch.from_numpy(lens))
+        mask_dev.copy_(torch.from_numpy(mask))
+        graph.replay()
+        collect(res, got)
+    compared = check_against_oracle(chans, got)
+    assert check_demod_against_batch(torch, chans, got, rx.out_stride) == sum(compared)
+    rx.close()
+
+
+# ------------------------------------------------------------------------------------------------- 6. the transmitter
+
+TX_LENGTHS = (0, 1, 5, 2047, 2048, 2049, 4000, 4095, 4096, 4097, 6143, 6144)
+TX_KINDS = {"mixed": ([1200, 300, 2400, 6000, 600, 1200, 300, 2400], [0.1, 0.05, 0.1, 0.02, 0.1, 0.3, 0.1, 0.05]),
+            "uniform_1200": ([1200] * 8, [0.1] * 8), "uniform_6000": ([6000] * 8, [0.02] * 8)}
+
+
+@pytest.mark.parametrize("kind", list(TX_KINDS))
+def test_ragged_pulls_play_every_message_at_its_start_and_write_nothing_beyond_a_length(torch_cuda, kind):
+    torch = torch_cuda
+    bauds, times = TX_KINDS[kind]
+    n = len(bauds)
+    rng = np.random.default_rng(61)
+    tx = LiveTransmitter(n, bauds, times, queue_depth=4, max_payload_len=24, device=DEV)
+    assert (tx.bit_frames is None) == (kind == "mixed")
+    refs = [afskmodem.Transmitter(b, t) for b, t in zip(bauds, times)]
+    msgs = []                                                   # (channel, start, n_samples, payload)
+
+    def submit(chs):
+        pays = [bytes(rng.integers(0, 256, int(rng.integers(0, 25)), dtype=np.uint8)) for _ in chs]
+        status, start, ns = tx.submit(chs, pays).cpu()
+        assert (status == _native.LIVE_TX_QUEUED).all()
+        for c, p, s, k in zip(chs, pays, start.tolist(), ns.tolist()):
+            assert k == len(refs[c].wav_samples(p))
+            msgs.append((c, s, k, p))
+
+    submit([0, 1, 2, 3, 3, 4, 5, 6, 7, 7])
+    buf = torch.empty((n, T), dtype=torch.int16, device=DEV)
+    streams = [[] for _ in range(n)]
+    pos = np.zeros(n, np.int64)
+    tick = 0
+    while True:
+        ends = np.array([max(s + k for c, s, k, _ in msgs if c == ch) for ch in range(n)])
+        if (pos >= ends).all() and tick > 12:
+            break
+        assert tick < 400
+        if tick == 6:
+            submit([0, 2, 2, 5])                                # on busy and on idle channels, part-way through
+        lens = rng.choice(TX_LENGTHS, n).astype(np.int32)
+        if tick == 3:
+            lens[:2] = (-5, T + 100)                            # clamped to 0 and T
+        want_len = np.clip(lens, 0, T)
+        buf.fill_(SENTINEL)
+        out = tx.pull(T, out=buf, lengths=torch.from_numpy(lens).to(DEV) if tick % 2 else lens.tolist())
+        rows = out.cpu().numpy()
+        pos += want_len
+        pending = tx.pending.cpu().numpy()
+        for c in range(n):
+            k = int(want_len[c])
+            streams[c].append(rows[c, :k].copy())
+            assert (rows[c, k:] == SENTINEL).all(), (tick, c, k)      # nothing written from len_c on
+            assert pending[c] == sum(1 for ch, s, ns, _ in msgs if ch == c and s + ns > pos[c]), (tick, c)
+        tick += 1
+    assert len({int(p) for p in pos}) > 1
+    for c in range(n):
+        have = np.concatenate(streams[c])
+        want = np.zeros(len(have), np.int16)
+        for ch, s, k, p in msgs:
+            if ch == c:
+                want[s: s + k] = refs[c].wav_samples(p)
+        assert np.array_equal(have, want), c
+    assert not tx.pending.cpu().numpy().any()
+    tx.close()
+
+
+# -------------------------------------------------------------------------------------------------- 7. ragged loopback
+
+def test_ragged_loopback_pull_into_push_as_one_graph(torch_cuda):
+    torch = torch_cuda
+    rng = np.random.default_rng(71)
+    bauds = [1200, 300, 2400, 6000, 600, 1200, 300, 2400]
+    n = len(bauds)
+    tx = LiveTransmitter(n, bauds, 0.1, max_payload_len=32, device=DEV)
+    rx = LiveReceiver(n, [48000 // b for b in bauds], max_burst_len=None, max_payload_len=32, max_chunk_len=T,
+                      device=DEV)
+    buf = torch.zeros((n, T), dtype=torch.int16, device=DEV)
+    poison = torch.from_numpy(POISON).to(DEV)
+    lens_dev = torch.full((n,), T, dtype=torch.int32, device=DEV)
+    res = rx.alloc_result()
+    got = []
+    # one silent tick (the gate discards a stream's first block), then a message on every channel
+    tx.pull(T, out=buf, lengths=lens_dev)
+    rx.push(buf, out=res, lengths=lens_dev)
+    pays = [bytes(rng.integers(0, 256, int(rng.integers(1, 33)), dtype=np.uint8)) for _ in range(n)]
+    status, start, ns = tx.submit(np.arange(n), pays).cpu()
+    assert (status == _native.LIVE_TX_QUEUED).all() and (start == T).all()
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            tx.pull(T, out=buf, lengths=lens_dev)
+            rx.push(buf, out=res, lengths=lens_dev)
+    torch.cuda.synchronize()
+    pos = np.full(n, T, np.int64)
+    ends = start + ns + 2 * BLOCK
+    ticks = 0
+    while (pos < ends).any():
+        lens = rng.choice([0, 1, 2047, 2049, 4000, T, T], n).astype(np.int32)        # a new l every tick
+        buf.copy_(poison.expand(n, T))                          # what the pull does not write must not be read
+        lens_dev.copy_(torch.from_numpy(lens))
+        graph.replay()
+        got += [(c, p) for c, _, _, p in res.bursts()]
+        pos += lens
+        ticks += 1
+        assert ticks < 400
+    got += [(c, p) for c, _, _, p in rx.flush().bursts()]
+    assert sorted(got) == [(c, pays[c]) for c in range(n)]
+    assert len({int(p) for p in pos}) > 1
+    tx.close()
+    rx.close()

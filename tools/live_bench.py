@@ -5,11 +5,15 @@
                                [--no-verify] [--kernel-stats STATS_CSV]
     python tools/live_bench.py --stream [--stream-cases 65536x8192@1200,...,16384x8192@long] [--json OUT]
     python tools/live_bench.py --tap [--parent PARENT.so] [--tap-cases 65536x8192@1200,...] [--json OUT] [--txt OUT]
+    python tools/live_bench.py --ragged [--parent PARENT.so] [--ragged-shape 65536x8192] [--json OUT] [--txt OUT]
 
 --stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
 (stream_ab below).  --tap times the streaming receiver's push with and without the payload tap (progressive=True) on the
 same pushes, alternately, and -- with --parent, a libafsk_amd.so of the parent commit -- against that build's
 streaming push in the same run (tap_ab below).
+
+--ragged times the ragged push and pull (lengths= per channel; ragged_ab below) of the stored, the streaming and the
+tapped receiver and of the transmitter against the plain calls, and the plain calls against the parent build's.
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -341,6 +345,135 @@ def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
     return rec
 
 
+def ragged_windows(torch, samples, lens):
+    """The pushes of a ragged schedule as buffers: [P, n, T] where row c of push p holds channel c's next lens[p, c]
+    samples of `samples` (and what follows them in the stream beyond: never read)."""
+    n, total = samples.shape
+    P, T = lens.shape[0], samples.shape[1] // lens.shape[0]
+    pos = torch.cumsum(lens.long(), 0) - lens.long()                     # [P, n] first sample of every push
+    col = torch.arange(T, device=samples.device)
+    return torch.stack([torch.gather(samples, 1, torch.clamp(pos[p][:, None] + col[None, :], max=total - 1))
+                        for p in range(P)])
+
+
+def ragged_ab(torch, n, T, seconds, reps, seed, parent):
+    """Per object -- the stored, the streaming and the tapped receiver, the transmitter -- at 1200 baud, every push or
+    pull replayed from a captured graph with HIP events around each replay, the variants taking turns pass by pass
+    after one warm-up pass each (measuring-on-mi355x, section 5 "Steady state and noise": warm up, compare two
+    versions in the same call, alternating them, and measure the spread of a repeat before trusting a difference;
+    section 4: call times from device events):
+      parent, parent_again  the plain call of the parent build, twice: the spread of that repeat is the margin
+      plain                 the plain call of this build (must stay inside the margin of the parent's)
+      ragged_full           the ragged call with every length T: what the ragged form itself costs over `plain`
+      ragged_half           the ragged call with lengths drawn uniformly from [T / 2, T] per channel and push: us per
+                            call and ns per sample actually taken
+    The receivers push stream_ab's synthetic workload (ragged_half: each channel's own consecutive samples, gathered
+    per push); the transmitter pulls one 24-byte message per channel, queued before every pass."""
+    from afskmodem_amd.live import LiveTransmitter
+    samples, n_push = stream_workload(torch, n, T, seconds, BAUD, seed, False)
+    rng = np.random.default_rng(seed)
+    full = torch.full((n_push, n), T, dtype=torch.int32, device="cuda")
+    half = torch.from_numpy(rng.integers(T // 2, T + 1, (n_push, n)).astype(np.int32)).to("cuda")
+    half_buf = ragged_windows(torch, samples, half)
+    side = torch.cuda.Stream()
+
+    def capture(fn):
+        graphs = []
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for p in range(n_push):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    fn(p)
+                graphs.append(g)
+        torch.cuda.synchronize()
+        return graphs
+
+    def timed(graphs):
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in graphs]
+        for g, (a, b) in zip(graphs, ev):
+            a.record()
+            g.replay()
+            b.record()
+        torch.cuda.synchronize()
+        return float(np.mean([a.elapsed_time(b) * 1e3 for a, b in ev]))
+
+    window = lambda p: samples[:, p * T: (p + 1) * T]  # noqa: E731
+    variants = ([("parent", parent, None), ("parent_again", parent, None)] if parent is not None else []) + [
+        ("plain", None, None), ("ragged_full", None, full), ("ragged_half", None, half)]
+    rec = dict(shape=f"{n}x{T}", baud=BAUD, pushes=n_push, reps=reps, samples_per_call=dict(
+        plain=n * T, ragged_full=n * T, ragged_half=int(half.sum()) // n_push), objects={})
+    pay = [bytes(rng.integers(0, 256, 24, dtype=np.uint8)) for _ in range(n)]
+    for obj, kw in (("stored", dict(max_burst_len=48000)), ("streaming", dict(max_burst_len=None, max_payload_len=256)),
+                    ("tapped", dict(max_burst_len=None, max_payload_len=256, progressive=True)), ("transmitter", None)):
+        runs = []
+        for name, lib, lens in variants:
+            with using(lib):
+                if obj == "transmitter":
+                    o = LiveTransmitter(n, BAUD, 0.1, max_payload_len=24)
+                    buf = torch.zeros((n, T), dtype=torch.int16, device="cuda")
+                    graphs = capture((lambda p: o.pull(T, out=buf)) if lens is None else
+                                     (lambda p: o.pull(T, out=buf, lengths=lens[p])))
+                    keep = buf
+                else:
+                    o = LiveReceiver(n, BF, max_chunk_len=T, **kw)
+                    out = o.alloc_result()
+                    src = half_buf if name == "ragged_half" else None
+                    graphs = capture((lambda p: o.push(window(p), out=out)) if lens is None else
+                                     (lambda p: o.push(window(p) if src is None else src[p], out=out, lengths=lens[p])))
+                    keep = out
+            runs.append(dict(name=name, lib=lib, o=o, graphs=graphs, keep=keep, passes=[]))
+        for r in range(reps + 1):
+            for v in runs:
+                with using(v["lib"]):
+                    if obj == "transmitter":
+                        v["o"].reset()
+                        v["o"].submit(np.arange(n), pay)
+                    else:
+                        v["o"].flush()
+                    t = timed(v["graphs"])
+                if r:
+                    v["passes"].append(t)
+        cells = {}
+        for v in runs:
+            m = float(np.mean(v["passes"]))
+            cells[v["name"]] = dict(us_mean=round(m, 2), us_passes=[round(x, 2) for x in v["passes"]],
+                                    spread=round((max(v["passes"]) - min(v["passes"])) / m, 4))
+        if parent is not None:
+            a, b = cells["parent"]["us_mean"], cells["parent_again"]["us_mean"]
+            margin = max(abs(a - b) / min(a, b), cells["parent"]["spread"], cells["parent_again"]["spread"])
+            cells["margin"] = round(margin, 4)
+            cells["plain_over_parent"] = round(cells["plain"]["us_mean"] / (0.5 * (a + b)), 4)
+            cells["plain_inside_margin"] = bool(cells["plain"]["us_mean"] <= max(a, b) * (1 + margin))
+        cells["ragged_full_over_plain"] = round(cells["ragged_full"]["us_mean"] / cells["plain"]["us_mean"], 4)
+        cells["ragged_half_over_plain"] = round(cells["ragged_half"]["us_mean"] / cells["plain"]["us_mean"], 4)
+        for k in ("plain", "ragged_full", "ragged_half"):
+            cells[k]["ns_per_sample_taken"] = round(cells[k]["us_mean"] * 1e3 / rec["samples_per_call"][k], 6)
+        rec["objects"][obj] = cells
+        torch.cuda.synchronize()
+        for v in runs:
+            del v["graphs"], v["keep"]
+            with using(v["lib"]):
+                v["o"].close()
+        torch.cuda.empty_cache()
+    return rec
+
+
+def ragged_lines(rec):
+    out = [f"{rec['shape']} @{rec['baud']}  {rec['pushes']} calls per pass, {rec['reps']} passes; us per call (mean), "
+           f"ns per sample taken"]
+    for obj, c in rec["objects"].items():
+        cols = [f"{k} {c[k]['us_mean']:9.1f} us" for k in ("parent", "parent_again", "plain") if k in c]
+        cols += [f"{k} {c[k]['us_mean']:9.1f} us {c[k]['ns_per_sample_taken']:.5f} ns/sample"
+                 for k in ("ragged_full", "ragged_half")]
+        tail = f"full/plain x{c['ragged_full_over_plain']:.4f}  half/plain x{c['ragged_half_over_plain']:.4f}"
+        if "margin" in c:
+            tail += (f"  plain/parent x{c['plain_over_parent']:.4f} (margin {100 * c['margin']:.2f} %: "
+                     f"{'inside' if c['plain_inside_margin'] else 'OUTSIDE'})")
+        out.append(f"{obj:12s}" + "  ".join(cols) + "   " + tail)
+    return out
+
+
 def tap_line(rec):
     head = f"{rec['shape']:>11s} @{rec['baud']:<5d} {rec['workload']:19s}"
     cells = [f"{k} {v['us_mean']:8.1f} us x{v['over_baseline']:.4f} (spread {100 * v['spread']:.2f} %)"
@@ -367,8 +500,11 @@ def main():
     ap.add_argument("--tap", action="store_true",
                     help="the streaming push with and without the payload tap, alternating, per --tap-cases entry")
     ap.add_argument("--tap-cases", default="65536x8192@1200,65536x2048@1200,16384x8192@long")
-    ap.add_argument("--parent", help="with --tap: libafsk_amd.so of the parent commit, timed in the same run")
-    ap.add_argument("--txt", help="with --tap: the table as text")
+    ap.add_argument("--parent", help="with --tap / --ragged: libafsk_amd.so of the parent commit, timed in the same run")
+    ap.add_argument("--txt", help="with --tap / --ragged: the table as text")
+    ap.add_argument("--ragged", action="store_true",
+                    help="the ragged push and pull against the plain ones, and the plain ones against --parent")
+    ap.add_argument("--ragged-shape", default="65536x8192")
     args = ap.parse_args()
     if args.kernel_stats:
         rows = list(csv.DictReader(open(args.kernel_stats)))
@@ -390,6 +526,19 @@ def main():
         return
     import torch
     res = []
+    if args.ragged:
+        n, T = (int(x) for x in args.ragged_shape.split("x"))
+        rec = ragged_ab(torch, n, T, args.seconds, args.reps, args.seed, load_build(args.parent) if args.parent else None)
+        lines = ragged_lines(rec)
+        print(json.dumps(rec))
+        print("\n".join(lines))
+        for path, text in ((args.json, json.dumps(dict(tool="tools/live_bench.py --ragged", parent=bool(args.parent),
+                                                       seconds=args.seconds, results=[rec]), indent=1)),
+                           (args.txt, "\n".join(lines) + "\n")):
+            if path:
+                with open(path, "w") as f:
+                    f.write(text)
+        return
     if args.tap:
         parent = load_build(args.parent) if args.parent else None
         lines = []
