@@ -23,7 +23,7 @@ typedef uint32_t vec16 __attribute__((ext_vector_type(4), aligned(2)));
 // sum |x| over the 2048 samples one wavefront holds as v[4] (lane l: samples 512 j + 8 l ... + 7 of load j):
 // v_sad_u16 accumulation (ref:94-98), then the wave sum with DPP (row_shr 1/2/4/8, row_bcast:15 / :31); lane 63
 // ends up with the total (__shfl_xor would be six ds_bpermute round trips).  amp = total >> 11 = int(sum / 2048).
-// Shared by block_amp_kernel and live_gate_kernel (afsk_live.hip).
+// Shared by block_amp_kernel and live_gate_walk (afsk_live.hip).
 __device__ __forceinline__ int block_abs_sum(const vec16 (&v)[4]) {
     uint32_t acc = 0;
 #pragma unroll
@@ -137,15 +137,14 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // unit: build.sh compiles a fixed list of files, and the hashed afsk_demod* sources and afsk_capi.hip (which the CPU
 // stub-runtime test builds without device code) must stay as they are.
 #include "afsk_split.hip"
-// The live receiver (afsk_live_*: stateful chunked gate + demodulation of the bursts a push closes), for the same
-// reason.
+// The live receiver (afsk_live_*: stateful chunked gate + demodulation of the bursts a push closes; the gate walk and
+// the stored sink), for the same reason.
 #include "afsk_live.hip"
-// The streaming live receiver (afsk_live_stream_layout / afsk_live_create_stream: the same gate walk, bursts
-// demodulated while they are gated), for the same reason.
+// The streaming live receiver (afsk_live_stream_layout / afsk_live_create_stream: the streaming sink -- bursts
+// demodulated while they are gated -- and its tapped instantiation), for the same reason.
 #include "afsk_live_stream.hip"
-// The streaming receiver's payload tap (afsk_live_tap_layout / afsk_live_create_stream_tap / afsk_live_push_tap: the
-// tapped instantiations of the streaming kernels), for the same reason.
+// The streaming receiver's payload tap (afsk_live_tap_layout / afsk_live_create_stream_tap), for the same reason.
 #include "afsk_live_tap.hip"
-// The ragged push of the live receivers (afsk_live_push_ragged: a sample count and a flush bit per channel, the ragged
-// instantiations of the six gate kernels), for the same reason.
-#include "afsk_live_ragged.hip"
+// Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged: the one kernel template over the
+// three sinks, its table of instantiations and the one host path), last: it needs all three sinks.
+#include "afsk_live_push.hip"

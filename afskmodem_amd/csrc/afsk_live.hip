@@ -1,11 +1,13 @@
 // afsk_live.hip -- the live receiver (afsk_live_*, include/afsk_amd.h): Receiver.receive (afskmodem.py:299-319,
 // 402-417) for many channels fed chunk by chunk, with nothing but device state carried from one push to the next.
 //
-// A push is two launches, in order on the caller's stream (a captured graph of them is a linear chain):
-//   live_gate_kernel     one wave per channel: walks the push's whole 2048-sample blocks through gate_scan_kernel's
-//                        state machine (discard one block, wait for amp > amp_start, record through the first
-//                        amp < amp_end), stores recorded blocks from registers into the channel's record row, and
-//                        lays every burst the push closes out as a fixed demodulator slot (row offset + length).
+// A push (afsk_live_push.hip: the one kernel template and host path of every receiver's push) is two launches, in
+// order on the caller's stream (a captured graph of them is a linear chain):
+//   live_push_kernel     its LiveStoreSink cells, one wave per channel: walks the push's whole 2048-sample blocks
+//                        through gate_scan_kernel's state machine (discard one block, wait for amp > amp_start,
+//                        record through the first amp < amp_end), stores recorded blocks from registers into the
+//                        channel's record row, and lays every burst the push closes out as a fixed demodulator slot
+//                        (row offset + length).
 //   demod_uniform_kernel afsk::launch_demod_uniform over n_channels * slots slots, reading the bursts in place
 //                        (length 0 = unused or overflowed slot: status TOO_SHORT, nothing read).
 //
@@ -15,7 +17,7 @@
 // the measurement against the per-stream kernel in slot order).
 //
 // A receiver with a threshold pair per channel (afsk_live_create_thresholds) keeps amp_start and amp_end as int32 [n]
-// behind the layout's bytes; its gate (live_gate_thr_kernel, the same walk) takes a channel's pair from there.  The
+// behind the layout's bytes; its gate (the PER_CHANNEL cells, the same walk) takes a channel's pair from there.  The
 // demod kernels take one amp_end per launch, so such a receiver launches them once per distinct amp_end -- a squelch
 // class, at most AFSK_LIVE_MAX_SQUELCH_CLASSES -- each over the list of that class's slots (DemodArgs::stream_index):
 // 1 + classes launches, still nothing on the host in between.  One class (distinct amp_start only) keeps the second
@@ -33,6 +35,7 @@
 #include <algorithm>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/afsk_amd.h"
@@ -60,6 +63,12 @@ struct LiveLayout {
     int64_t slots = 0;          // slots per channel and push: 1 + k_blocks / 3
     int64_t row_len = 0;        // samples per record row: (cap_blocks + k_blocks) * 2048
     int64_t o_carry = 0, o_slot_off = 0, o_slot_len = 0, o_rows = 0, bytes = 0;
+};
+
+// the streaming receiver's (afsk_live_stream.hip: live_stream_layout); here because afsk_live keeps one
+struct LiveStreamLayout {
+    int64_t n = 0, slots = 0, max_payload = 0;
+    int64_t o_carry = 0, o_demod = 0, o_bf = 0, o_win = 0, o_pay = 0, bytes = 0;
 };
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
@@ -136,6 +145,7 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 // machine with the next block's load in flight, and hands every event to its sink -- the stored receiver's
 // (LiveStoreSink: record rows and demodulator slots) or the streaming one's (afsk_live_stream.hip: demodulation as
 // the blocks arrive).  A sink has:
+//   Args, Sink(const Args&), gate(const Args&)  the kernel argument it is built from, and the LiveArgs inside that
 //   init(a, c, amp_end)           the channel's state is loaded (amp_end: the channel's squelch threshold)
 //   begin(a, lane, st)            before the first block
 //   overflowed(a, st)             the burst being reported is longer than the sink keeps
@@ -149,10 +159,15 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 // PER_CHANNEL: the thresholds are channel c's entries of thr_start / thr_end (int32 [n] in the receiver's state) instead
 // of a.amp_start / a.amp_end.  One wave walks one channel, so they are wave-uniform: two scalar loads before the block
 // loop, the values in SGPRs for the whole walk.  The instantiations without the flag are the code they were.
-// RAGGED (afsk_live_ragged.hip): the channel takes len = clamp(chunk_lens[c], 0, a.chunk_len) samples of its row (a null
+// RAGGED (afsk_live_push_ragged): the channel takes len = clamp(chunk_lens[c], 0, a.chunk_len) samples of its row (a null
 // chunk_lens: a.chunk_len) and flushes when a.flush or flush_mask[c] is set (a null flush_mask: a.flush alone) -- two
 // more wave-uniform scalar loads, walked with in place of a.chunk_len and a.flush.  Nothing at or beyond column len
-// of the row is read.  The instantiations without the flag are the code they were.
+// of the row is read: the push walks nblk = (cl + len) / 2048 whole blocks (cl: carried samples), block b >= 1 is
+// columns [b * 2048 - cl, + 2048) and ends at nblk * 2048 - cl <= len, block 0 of a push with a carry takes its columns
+// [0, 2048 - cl) sample by sample (2048 - cl <= len as nblk >= 1), and the carry copy takes columns [nblk * 2048 - cl,
+// len).  A channel with len 0 and no flush walks no block, copies nothing, and stores the state it loaded.  The sinks
+// never see either value, so plain and ragged pushes of one receiver may alternate.  The instantiations without the
+// flag are the code they were.
 template <bool PER_CHANNEL = false, bool RAGGED = false, class Sink>
 __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, const int32_t* thr_start = nullptr,
                                                const int32_t* thr_end = nullptr, const int32_t* chunk_lens = nullptr,
@@ -271,9 +286,13 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
 // The stored receiver's sink: recorded blocks go from registers into the channel's record row, and every burst the
 // push closes becomes a demodulator slot (row offset + length) for the push's second launch.
 struct LiveStoreSink {
+    using Args = LiveArgs;      // what live_push_kernel (afsk_live_push.hip) hands the sink, and the gate's part of it
     int16_t* row;
     int64_t wp;                 // row offset of the next stored block
     int64_t brow;               // row offset of the open burst
+
+    __device__ __forceinline__ explicit LiveStoreSink(const Args&) {}
+    static __device__ __forceinline__ const LiveArgs& gate(const Args& a) { return a; }
 
     // the open burst's stored prefix goes to the row front (it opened in the previous push behind closed bursts,
     // so it is at most one push of blocks, and head >= 2048: copying block by block front to back never overwrites
@@ -317,17 +336,6 @@ struct LiveStoreSink {
         a.slot_len[slot0 + i] = 0;
     }
 };
-
-__global__ __launch_bounds__(256) void live_gate_kernel(LiveArgs a) {
-    LiveStoreSink sk;
-    live_gate_walk(a, sk);
-}
-
-// the stored receiver with a threshold pair per channel (afsk_live_create_thresholds)
-__global__ __launch_bounds__(256) void live_gate_thr_kernel(LiveArgs a, const int32_t* thr_start, const int32_t* thr_end) {
-    LiveStoreSink sk;
-    live_gate_walk<true>(a, sk, thr_start, thr_end);
-}
 
 __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const uint8_t* mask, int32_t n) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -400,9 +408,10 @@ struct SquelchClasses {
 struct afsk_live {
     afsk::DeviceState state;            // the layout's L.bytes (+ the per-channel part of a thresholds receiver)
     afsk::LiveLayout L;
+    afsk::LiveStreamLayout SL;          // a streaming receiver's layout (L then holds n and slots only)
     int32_t bit_frames = 0, amp_start = 0, amp_end = 0, max_chunk_len = 0;   // (a mixed receiver: bit_frames 0)
     afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
-    int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip; L: n and slots only)
+    int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip)
     int32_t tap_cap = 0;                // > 0: a tapped streaming receiver (afsk_live_tap.hip): bytes per tap row
     // a threshold pair per channel (afsk_live_create_thresholds / _stream_thresholds): amp_start int32 [n] at o_thr,
     // amp_end int32 [n] behind it; a stored receiver of two or more squelch classes also the classes' slot lists
@@ -418,10 +427,7 @@ struct afsk_live {
 };
 
 namespace afsk {
-// the streaming receiver's push and reset (afsk_live_stream.hip), after afsk_live_push's / afsk_live_reset's checks
-int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
-                     int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                     const DemodOutputs& o, hipStream_t stream);
+// the streaming receiver's reset (afsk_live_stream.hip), after afsk_live_reset's checks
 int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_t stream);
 
 // What a create entry asks for, after its own argument checks.  bit_frames: [n] when `mixed`, else bit_frames[0] for
@@ -444,48 +450,6 @@ int live_stream_state(const LiveSpec& sp, afsk_live& lv);
 }  // namespace afsk
 
 namespace afsk {
-
-// The checks afsk_live_push and afsk_live_push_ragged share, after the null-handle check and before any device work.
-int live_push_checks(const afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len,
-                     const int32_t* out_n_closed, const int64_t* out_burst_start, const int32_t* out_burst_len,
-                     const int32_t* out_flags, const DemodOutputs& o) {
-    if (chunk_len < 0 || chunk_row_stride < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
-    if (chunk_len > live->max_chunk_len)
-        return fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
-    if ((chunk_len > 0 && !chunk) || !out_n_closed || !out_burst_start || !out_burst_len || !out_flags || o.missing())
-        return fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (live->max_payload_len >= 0 && o.margins)
-        return fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
-    return AFSK_OK;
-}
-
-// the stored receiver's gate arguments of a push
-void live_stored_args(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
-                      int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                      LiveArgs& g) {
-    const LiveLayout& L = live->L;
-    uint8_t* d = live->state.ptr();
-    g = LiveArgs{};
-    g.chan = reinterpret_cast<LiveChan*>(d);
-    g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
-    g.slot_off = reinterpret_cast<int64_t*>(d + L.o_slot_off);
-    g.slot_len = reinterpret_cast<int32_t*>(d + L.o_slot_len);
-    g.rows = reinterpret_cast<int16_t*>(d + L.o_rows);
-    g.chunk = chunk_len > 0 ? chunk : g.rows;        // (T = 0: never read)
-    g.chunk_stride = chunk_len > 0 ? chunk_row_stride : 0;
-    g.row_len = L.row_len;
-    g.cap = L.cap_blocks * kListenBlock;
-    g.chunk_len = chunk_len;
-    g.flush = flush != 0;
-    g.n = (int32_t)L.n;
-    g.slots = (int32_t)L.slots;
-    g.amp_start = live->amp_start;
-    g.amp_end = live->amp_end;
-    g.out_n_closed = out_n_closed;
-    g.out_burst_start = out_burst_start;
-    g.out_burst_len = out_burst_len;
-    g.out_flags = out_flags;
-}
 
 // the stored receiver's second launch (or launches, one per squelch class): the demodulator over the slots
 int live_stored_demod(afsk_live* live, const LiveArgs& g, const DemodOutputs& o, hipStream_t st) {
@@ -679,37 +643,6 @@ int afsk_live_info(const afsk_live* live, int32_t* out_n_channels, int32_t* out_
     if (out_slots) *out_slots = (int32_t)live->L.slots;
     if (out_state_bytes) *out_state_bytes = live->state.bytes + (live->plan ? 8 * live->L.n * live->L.slots : 0);
     return AFSK_OK;
-}
-
-int afsk_live_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
-                   int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                   uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes, int32_t* out_nbits,
-                   int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status, int32_t* out_corrected,
-                   int32_t* out_margins, int32_t margin_stride, void* hip_stream) {
-    const afsk::DemodOutputs o{out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame, out_status,
-                               out_corrected, out_margins, margin_stride};
-    if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
-    if (int rc = afsk::live_push_checks(live, chunk, chunk_row_stride, chunk_len, out_n_closed, out_burst_start,
-                                        out_burst_len, out_flags, o))
-        return rc;
-    if (int rc = live->state.check_current()) return rc;
-    if (live->max_payload_len >= 0)
-        return afsk::live_stream_push(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
-                                      out_burst_len, out_flags, o, (hipStream_t)hip_stream);
-    const afsk::LiveLayout& L = live->L;
-    afsk::LiveArgs g;
-    afsk::live_stored_args(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
-                           out_burst_len, out_flags, g);
-    const hipStream_t st = (hipStream_t)hip_stream;
-    if (live->per_channel)
-        hipLaunchKernelGGL(afsk::live_gate_thr_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g,
-                           live->thr_start(), live->thr_end());
-    else
-        hipLaunchKernelGGL(afsk::live_gate_kernel, dim3((uint32_t)((L.n + 3) / 4)), dim3(256), 0, st, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return afsk::hip_fail(e, live->per_channel ? "launch live_gate_thr_kernel" : "launch live_gate_kernel");
-    return afsk::live_stored_demod(live, g, o, st);
 }
 
 int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_stream) {

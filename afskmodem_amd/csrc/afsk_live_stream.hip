@@ -3,9 +3,10 @@
 // gated.  No samples of a burst are kept beyond what the next push needs, so burst length has no cap and the state per
 // channel does not depend on it.
 //
-// A push is ONE launch: live_stream_kernel runs live_gate_walk (afsk_live.hip) with LiveStreamSink.  For every block
-// the gate records into a burst, the sink writes the block from registers into the wave's two-block LDS window (burst
-// block j in half j & 1, so the window holds sample p of the burst at p & 4095) and moves the burst's demodulator on:
+// A push is ONE launch: live_push_kernel (afsk_live_push.hip) runs live_gate_walk (afsk_live.hip) with LiveStreamSink.
+// For every block the gate records into a burst, the sink writes the block from registers into the wave's two-block
+// LDS window (burst block j in half j & 1, so the window holds sample p of the burst at p & 4095) and moves the
+// burst's demodulator on:
 //   block 0        nothing more (the clock index needs the first 4096 samples)
 //   block 1        clock recovery on the window (split_clock_kernel's helpers: clock_index_is_zero /
 //                  recover_clock_index_lanes at bit_frames 40, recover_clock_index_rt otherwise)
@@ -24,12 +25,13 @@
 // StreamDemod and the payload row (bytes [0, min(nbytes, max_payload_len, out_stride)) are copied into its row).
 //
 // A receiver with a threshold pair per channel (afsk_live_create_stream_thresholds) keeps amp_start and amp_end as
-// int32 [n] behind bit_frames; live_stream_thr_kernel (the same walk and sink) gates with the channel's pair and sets
-// the sink's per-symbol squelch from the channel's amp_end -- any number of distinct pairs, still one launch.
+// int32 [n] behind bit_frames; the PER_CHANNEL cells of live_push_kernel (the same walk and sink) gate with the
+// channel's pair and set the sink's per-symbol squelch from the channel's amp_end -- any number of distinct pairs,
+// still one launch.
 //
 // A tapped receiver (afsk_live_tap.hip: afsk_live_create_stream_tap, afsk_live_push_tap) is this receiver with the same
 // state; its push runs the sink's tapped instantiation (LiveStreamSinkT<true>), which also hands out every payload
-// byte in the push that commits it.  The kernels of this file are the untapped instantiation.
+// byte in the push that commits it.
 //
 // This file is compiled as part of afsk_gate.hip's translation unit (see the #include at its end), after afsk_split.hip
 // (the demod helpers) and afsk_live.hip (the gate walk, LiveChan, LiveArgs).
@@ -53,14 +55,10 @@ constexpr int kStreamWin = 2 * kListenBlock;                  // samples in a wi
 constexpr int kStreamWinLds = 2 * kStreamWin + 128;           // LDS bytes per wave: the window + what the clock
                                                               // searches read past its end (idle lanes, ignored)
 
-struct LiveStreamLayout {
-    int64_t n = 0, slots = 0, max_payload = 0;
-    int64_t o_carry = 0, o_demod = 0, o_bf = 0, o_win = 0, o_pay = 0, bytes = 0;
-};
-
-// LiveChan [n] | carry int16 [n, 2048] | StreamDemod [n] | bit_frames int32 [n] | window int16 [n, 4096] | payload
-// uint8 [n, max_payload_len] | 256 spare bytes; every part 256-byte aligned.  `per_channel` (a threshold pair per
-// channel, afsk_live_create_stream_thresholds): the bit_frames part holds int32 [3, n] -- bit_frames, amp_start, amp_end.
+// LiveStreamLayout (defined in afsk_live.hip: afsk_live keeps the one its receiver was created with): LiveChan [n] |
+// carry int16 [n, 2048] | StreamDemod [n] | bit_frames int32 [n] | window int16 [n, 4096] | payload uint8
+// [n, max_payload_len] | 256 spare bytes; every part 256-byte aligned.  `per_channel` (a threshold pair per channel,
+// afsk_live_create_stream_thresholds): the bit_frames part holds int32 [3, n] -- bit_frames, amp_start, amp_end.
 inline int live_stream_layout(int32_t n_channels, int32_t max_payload_len, int32_t max_chunk_len, LiveStreamLayout& L,
                               bool per_channel = false) {
     if (n_channels < 1) return fail(AFSK_E_INVALID_ARG, "n_channels must be at least 1");
@@ -144,6 +142,10 @@ struct LiveTapArgs {
     int64_t* open_start;        // int64 [n]: rec_start of the burst still recording, or -1
     int32_t* open_nbytes;       // int32 [n]: its payload bytes committed so far
 };
+struct LiveStreamTapArgs {      // the tapped sink's kernel argument
+    LiveStreamArgs s;
+    LiveTapArgs t;
+};
 template <bool TAP>
 struct LiveTapState {};
 template <>
@@ -155,6 +157,7 @@ struct LiveTapState<true> {
 
 template <bool TAP>
 struct LiveStreamSinkT {
+    using Args = std::conditional_t<TAP, LiveStreamTapArgs, LiveStreamArgs>;
     const LiveStreamArgs& A;
     int16_t* lwin;              // the wave's LDS window
     StreamDemod ds;
@@ -164,6 +167,17 @@ struct LiveStreamSinkT {
     uint8_t* pay;               // the channel's payload row
     LiveTapState<TAP> tp;
 
+    static __device__ __forceinline__ const LiveStreamArgs& stream(const Args& a) {
+        if constexpr (TAP) return a.s;
+        else return a;
+    }
+    static __device__ __forceinline__ const LiveArgs& gate(const Args& a) { return stream(a).g; }
+    // the block's four windows are the sink's own LDS; a wave takes its part
+    __device__ __forceinline__ explicit LiveStreamSinkT(const Args& a) : A(stream(a)) {
+        __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kStreamWinLds];
+        lwin = reinterpret_cast<int16_t*>(lds + (threadIdx.x >> 6) * kStreamWinLds);
+        if constexpr (TAP) tp.T = a.t;
+    }
     // amp_end: the channel's squelch threshold (the per-symbol squelch of ref:375)
     __device__ __forceinline__ void init(const LiveArgs&, int c, int32_t amp_end) {
         ds = A.dm[c];
@@ -367,20 +381,6 @@ struct LiveStreamSinkT {
 };
 using LiveStreamSink = LiveStreamSinkT<false>;
 
-__global__ __launch_bounds__(256) void live_stream_kernel(LiveStreamArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kStreamWinLds];
-    LiveStreamSink sk{a, reinterpret_cast<int16_t*>(lds + (threadIdx.x >> 6) * kStreamWinLds)};
-    live_gate_walk(a.g, sk);
-}
-
-// the streaming receiver with a threshold pair per channel (afsk_live_create_stream_thresholds)
-__global__ __launch_bounds__(256) void live_stream_thr_kernel(LiveStreamArgs a, const int32_t* thr_start,
-                                                              const int32_t* thr_end) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kStreamWinLds];
-    LiveStreamSink sk{a, reinterpret_cast<int16_t*>(lds + (threadIdx.x >> 6) * kStreamWinLds)};
-    live_gate_walk<true>(a.g, sk, thr_start, thr_end);
-}
-
 __global__ __launch_bounds__(256) void live_stream_reset_kernel(LiveChan* chan, StreamDemod* dm, const uint8_t* mask,
                                                                 int32_t n) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -394,67 +394,8 @@ __global__ __launch_bounds__(256) void live_stream_reset_kernel(LiveChan* chan, 
 
 namespace afsk {
 
-// the kernel arguments of a push (live_stream_push below, live_stream_push_tap in afsk_live_tap.hip)
-int live_stream_args(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
-                     int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                     const DemodOutputs& o, LiveStreamArgs& a) {
-    LiveStreamLayout L;
-    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L, live->per_channel))
-        return rc;
-    uint8_t* d = live->state.ptr();
-    a = LiveStreamArgs{};
-    a.g.chan = reinterpret_cast<LiveChan*>(d);
-    a.g.carry = reinterpret_cast<int16_t*>(d + L.o_carry);
-    a.g.chunk = chunk_len > 0 ? chunk : a.g.carry;       // (T = 0: never read)
-    a.g.chunk_stride = chunk_len > 0 ? chunk_row_stride : 0;
-    a.g.chunk_len = chunk_len;
-    a.g.flush = flush != 0;
-    a.g.n = (int32_t)L.n;
-    a.g.slots = (int32_t)L.slots;
-    a.g.amp_start = live->amp_start;
-    a.g.amp_end = live->amp_end;
-    a.g.out_n_closed = out_n_closed;
-    a.g.out_burst_start = out_burst_start;
-    a.g.out_burst_len = out_burst_len;
-    a.g.out_flags = out_flags;
-    a.dm = reinterpret_cast<StreamDemod*>(d + L.o_demod);
-    a.bit_frames = reinterpret_cast<const int32_t*>(d + L.o_bf);
-    a.win = reinterpret_cast<int16_t*>(d + L.o_win);
-    a.pay = d + L.o_pay;
-    a.max_payload = (int32_t)L.max_payload;
-    a.out_bytes = o.bytes;
-    a.out_stride = o.stride;
-    a.out_nbytes = o.nbytes;
-    a.out_nbits = o.nbits;
-    a.out_clock_idx = o.clock_idx;
-    a.out_term_frame = o.term_frame;
-    a.out_status = o.status;
-    a.out_corrected = o.corrected;
-    return AFSK_OK;
-}
-
-int live_stream_push(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len, int32_t flush,
-                     int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
-                     const DemodOutputs& o, hipStream_t stream) {
-    LiveStreamArgs a;
-    if (int rc = live_stream_args(live, chunk, chunk_row_stride, chunk_len, flush, out_n_closed, out_burst_start,
-                                  out_burst_len, out_flags, o, a))
-        return rc;
-    const uint32_t grid = (uint32_t)((live->L.n + 3) / 4);
-    if (live->per_channel)
-        hipLaunchKernelGGL(live_stream_thr_kernel, dim3(grid), dim3(256), 0, stream, a, live->thr_start(),
-                           live->thr_end());
-    else
-        hipLaunchKernelGGL(live_stream_kernel, dim3(grid), dim3(256), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AFSK_OK
-                           : hip_fail(e, live->per_channel ? "launch live_stream_thr_kernel" : "launch live_stream_kernel");
-}
-
 int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_t stream) {
-    LiveStreamLayout L;
-    if (int rc = live_stream_layout((int32_t)live->L.n, live->max_payload_len, live->max_chunk_len, L, live->per_channel))
-        return rc;
+    const LiveStreamLayout& L = live->SL;
     uint8_t* d = live->state.ptr();
     hipLaunchKernelGGL(live_stream_reset_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<LiveChan*>(d), reinterpret_cast<StreamDemod*>(d + L.o_demod), d_mask_or_null,
@@ -465,7 +406,7 @@ int live_stream_reset(afsk_live* live, const uint8_t* d_mask_or_null, hipStream_
 
 // the streaming receiver's part of live_create (afsk_live.hip): the layout, the host fields that depend on it, the state
 int live_stream_state(const LiveSpec& sp, afsk_live& lv) {
-    LiveStreamLayout L;
+    LiveStreamLayout& L = lv.SL;
     if (int rc = live_stream_layout(sp.n_channels, sp.max_payload_len, sp.max_chunk_len, L, sp.per_channel)) return rc;
     lv.L.n = L.n;
     lv.L.slots = L.slots;

@@ -540,3 +540,72 @@ def test_ragged_loopback_pull_into_push_as_one_graph(torch_cuda):
     assert len({int(p) for p in pos}) > 1
     tx.close()
     rx.close()
+
+
+# ------------------------------------------------------------------------------- 8. every cell of the push kernel table
+
+CELL_LENGTHS = (0, 1, 2047, 2048, 2049, 6144)
+CELL_PAIRS = {False: [(18000, 14000)] * 8, True: [(18000, 14000), (18000, 14000), (12000, 8000), (12000, 8000)] * 2}
+
+
+@functools.lru_cache(maxsize=None)
+def cell_captures():
+    """Eight captures of one length (a multiple of T), 1200 and 300 baud interleaved, one message each -- about
+    thirteen thousand samples, starting in the capture's second T samples."""
+    rng = np.random.default_rng(81)
+    caps = []
+    for c in range(8):
+        bf = (40, 160)[c % 2]
+        pay = bytes(rng.integers(0, 256, 14 if bf == 40 else 5, dtype=np.uint8))
+        caps.append(capture_of(rng, bf, [pay], sigma=1500.0, training=0.1 if bf == 40 else 0.05))
+    total = -(-max(len(c) for c in caps) // T) * T
+    return tuple(np.concatenate([c, np.zeros(total - len(c), np.int16)]) for c in caps)
+
+
+@functools.lru_cache(maxsize=None)
+def cell_plan(per_channel):
+    """(channels, ragged schedule, its push buffers) at one threshold pair or two: under either, every channel holds one
+    burst, and pushed T samples at a time it opens in one push and closes two pushes later."""
+    chans = tuple(channel(cap, (40, 160)[c % 2], *CELL_PAIRS[per_channel][c]) for c, cap in enumerate(cell_captures()))
+    for ch in chans:
+        (s, n, flags, pay), = ch["want"]
+        assert flags == 0 and pay and s // T + 2 == (s + n - 1) // T, (s, n)
+    sched = schedule(np.random.default_rng(82), [len(ch["cap"]) for ch in chans], T, CELL_LENGTHS)
+    assert {int(x) for lens, _ in sched for x in lens} >= set(CELL_LENGTHS)
+    return chans, sched, push_buffers([ch["cap"] for ch in chans], sched)
+
+
+@functools.lru_cache(maxsize=None)
+def cell_decode_captures(per_channel):
+    """Receiver.decode_captures of every channel's whole capture, at the channel's rate and threshold pair."""
+    chans = cell_plan(per_channel)[0]
+    out = [None] * len(chans)
+    for key in sorted({(ch["bf"], ch["a_start"], ch["a_end"]) for ch in chans}):
+        idx = [c for c, ch in enumerate(chans) if (ch["bf"], ch["a_start"], ch["a_end"]) == key]
+        dec = afskmodem.Receiver(48000 // key[0], key[1], key[2]).decode_captures([chans[c]["cap"] for c in idx])
+        for c, d in zip(idx, dec):
+            out[c] = d
+    assert all(len(d) == 1 and d[0] for d in out)
+    return out
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["plain", "ragged"])
+@pytest.mark.parametrize("per_channel", [False, True], ids=["one_pair", "two_pairs"])
+@pytest.mark.parametrize("kind", ["stored", "stream", "tapped"])
+def test_every_cell_of_the_push_table_decodes_the_whole_capture(torch_cuda, kind, per_channel, ragged):
+    torch = torch_cuda
+    chans, sched, host = cell_plan(per_channel)
+    want = cell_decode_captures(per_channel)
+    rx = receiver(chans, kind)
+    assert rx.bit_frames is None and (rx.amp_end_threshold is None) == per_channel and rx.progressive == (kind == "tapped")
+    if ragged:
+        got = drive(torch, rx, host, sched)
+    else:                                                       # afsk_live_push / afsk_live_push_tap, T samples a push
+        dev = torch.from_numpy(np.stack([ch["cap"] for ch in chans])).to(DEV)
+        got = [[] for _ in chans]
+        for p in range(0, dev.shape[1], T):
+            collect(rx.push(dev[:, p: p + T], flush=p + T == dev.shape[1]), got)
+    for c, ch in enumerate(chans):
+        assert spans(got[c]) == oracle_bursts(ch["cap"], ch["a_start"], ch["a_end"]), c
+        assert [g["bytes"] for g in got[c]] == want[c], c
+    rx.close()

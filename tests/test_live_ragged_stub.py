@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests.live_push_cells import CELLS, push_cell
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32P = C.POINTER(C.c_int32)
@@ -34,13 +35,17 @@ def stub(tmp_path_factory):
 
 
 def launches(lib):
-    """The launches since the last call, in order: a kernel's plain name (with the bool of a one-parameter template,
-    e.g. live_tx_tile_kernel<0>), or "demod" for a call of a demod launcher."""
+    """The launches since the last call, in order: the cell (sink, per_channel, ragged) of a live_push_kernel
+    instantiation, any other kernel's plain name (with the bool of a one-parameter template, e.g.
+    live_tx_tile_kernel<0>), or "demod" for a call of a demod launcher."""
     buf = C.create_string_buffer(1 << 14)
     assert lib.afsk_stub_kernel_log(buf, len(buf), 1) <= len(buf)
     out = []
     for line in buf.value.decode().split():
         m = re.match(r"_ZN4afsk(\d+)", line)
+        if push_cell(line):
+            out.append(push_cell(line))
+            continue
         if not m:
             out.append(line)
             continue
@@ -88,35 +93,35 @@ class Buffers:
 
 
 def create(lib, kind):
-    """One receiver of each kind: (handle, plain kernel, ragged kernel, tapped)."""
+    """One receiver of each kind: (handle, the cell of its plain push, the cell of its ragged push)."""
     uniform, mixed = [40] * N, [40, 160] * (N // 2)
     one, two = [14000] * N, [14000, 9000] * (N // 2)
     h = C.c_void_p()
     s = i32([18000] * N)[1]
     if kind == "stored":
         rc = lib.afsk_live_create(N, 40, 18000, 14000, 48000, T, C.byref(h))
-        names = ("live_gate_kernel", "live_gate_ragged_kernel")
+        cell = ("stored", False)
     elif kind == "stored_thr":                                     # two squelch classes
         rc = lib.afsk_live_create_thresholds(N, i32(uniform)[1], s, i32(two)[1], 48000, T, C.byref(h))
-        names = ("live_gate_thr_kernel", "live_gate_thr_ragged_kernel")
+        cell = ("stored", True)
     elif kind == "stored_mixed":
         rc = lib.afsk_live_create_mixed(N, i32(mixed)[1], 18000, 14000, 48000, T, C.byref(h))
-        names = ("live_gate_kernel", "live_gate_ragged_kernel")
+        cell = ("stored", False)
     elif kind == "stream":
         rc = lib.afsk_live_create_stream(N, i32(mixed)[1], 18000, 14000, 64, T, C.byref(h))
-        names = ("live_stream_kernel", "live_stream_ragged_kernel")
+        cell = ("stream", False)
     elif kind == "stream_thr":
         rc = lib.afsk_live_create_stream_thresholds(N, i32(mixed)[1], s, i32(two)[1], 64, T, C.byref(h))
-        names = ("live_stream_thr_kernel", "live_stream_thr_ragged_kernel")
+        cell = ("stream", True)
     elif kind == "tap":
         rc = lib.afsk_live_create_stream_tap(N, i32(mixed)[1], s, i32(one)[1], 0, T, C.byref(h))
-        names = ("live_stream_kernel", "live_stream_ragged_kernel")
+        cell = ("stream", False)
     else:
         assert kind == "tap_thr"
         rc = lib.afsk_live_create_stream_tap(N, i32(mixed)[1], s, i32(two)[1], 0, T, C.byref(h))
-        names = ("live_stream_thr_kernel", "live_stream_thr_ragged_kernel")
+        cell = ("stream", True)
     assert rc == 0 and h
-    return h, names[0], names[1]
+    return h, cell + (False,), cell + (True,)
 
 
 KINDS = ("stored", "stored_thr", "stored_mixed", "stream", "stream_thr", "tap", "tap_thr")
@@ -145,13 +150,11 @@ def test_a_ragged_push_launches_the_ragged_kernel_and_as_many_launches_as_the_pl
     assert stub.afsk_live_push(*b.plain(h, flush=1)) == 0
     assert launches(stub) == first
     if kind.startswith("tap"):
-        tapped = plain.replace("live_stream", "live_stream_tap")
+        assert plain == ("stream", kind == "tap_thr", False)           # (untapped pushes: the streaming cells)
         assert stub.afsk_live_push_tap(*b.plain(h)[:-1], *[a.ctypes.data for a in b.tap], None) == 0
-        assert launches(stub) == [tapped]
+        assert launches(stub) == [("tap", kind == "tap_thr", False)]
         assert stub.afsk_live_push_ragged(*b.ragged(h, taps=True)) == 0
-        assert launches(stub) == [tapped.replace("_kernel", "_ragged_kernel")]
-        assert {"tap": "live_stream_tap_ragged_kernel", "tap_thr": "live_stream_tap_thr_ragged_kernel"}[kind] == \
-            tapped.replace("_kernel", "_ragged_kernel")
+        assert launches(stub) == [("tap", kind == "tap_thr", True)]
     assert stub.afsk_live_destroy(h) == 0
 
 
@@ -183,6 +186,37 @@ def test_push_ragged_argument_checks(stub, kind):
     args[1] = None                                                                         # chunk_len 0: no chunk needed
     assert stub.afsk_live_push_ragged(*args) == 0
     assert len(launches(stub)) >= 1
+    assert stub.afsk_live_destroy(h) == 0
+
+
+@pytest.fixture(scope="module")
+def cell_names():
+    return {}
+
+
+@pytest.mark.parametrize("cell", CELLS, ids=lambda c: "-".join([c[0]] + ["thr"] * c[1] + ["ragged"] * c[2]))
+def test_every_cell_of_the_push_table_is_reached_and_is_its_own_kernel(stub, cell_names, cell):
+    """Each of the twelve cells through the entry and receiver that select it: the launched kernel is the
+    instantiation the cell names, and no two cells launch one mangled name (a cell copied wrong in the table launches
+    another cell's kernel)."""
+    sink, per_channel, ragged = cell
+    h = create(stub, sink + "_thr" * per_channel)[0]
+    b = Buffers()
+    launches(stub)
+    if ragged:
+        assert stub.afsk_live_push_ragged(*b.ragged(h, taps=sink == "tap")) == 0
+    elif sink == "tap":
+        assert stub.afsk_live_push_tap(*b.plain(h)[:-1], *[a.ctypes.data for a in b.tap], None) == 0
+    else:
+        assert stub.afsk_live_push(*b.plain(h)) == 0
+    buf = C.create_string_buffer(1 << 14)
+    assert stub.afsk_stub_kernel_log(buf, len(buf), 1) <= len(buf)
+    name = buf.value.decode().split()[0]
+    assert push_cell(name) == cell
+    cell_names[cell] = name
+    assert len(set(cell_names.values())) == len(cell_names)
+    if len(cell_names) == len(CELLS):
+        assert len(set(cell_names.values())) == 12
     assert stub.afsk_live_destroy(h) == 0
 
 

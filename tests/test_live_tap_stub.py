@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests.live_push_cells import push_cell
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32P = C.POINTER(C.c_int32)
@@ -72,8 +73,7 @@ def create_tapped(lib, n=6, per_channel=False, maxp=0, chunk=8192):
 
 
 def test_tapped_push_launches_the_tapped_kernels(stub):
-    for per_channel, tapped, plain in ((False, "live_stream_tap_kernel", "live_stream_kernel"),
-                                       (True, "live_stream_tap_thr_kernel", "live_stream_thr_kernel")):
+    for per_channel in (False, True):
         h = create_tapped(stub, 6, per_channel)
         slots, nbytes = C.c_int32(), C.c_int64()
         assert stub.afsk_live_info(h, None, C.byref(slots), C.byref(nbytes)) == 0
@@ -86,11 +86,11 @@ def test_tapped_push_launches_the_tapped_kernels(stub):
         before = last_kernel(stub)[0]
         assert stub.afsk_live_push_tap(*b.push_args(h), *b.tap_args(), None) == 0
         n, name, grid = last_kernel(stub)
-        assert n == before + 1 and tapped in name and grid == 2       # ONE launch, a wave per channel
+        assert n == before + 1 and push_cell(name) == ("tap", per_channel, False) and grid == 2   # ONE launch, a wave per channel
         # afsk_live_push on a tapped receiver: accepted, the untapped kernel
         assert stub.afsk_live_push(*b.push_args(h), None) == 0
         n, name, grid = last_kernel(stub)
-        assert n == before + 2 and plain in name and "tap" not in name
+        assert n == before + 2 and push_cell(name) == ("stream", per_channel, False)
         assert stub.afsk_live_push_tap(*b.push_args(h, T=0, flush=1), *b.tap_args(), None) == 0
         assert stub.afsk_live_reset(h, None, None) == 0
         assert "live_stream_reset_kernel" in last_kernel(stub)[1]

@@ -290,14 +290,16 @@ class using:
 
 
 def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
-    """The streaming push of the parent build (`parent`, a loaded library or None), this build's untapped push and
-    this build's tapped push (payload rows of 256 and of 0 bytes) on the same pushes of stream_ab's workload: one
+    """The streaming push of the parent build (`parent`, a loaded library or None: untapped twice -- the spread of that
+    repeat is the margin -- and tapped), this build's untapped push and this build's tapped push (payload rows of 256
+    and of 0 bytes) on the same pushes of stream_ab's workload: one
     graph per column window, replayed in stream order with HIP events around each replay; the variants take turns
     pass by pass (after one warm-up pass each), so drift hits all alike.  Per variant: the mean us per push of every
     pass, their mean, and the spread (max - min) / mean of the passes."""
     samples, n_push = stream_workload(torch, n, T, seconds, baud, seed, long_messages)
     bf = 48000 // baud
-    variants = ([("parent", parent, {})] if parent is not None else []) + [
+    variants = ([("parent", parent, {}), ("parent_again", parent, {}), ("parent_tapped", parent, dict(progressive=True))]
+                if parent is not None else []) + [
         ("untapped", None, {}), ("tapped", None, dict(progressive=True)),
         ("tapped_rows0", None, dict(progressive=True, max_payload_len=0))]
     runs = []
@@ -333,6 +335,15 @@ def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
     rec["baseline"] = "parent" if "parent" in rec["variants"] else "untapped"
     for name, v in rec["variants"].items():
         v["over_baseline"] = round(v["us_mean"] / base["us_mean"], 4)
+    if parent is not None:
+        V = rec["variants"]
+        a, b = V["parent"]["us_mean"], V["parent_again"]["us_mean"]
+        margin = max(abs(a - b) / min(a, b), V["parent"]["spread"], V["parent_again"]["spread"])
+        rec["parent_spread"] = round(margin, 4)
+        rec["untapped_over_parent"] = round(V["untapped"]["us_mean"] / (0.5 * (a + b)), 4)
+        rec["untapped_inside_spread"] = bool(V["untapped"]["us_mean"] <= max(a, b) * (1 + margin))
+        rec["tapped_over_parent_tapped"] = round(V["tapped"]["us_mean"] / V["parent_tapped"]["us_mean"], 4)
+        rec["tapped_inside_spread"] = bool(V["tapped"]["us_mean"] <= V["parent_tapped"]["us_mean"] * (1 + margin))
     assert len({v["nbytes"] for v in runs}) == 1, "the variants decoded different payloads"
     assert all(v["tapped"] == v["nbytes"] for v in runs if v["tap_cap"]), "the tap byte count is not the sum of nbytes"
     torch.cuda.synchronize()
@@ -363,8 +374,10 @@ def ragged_ab(torch, n, T, seconds, reps, seed, parent):
     versions in the same call, alternating them, and measure the spread of a repeat before trusting a difference;
     section 4: call times from device events):
       parent, parent_again  the plain call of the parent build, twice: the spread of that repeat is the margin
+      parent_ragged_full    the parent build's ragged call with every length T
       plain                 the plain call of this build (must stay inside the margin of the parent's)
-      ragged_full           the ragged call with every length T: what the ragged form itself costs over `plain`
+      ragged_full           the ragged call with every length T: what the ragged form itself costs over `plain` (and
+                            must stay inside the margin of the parent's)
       ragged_half           the ragged call with lengths drawn uniformly from [T / 2, T] per channel and push: us per
                             call and ns per sample actually taken
     The receivers push stream_ab's synthetic workload (ragged_half: each channel's own consecutive samples, gathered
@@ -399,7 +412,8 @@ def ragged_ab(torch, n, T, seconds, reps, seed, parent):
         return float(np.mean([a.elapsed_time(b) * 1e3 for a, b in ev]))
 
     window = lambda p: samples[:, p * T: (p + 1) * T]  # noqa: E731
-    variants = ([("parent", parent, None), ("parent_again", parent, None)] if parent is not None else []) + [
+    variants = ([("parent", parent, None), ("parent_again", parent, None), ("parent_ragged_full", parent, full)]
+                if parent is not None else []) + [
         ("plain", None, None), ("ragged_full", None, full), ("ragged_half", None, half)]
     rec = dict(shape=f"{n}x{T}", baud=BAUD, pushes=n_push, reps=reps, samples_per_call=dict(
         plain=n * T, ragged_full=n * T, ragged_half=int(half.sum()) // n_push), objects={})
@@ -445,6 +459,9 @@ def ragged_ab(torch, n, T, seconds, reps, seed, parent):
             cells["margin"] = round(margin, 4)
             cells["plain_over_parent"] = round(cells["plain"]["us_mean"] / (0.5 * (a + b)), 4)
             cells["plain_inside_margin"] = bool(cells["plain"]["us_mean"] <= max(a, b) * (1 + margin))
+            pr = cells["parent_ragged_full"]["us_mean"]
+            cells["ragged_full_over_parent"] = round(cells["ragged_full"]["us_mean"] / pr, 4)
+            cells["ragged_full_inside_margin"] = bool(cells["ragged_full"]["us_mean"] <= pr * (1 + margin))
         cells["ragged_full_over_plain"] = round(cells["ragged_full"]["us_mean"] / cells["plain"]["us_mean"], 4)
         cells["ragged_half_over_plain"] = round(cells["ragged_half"]["us_mean"] / cells["plain"]["us_mean"], 4)
         for k in ("plain", "ragged_full", "ragged_half"):
@@ -463,13 +480,15 @@ def ragged_lines(rec):
     out = [f"{rec['shape']} @{rec['baud']}  {rec['pushes']} calls per pass, {rec['reps']} passes; us per call (mean), "
            f"ns per sample taken"]
     for obj, c in rec["objects"].items():
-        cols = [f"{k} {c[k]['us_mean']:9.1f} us" for k in ("parent", "parent_again", "plain") if k in c]
+        cols = [f"{k} {c[k]['us_mean']:9.1f} us" for k in ("parent", "parent_again", "parent_ragged_full", "plain")
+                if k in c]
         cols += [f"{k} {c[k]['us_mean']:9.1f} us {c[k]['ns_per_sample_taken']:.5f} ns/sample"
                  for k in ("ragged_full", "ragged_half")]
         tail = f"full/plain x{c['ragged_full_over_plain']:.4f}  half/plain x{c['ragged_half_over_plain']:.4f}"
         if "margin" in c:
             tail += (f"  plain/parent x{c['plain_over_parent']:.4f} (margin {100 * c['margin']:.2f} %: "
-                     f"{'inside' if c['plain_inside_margin'] else 'OUTSIDE'})")
+                     f"{'inside' if c['plain_inside_margin'] else 'OUTSIDE'})  ragged_full/parent's "
+                     f"x{c['ragged_full_over_parent']:.4f} ({'inside' if c['ragged_full_inside_margin'] else 'OUTSIDE'})")
         out.append(f"{obj:12s}" + "  ".join(cols) + "   " + tail)
     return out
 
@@ -478,7 +497,13 @@ def tap_line(rec):
     head = f"{rec['shape']:>11s} @{rec['baud']:<5d} {rec['workload']:19s}"
     cells = [f"{k} {v['us_mean']:8.1f} us x{v['over_baseline']:.4f} (spread {100 * v['spread']:.2f} %)"
              for k, v in rec["variants"].items()]
-    return head + "  ".join(cells) + f"   baseline: {rec['baseline']}"
+    tail = ""
+    if "parent_spread" in rec:
+        word = lambda ok: "inside" if ok else "OUTSIDE"  # noqa: E731
+        tail = (f"   parent_spread {100 * rec['parent_spread']:.2f} %: untapped/parent x{rec['untapped_over_parent']:.4f} "
+                f"({word(rec['untapped_inside_spread'])}), tapped/parent_tapped x{rec['tapped_over_parent_tapped']:.4f} "
+                f"({word(rec['tapped_inside_spread'])})")
+    return head + "  ".join(cells) + f"   baseline: {rec['baseline']}" + tail
 
 
 def main():
@@ -512,7 +537,8 @@ def main():
         doc["profiled_shape"] = args.profiled_shape
         for r in rows:
             name = r.get("Name") or r.get("KernelName") or ""
-            if "live_gate_kernel" in name:
+            # the stored sink's instantiations of the push kernel, mangled or demangled (a run pushes through one)
+            if "live_push_kernel" in name and "LiveStoreSink" in name:
                 doc["gate_kernel_calls"] = int(r["Calls"])
                 doc["gate_kernel_mean_us"] = round(float(r["AverageNs"]) / 1e3, 2)
             if "demod_uniform" in name:
