@@ -148,3 +148,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged: the one kernel template over the
 // three sinks, its table of instantiations and the one host path), last: it needs all three sinks.
 #include "afsk_live_push.hip"
+// The packed event list of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into
+// a count, records and payload bytes), for the same reason.
+#include "afsk_live_events.hip"

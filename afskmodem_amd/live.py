@@ -8,7 +8,9 @@ returns the bursts that closed during those T samples, already demodulated -- tw
 (``afsk_live_push``), no host synchronisation, so one push of a fixed T can be captured into a graph and replayed
 for every chunk.  ``flush`` ends every stream (a burst still recording is reported as open-ended); ``reset`` drops
 channels without reporting.  A ``progressive`` streaming receiver also returns, push by push, the payload bytes decoded
-during each push (``LiveResult.partials``, ``PayloadAssembler``).
+during each push (``LiveResult.partials``, ``PayloadAssembler``).  ``push(..., events=ev)`` also packs the bursts the push
+reported into one compact list on the device (``LiveEvents``, ``afsk_live_pack``): the host then copies a header, the
+records and the payload bytes of what closed instead of every slot of every channel.
 Any sequence of pushes followed by a flush reports what ``gate_batch`` +
 ``Receiver.decode_captures`` report on the concatenated capture.
 
@@ -262,6 +264,180 @@ class LiveResult:
         return out
 
 
+def _slot_bursts(result: "LiveResult", string: bool = False, only=None, copied=None):
+    """``LiveResult.bursts`` from the slot arrays of a device- or numpy-backed result.  ``only``: a list of
+    ``(channel, slot)`` -- then the payloads of just those slots, in that order (one row copied per slot).  ``copied``:
+    a one-entry list that receives the bytes brought to the host.
+
+    This repeats the rule of ``LiveResult.bursts`` (which reads CUDA tensors only and stays as it is): which slots are
+    listed, in which order, and which bytes of a row are the payload.  A change to one belongs in the other."""
+    if hasattr(result.n_closed, "is_cuda") and result.n_closed.is_cuda:
+        batch._torch().cuda.synchronize(result.n_closed.device)
+    total = 0
+
+    def host(t):
+        nonlocal total
+        a = _host(t)
+        total += a.nbytes
+        return a
+
+    s, d = result.slots, result.demod
+    stride = int(d.bytes.shape[1])
+    out = []
+    if only is not None:
+        nbytes = host(d.nbytes)
+        out = [_text_or_bytes(host(d.bytes[c * s + k])[: min(max(int(nbytes[c * s + k]), 0), stride)].tobytes(), string)
+               for c, k in only]
+    else:
+        nc, bs, bl, fl = (host(t) for t in (result.n_closed, result.burst_start, result.burst_len, result.flags))
+        chans = np.nonzero(nc)[0]
+        if chans.size:
+            rows, nbytes = host(d.bytes), host(d.nbytes)
+        for c in chans.tolist():
+            for k in range(int(nc[c])):
+                r = c * s + k
+                data = b"" if fl[c, k] & _native.LIVE_OVERFLOW else \
+                    _text_or_bytes(rows[r, : min(max(int(nbytes[r]), 0), stride)].tobytes(), string)
+                out.append((c, int(bs[c, k]), int(bl[c, k]), data))
+    if copied is not None:
+        copied[0] += total
+    return out
+
+
+# afsk_live_event (include/afsk_amd.h), field for field: 48 bytes, no padding
+EVENT_DTYPE = np.dtype([("channel", "<i4"), ("slot", "<i4"), ("burst_start", "<i8"), ("burst_len", "<i4"),
+                        ("flags", "<i4"), ("status", "<i4"), ("nbytes", "<i4"), ("nbits", "<i4"), ("clock_idx", "<i4"),
+                        ("term_frame", "<i4"), ("payload_offset", "<i4")])
+# the 32-byte header of an events buffer
+EVENTS_HEADER_DTYPE = np.dtype([("count", "<i4"), ("stored", "<i4"), ("n_bytes", "<i8"), ("stored_bytes", "<i8"),
+                                ("reserved", "<i8")])
+
+
+def events_layout(n_channels: int, slots: int, max_events: int, max_bytes: int) -> tuple[int, int, int]:
+    """``(records_offset, payload_offset, total_bytes)`` of the events buffer of ``afsk_live_pack`` for ``max_events``
+    records and ``max_bytes`` payload bytes (``afsk_live_events_layout``: host-only)."""
+    ro, po, total = C.c_int64(), C.c_int64(), C.c_int64()
+    _native.check(_native.lib().afsk_live_events_layout(int(n_channels), int(slots), int(max_events), int(max_bytes),
+                                                        C.byref(ro), C.byref(po), C.byref(total)))
+    return int(ro.value), int(po.value), int(total.value)
+
+
+class LiveEvents:
+    """The packed event list of one push (``afsk_live_pack``): ``buffer`` is the events buffer -- a uint8 CUDA tensor
+    (``LiveReceiver.alloc_events``) or a numpy uint8 array laid out the same way -- holding a 32-byte header, up to
+    ``max_events`` records of ``EVENT_DTYPE`` from ``records_offset`` on, in the order of ``LiveResult.bursts()``, and
+    up to ``max_bytes`` payload bytes from ``payload_offset`` on.  ``result`` is the ``LiveResult`` that was packed:
+    what did not fit the buffer is read from its slot arrays, so ``bursts()`` is always complete.  Reading copies the
+    header, then only the records and payload bytes the header counts."""
+
+    def __init__(self, buffer, max_events: int, max_bytes: int, records_offset: int | None = None,
+                 payload_offset: int | None = None, result: "LiveResult | None" = None):
+        self.buffer = buffer
+        self.max_events, self.max_bytes = int(max_events), int(max_bytes)
+        self.records_offset = EVENTS_HEADER_DTYPE.itemsize if records_offset is None else int(records_offset)
+        self.payload_offset = self.records_offset + EVENT_DTYPE.itemsize * self.max_events \
+            if payload_offset is None else int(payload_offset)
+        self.result = result
+        # what the last header() / records() / payload() / bursts() copied to the host, the slot arrays read for what
+        # did not fit the buffer included
+        self.copied_bytes = 0
+
+    def _read(self, lo: int, hi: int) -> np.ndarray:
+        self.copied_bytes += hi - lo
+        part = self.buffer[lo:hi]
+        return part.cpu().numpy() if hasattr(part, "cpu") else np.array(part, np.uint8)
+
+    def header(self) -> np.void:
+        """Synchronise and return the header (``EVENTS_HEADER_DTYPE``): count, stored, n_bytes, stored_bytes."""
+        if hasattr(self.buffer, "is_cuda") and self.buffer.is_cuda:
+            batch._torch().cuda.synchronize(self.buffer.device)
+        self.copied_bytes = 0
+        return self._read(0, EVENTS_HEADER_DTYPE.itemsize).view(EVENTS_HEADER_DTYPE)[0]
+
+    @property
+    def count(self) -> int:
+        """Bursts the push reported, over all channels (may exceed ``max_events``)."""
+        return int(self.header()["count"])
+
+    @property
+    def stored(self) -> int:
+        """Records in the buffer: ``min(count, max_events)``."""
+        return int(self.header()["stored"])
+
+    @property
+    def overflowed(self) -> bool:
+        """Whether a record or a payload did not fit the buffer (``bursts()`` then reads the slot arrays for it)."""
+        h = self.header()
+        return bool(h["count"] > h["stored"] or h["n_bytes"] > h["stored_bytes"])
+
+    def _records(self, h) -> np.ndarray:
+        n = int(h["stored"])
+        return self._read(self.records_offset, self.records_offset + EVENT_DTYPE.itemsize * n).view(EVENT_DTYPE)
+
+    def records(self) -> np.ndarray:
+        """The first ``stored`` records as a numpy array of ``EVENT_DTYPE``."""
+        return self._records(self.header())
+
+    def _payloads(self, h, recs) -> list:
+        """The payload bytes of every record in ``recs``; None where the buffer does not hold them."""
+        # the written payloads are those of the first records; each ends where the next begins, the last at stored_bytes
+        off = recs["payload_offset"].astype(np.int64)
+        w = int(np.count_nonzero(off >= 0))
+        end = np.append(off[1:w], int(h["stored_bytes"]))
+        data = self._read(self.payload_offset, self.payload_offset + int(h["stored_bytes"]))
+        return [data[off[i]: end[i]].tobytes() if i < w else None for i in range(recs.size)]
+
+    def _from_slots(self, string: bool, only=None):
+        """``_slot_bursts`` over the referenced result, its copies counted."""
+        if self.result is None:
+            raise ValueError("the events buffer is too small for this push and no LiveResult is referenced to read "
+                             "the rest from")
+        copied = [0]
+        out = _slot_bursts(self.result, string, only, copied)
+        self.copied_bytes += copied[0]
+        return out
+
+    def payload(self, i: int) -> bytes:
+        """The kept payload bytes of record ``i`` (< ``stored``): b"" for an overflowed burst.  Copies the header,
+        records ``i`` and ``i + 1`` and those bytes alone; for every record use ``bursts()``, which copies each part
+        once."""
+        h = self.header()
+        n = int(h["stored"])
+        if not 0 <= i < n:
+            raise IndexError(f"record {i} of {n}")
+        at = self.records_offset + EVENT_DTYPE.itemsize * i
+        recs = self._read(at, at + EVENT_DTYPE.itemsize * min(2, n - i)).view(EVENT_DTYPE)
+        off = int(recs["payload_offset"][0])
+        if off >= 0:
+            # it ends where the next payload begins; the last one written ends at stored_bytes
+            end = int(recs["payload_offset"][1]) if recs.size > 1 and recs["payload_offset"][1] >= 0 \
+                else int(h["stored_bytes"])
+            return self._read(self.payload_offset + off, self.payload_offset + end).tobytes()
+        if recs["flags"][0] & _native.LIVE_OVERFLOW:
+            return b""
+        return self._from_slots(False, [(int(recs["channel"][0]), int(recs["slot"][0]))])[0]
+
+    def bursts(self, string: bool = False) -> list[tuple[int, int, int, "bytes | str"]]:
+        """What ``result.bursts(string)`` returns -- ``(channel, start, length, payload)`` per reported burst, channel
+        by channel and in time order -- from the header, the ``stored`` records and the ``stored_bytes`` payload bytes.
+        Records past ``max_events`` and payloads past ``max_bytes`` come from the referenced result's slot arrays."""
+        h = self.header()
+        if h["count"] == 0:
+            return []
+        if h["count"] > h["stored"]:
+            return self._from_slots(string)
+        recs = self._records(h)
+        data = self._payloads(h, recs)
+        over = (recs["flags"] & _native.LIVE_OVERFLOW) != 0
+        missing = [i for i in range(recs.size) if data[i] is None and not over[i]]
+        if missing:
+            rows = self._from_slots(False, [(int(recs["channel"][i]), int(recs["slot"][i])) for i in missing])
+            for i, row in zip(missing, rows):
+                data[i] = row
+        return [(int(r["channel"]), int(r["burst_start"]), int(r["burst_len"]),
+                 b"" if over[i] else _text_or_bytes(data[i], string)) for i, r in enumerate(recs)]
+
+
 class PayloadAssembler:
     """Puts the payload segments of a progressive receiver's pushes back together (host only).  ``feed(result)`` takes
     the ``LiveResult`` of every push, in order, and returns ``(channel, start, length, payload)`` for the bursts that
@@ -458,6 +634,50 @@ class LiveReceiver(batch._NativePlan):
         return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod,
                           tap)
 
+    def alloc_events(self, max_events: int | None = None, max_bytes: int | None = None) -> LiveEvents:
+        """An events buffer for ``push(events=...)`` / ``pack``: one uint8 device allocation (``events_layout``) for
+        ``max_events`` records and ``max_bytes`` payload bytes.  The defaults never overflow: ``n_channels * slots``
+        records and ``max_events * out_stride`` bytes (capped below 2^31); callers who know their traffic pass
+        smaller ones -- what does not fit is read from the slot arrays by ``LiveEvents.bursts``.  ``max_bytes=0`` is
+        valid (a progressive receiver with ``max_payload_len=0`` has no payload rows)."""
+        torch = batch._torch()
+        if max_events is None:
+            max_events = self.n_channels * self.slots
+        if max_bytes is None:
+            max_bytes = min(int(max_events) * self.out_stride, 2 ** 31 - 1)
+        ro, po, total = events_layout(self.n_channels, self.slots, max_events, max_bytes)
+        return LiveEvents(torch.zeros(total, dtype=torch.uint8, device=self.device), max_events, max_bytes, ro, po)
+
+    def pack(self, result: LiveResult, out: LiveEvents | None = None, stream=None) -> LiveEvents:
+        """Pack the bursts ``result`` reports into ``out`` (``alloc_events``; None: a new one of the default size) with
+        ``afsk_live_pack``: three launches on ``stream`` (default: torch's current stream), behind the push that
+        writes ``result`` when that ran on the same stream.  Nothing synchronises, so push + pack of fixed buffers can
+        be captured into one graph.  ``out.result`` is ``result`` from then on."""
+        torch = batch._torch()
+        dev = self.device
+        fresh = out is None
+        if fresh:
+            out = self.alloc_events()
+        n, s, d = int(result.n_closed.numel()), result.slots, result.demod
+        buf = out.buffer
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device != dev \
+                or not buf.is_contiguous():
+            raise ValueError("out= was not allocated by this receiver's alloc_events")
+        ro, po, total = events_layout(n, s, out.max_events, out.max_bytes)
+        if (out.records_offset, out.payload_offset) != (ro, po) or int(buf.numel()) < total:
+            raise ValueError("out= was not allocated by this receiver's alloc_events")
+        stride = int(d.bytes.shape[1])
+        with torch.cuda.device(dev):
+            if fresh:
+                batch._order_after_current(stream, dev)
+            _native.check(_native.lib().afsk_live_pack(
+                n, s, result.n_closed.data_ptr(), result.burst_start.data_ptr(), result.burst_len.data_ptr(),
+                result.flags.data_ptr(), d.bytes.data_ptr() if stride else None, stride, d.nbytes.data_ptr(),
+                d.nbits.data_ptr(), d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(),
+                buf.data_ptr(), out.max_events, out.max_bytes, batch._stream_ptr(stream, dev)))
+        out.result = result
+        return out
+
     def assembler(self, string: bool = False) -> PayloadAssembler:
         """A ``PayloadAssembler`` for this (progressive) receiver's pushes."""
         if not self.progressive:
@@ -482,7 +702,8 @@ class LiveReceiver(batch._NativePlan):
         _check_rows(chunk, "chunk", "receiver", self.n_channels, self.device, max_chunk_len=self.max_chunk_len)
         return chunk, False
 
-    def push(self, chunk, stream=None, out: LiveResult | None = None, flush=False, lengths=None) -> LiveResult:
+    def push(self, chunk, stream=None, out: LiveResult | None = None, flush=False, lengths=None,
+             events: LiveEvents | None = None) -> LiveResult:
         """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
         column window of a [channels, time] buffer, no copy -- or a numpy array, uploaded with one copy; None = T 0)
         to every channel's stream and return the bursts that closed, demodulated.  ``flush``: then end every stream
@@ -495,7 +716,10 @@ class LiveReceiver(batch._NativePlan):
         run, so a captured push replays with new lengths), a host sequence or numpy array is uploaded with one copy.
         ``flush`` may be an [n_channels] bool / uint8 mask (host or device): only those channels' streams end.  A
         channel with length 0 and no flush keeps its state.  Without ``lengths`` and with a bool ``flush`` the push is
-        the plain one."""
+        the plain one.
+
+        ``events`` (``alloc_events``): also ``pack`` the result into it, right behind the push on the same stream; the
+        returned result then carries it as ``.events``.  Without it the call launches and sets nothing more."""
         torch = batch._torch()
         chunk, uploaded = self._chunk(chunk)
         dev = self.device
@@ -550,13 +774,18 @@ class LiveReceiver(batch._NativePlan):
                 _native.check(_native.lib().afsk_live_push(*head, int(bool(flush)), *outs,
                                                            batch._stream_ptr(stream, dev)))
         out._chunk_keepalive = (chunk, lens, mask)  # type: ignore[attr-defined]
+        if events is not None:
+            out.events = self.pack(out, out=events, stream=stream)  # type: ignore[attr-defined]
         return out
 
-    def flush(self, chunk=None, stream=None, out: LiveResult | None = None, mask=None, lengths=None) -> LiveResult:
+    def flush(self, chunk=None, stream=None, out: LiveResult | None = None, mask=None, lengths=None,
+              events: LiveEvents | None = None) -> LiveResult:
         """``push(chunk, flush=True)``: end every channel's stream.  A burst still recording is reported (whole blocks,
         ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0.  ``mask``
-        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths``: as ``push``."""
-        return self.push(chunk, stream=stream, out=out, flush=True if mask is None else mask, lengths=lengths)
+        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths`` and ``events``: as
+        ``push``."""
+        return self.push(chunk, stream=stream, out=out, flush=True if mask is None else mask, lengths=lengths,
+                         events=events)
 
     def reset(self, mask=None, stream=None) -> None:
         """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /

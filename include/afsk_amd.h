@@ -771,6 +771,87 @@ extern int afsk_live_tx_pull_ragged(afsk_live_tx *tx, int16_t *out, int64_t out_
                                     const int32_t *d_lens_or_null, int32_t *out_pending, void *hip_stream);
 
 /*
+ * The packed event list of a push (added after ABI version 2; the version is unchanged).  A push answers in slots:
+ * finding the handful of bursts it closed means copying n_closed, the slot arrays and every payload row of every channel.
+ * afsk_live_pack turns the outputs of ONE push -- of any receiver kind and of the plain, tapped or ragged entry alike --
+ * into a compact list on the device, so that the host copies a 32-byte header, `stored` records and `stored_bytes`
+ * payload bytes: a cost in proportion to what closed.  It reads the push's outputs and writes only into the events
+ * buffer, one caller-provided DEVICE allocation of out_total_bytes, 16-byte aligned:
+ *
+ *   [0, 32)                                  the header
+ *        int32 count         bursts the push reported, over all channels (the sum of n_closed); may exceed max_events
+ *        int32 stored        min(count, max_events): the records written
+ *        int64 n_bytes       kept payload bytes of all `count` bursts
+ *        int64 stored_bytes  payload bytes actually written
+ *        8 bytes reserved, written as 0
+ *   [records_offset, + 48 * max_events)      afsk_live_event records (records_offset = 32)
+ *   [payload_offset, + max_bytes)            the records' payloads back to back in record order
+ *   [.., out_total_bytes)                    scratch of the scan: 16 bytes per AFSK_LIVE_EVENTS_SPAN channels
+ *
+ * Record order is channel ascending, then slot ascending -- the order in which a host loop over n_closed visits the
+ * slots -- and is the same on every replay.  A record holds the slot's values as the slot arrays hold them:
+ *
+ *   offset  0  int32 channel
+ *           4  int32 slot            k: the record is slot (channel, k), demodulator row channel * slots + k
+ *           8  int64 burst_start
+ *          16  int32 burst_len
+ *          20  int32 flags           AFSK_LIVE_OPEN_END | AFSK_LIVE_OVERFLOW
+ *          24  int32 status
+ *          28  int32 nbytes          the demodulator's full count (a truncated streaming row: above out_stride)
+ *          32  int32 nbits
+ *          36  int32 clock_idx
+ *          40  int32 term_frame
+ *          44  int32 payload_offset  where its payload starts in the payload part, or -1: not written
+ *
+ * A record keeps kept = min(max(nbytes, 0), out_stride) bytes of its row, and 0 with AFSK_LIVE_OVERFLOW.  Its
+ * payload_offset is the sum of the kept bytes of ALL records before it, and -1 when that sum + kept exceeds max_bytes:
+ * that payload is not written.  Records from index max_events on are not written, nor are their payloads; the header
+ * still holds the true count and n_bytes, so the host sees that the list is short and reads the slot arrays.  Nothing is
+ * written outside the header, the first `stored` records, the first stored_bytes payload bytes and the scratch.
+ * Only n_closed is read for every channel: the slot arrays and the rows are read for slots k < n_closed[c] alone.
+ *
+ *  afsk_live_events_layout  host-only, needs no device: the offsets of the records and of the payload part and the size
+ *                           of the events buffer for max_events records and max_bytes payload bytes
+ *                           (records_offset = 32, payload_offset = 32 + 48 * max_events, out_total_bytes = payload_offset
+ *                           + max_bytes rounded up to 16, + 16 * AFSK_LIVE_EVENTS_BLOCKS(n_channels)).
+ *                           n_channels * slots records and that many times out_stride bytes never overflow.
+ *  afsk_live_pack           packs the outputs of one push: n_closed [n_channels]; burst_start, burst_len, flags
+ *                           [n_channels, slots]; out_bytes [n_channels * slots, out_stride] (may be NULL when out_stride
+ *                           is 0); nbytes, nbits, clock_idx, term_frame, status [n_channels * slots] -- all DEVICE
+ *                           pointers, as the push wrote them.  It takes no receiver: it is a function of the arrays.
+ *                           Three launches in order on hip_stream (totals per span of channels, one block's scan of
+ *                           those totals, records and payloads); no block waits for another.  No allocation, no
+ *                           synchronisation, no host read: capturable into a graph behind the push.
+ * Both: AFSK_E_INVALID_ARG for n_channels < 1, slots < 1, n_channels * slots >= 2^31, max_events < 0, max_bytes < 0 or
+ * >= 2^31, or a NULL pointer.  afsk_live_pack alone: AFSK_E_INVALID_ARG also for out_stride < 0 and for an events buffer
+ * that is not 16-byte aligned (the records and the payload copy are written with 16-byte stores), and AFSK_E_NO_DEVICE
+ * without a device.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_EVENT_SIGNATURES.)
+ */
+#define AFSK_LIVE_EVENTS_SPAN 256 /* channels one block of the pack kernels scans */
+#define AFSK_LIVE_EVENTS_BLOCKS(n_channels) (((int64_t)(n_channels) + AFSK_LIVE_EVENTS_SPAN - 1) / AFSK_LIVE_EVENTS_SPAN)
+typedef struct afsk_live_event {
+    int32_t channel;
+    int32_t slot;
+    int64_t burst_start;
+    int32_t burst_len;
+    int32_t flags;
+    int32_t status;
+    int32_t nbytes;
+    int32_t nbits;
+    int32_t clock_idx;
+    int32_t term_frame;
+    int32_t payload_offset;
+} afsk_live_event;
+extern int afsk_live_events_layout(int32_t n_channels, int32_t slots, int32_t max_events, int64_t max_bytes,
+                                   int64_t *out_records_offset, int64_t *out_payload_offset, int64_t *out_total_bytes);
+extern int afsk_live_pack(int32_t n_channels, int32_t slots, const int32_t *n_closed, const int64_t *burst_start,
+                          const int32_t *burst_len, const int32_t *flags, const uint8_t *out_bytes, int32_t out_stride,
+                          const int32_t *nbytes, const int32_t *nbits, const int32_t *clock_idx,
+                          const int32_t *term_frame, const int32_t *status, void *events, int32_t max_events,
+                          int64_t max_bytes, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,

@@ -6,6 +6,7 @@
     python tools/live_bench.py --stream [--stream-cases 65536x8192@1200,...,16384x8192@long] [--json OUT]
     python tools/live_bench.py --tap [--parent PARENT.so] [--tap-cases 65536x8192@1200,...] [--json OUT] [--txt OUT]
     python tools/live_bench.py --ragged [--parent PARENT.so] [--ragged-shape 65536x8192] [--json OUT] [--txt OUT]
+    python tools/live_bench.py --events [--shapes ...] [--events-max-burst 96000] [--json OUT] [--txt OUT]
 
 --stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
 (stream_ab below).  --tap times the streaming receiver's push with and without the payload tap (progressive=True) on the
@@ -14,6 +15,10 @@ streaming push in the same run (tap_ab below).
 
 --ragged times the ragged push and pull (lengths= per channel; ragged_ab below) of the stored, the streaming and the
 tapped receiver and of the transmitter against the plain calls, and the plain calls against the parent build's.
+
+--events times what it costs to learn which bursts a push closed (events_ab below): the push alone, the push with the
+device-side pack (LiveReceiver.push(events=), afsk_live_pack), and both followed by the host's read -- LiveResult.bursts()
+over every slot array against LiveEvents.bursts() over the packed list -- with the bytes each read copies.
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -34,6 +39,7 @@ import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -356,6 +362,132 @@ def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
     return rec
 
 
+def events_ab(torch, n, T, seconds, reps, seed, max_burst):
+    """What it costs to learn which bursts a push closed, on run_shape's workload with a stored receiver
+    (max_burst_len = max_burst): per push, the variants taking turns pass by pass after one warm-up pass each,
+      a  the push alone, replayed from a graph (HIP events around the replay)
+      b  push + pack in one graph (likewise)
+      c  the replay of a, then LiveResult.bursts() on the host (wall clock from before the replay until the list is there)
+      d  the replay of b, then LiveEvents.bursts() on the host (likewise)
+    and the bytes c and d copy to the host per push.  c is the path that existed before the pack and the only baseline:
+    the spread of its passes, (max - min) / mean, is the margin d's advantage has to exceed."""
+    total = int(seconds * 48000)
+    n_push = total // T
+    total = n_push * T
+    samples, _ = synth.live_channels(n, total, BAUD, seed, bursts_per_channel=2, payload_lens=(4, 12, 24),
+                                     silent_every=8, device="cuda")
+    rx = [LiveReceiver(n, BF, max_burst_len=max_burst, max_chunk_len=T) for _ in range(2)]
+    out = [r.alloc_result() for r in rx]
+    events = rx[1].alloc_events()
+    # eager pass: the packed list reports what the slot arrays report
+    n_bursts = payload = 0
+    for p in range(n_push):
+        w = samples[:, p * T: (p + 1) * T]
+        want = rx[0].push(w, out=out[0], flush=p == n_push - 1).bursts()
+        got = rx[1].push(w, out=out[1], flush=p == n_push - 1, events=events).events.bursts()
+        assert got == want, f"push {p}: the packed list differs from the slot arrays"
+        n_bursts += len(want)
+        payload += sum(len(b[3]) for b in want)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graphs = [[], []]
+    with torch.cuda.stream(side):
+        for p in range(n_push):
+            for i in range(2):
+                gph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gph, stream=side):
+                    rx[i].push(samples[:, p * T: (p + 1) * T], out=out[i], events=events if i else None)
+                graphs[i].append(gph)
+    torch.cuda.synchronize()
+    stride = int(out[0].demod.bytes.shape[1])
+    # what LiveResult.bursts() copies, derived from its tensors' sizes (it does not count its copies; LiveEvents does)
+    slot_arrays = 4 * n + n * rx[0].slots * 16                     # n_closed; burst_start, burst_len, flags
+    demod_arrays = n * rx[0].slots * (stride + 20)                 # the rows and the five vectors (read when a burst closed)
+
+    def host_pass(i):
+        rx[i].flush()
+        torch.cuda.synchronize()
+        us, copied = [], []
+        for p in range(n_push):
+            t0 = time.perf_counter()
+            graphs[i][p].replay()
+            got = events.bursts() if i else out[0].bursts()
+            us.append((time.perf_counter() - t0) * 1e6)
+            copied.append(events.copied_bytes if i else slot_arrays + (demod_arrays if got else 0))
+        return us, copied
+
+    passes = dict(a=[], b=[], c=[], d=[])
+    per_push = dict(a=[], b=[], c=[], d=[])
+    copied = dict(c=[], d=[])
+    for r in range(reps + 1):
+        for k, i in (("a", 0), ("b", 1)):
+            t = timed_pass(torch, rx[i], graphs[i])
+            if r:
+                passes[k].append(float(np.mean(t)))
+                per_push[k] += t
+        for k, i in (("c", 0), ("d", 1)):
+            t, by = host_pass(i)
+            if r:
+                passes[k].append(float(np.mean(t)))
+                per_push[k] += t
+                copied[k] = by
+    cell = lambda k: dict(us_mean=round(float(np.mean(per_push[k])), 2),  # noqa: E731
+                          us_median=round(float(np.median(per_push[k])), 2),
+                          us_passes=[round(x, 2) for x in passes[k]],
+                          spread=round((max(passes[k]) - min(passes[k])) / float(np.mean(passes[k])), 4))
+    rec = dict(shape=f"{n}x{T}", channels=n, T=T, pushes=n_push, reps=reps, slots=rx[0].slots, out_stride=stride,
+               max_burst_len=max_burst, bursts=n_bursts, payload_bytes=payload,
+               events_buffer_bytes=int(events.buffer.numel()), push=cell("a"), push_pack=cell("b"),
+               push_bursts=cell("c"), push_pack_events=cell("d"),
+               host_bytes_per_push_bursts=int(np.mean(copied["c"])), host_bytes_per_push_events=int(np.mean(copied["d"])))
+    a, b, c, d = (rec[k]["us_mean"] for k in ("push", "push_pack", "push_bursts", "push_pack_events"))
+    rec["pack_us"] = round(b - a, 2)
+    rec["pack_over_push"] = round((b - a) / a, 4)
+    rec["events_over_bursts"] = round(d / c, 4)
+    rec["bursts_spread"] = rec["push_bursts"]["spread"]
+    rec["events_faster_beyond_spread"] = bool(d < c * (1 - rec["bursts_spread"]))
+    # the pack alone at its densest: every slot of every channel in use with a 24-byte payload (hand-made arrays in the
+    # result's own tensors; the pack visits a wave's 64 channels one after the other)
+    o = out[1]
+    o.n_closed.fill_(rx[1].slots)
+    o.flags.zero_()
+    o.demod.nbytes.fill_(min(24, stride))
+    t = []
+    for _ in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        rx[1].pack(o, out=events)
+        e1.record()
+        torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1) * 1e3)
+    rec["pack_all_slots_us"] = round(float(np.mean(t[1:])), 2)
+    rec["pack_all_slots_records"] = int(events.count)
+    del graphs, samples
+    torch.cuda.synchronize()
+    for r in rx:
+        r.close()
+    torch.cuda.empty_cache()
+    return rec
+
+
+def events_lines(recs):
+    out = ["us per push, mean / median over every push of every timed pass; host bytes copied per push (mean): d bytes are "
+           "counted at LiveEvents' copies, c bytes are derived from the sizes of the tensors LiveResult.bursts() copies",
+           f"{'shape':>12s} {'bursts':>7s} {'a push':>17s} {'b push+pack':>17s} {'(b-a)/a':>8s} "
+           f"{'c push+bursts()':>19s} {'d push+pack+events':>19s} {'d/c':>7s} {'c spread':>9s} "
+           f"{'c bytes':>11s} {'d bytes':>9s}"]
+    for r in recs:
+        f = lambda k, w: f"{r[k]['us_mean']:.1f} / {r[k]['us_median']:.1f}".rjust(w)  # noqa: E731
+        out.append(f"{r['shape']:>12s} {r['bursts']:7d} {f('push', 17)} {f('push_pack', 17)} {r['pack_over_push']:8.4f} "
+                   f"{f('push_bursts', 19)} {f('push_pack_events', 19)} {r['events_over_bursts']:7.4f} "
+                   f"{100 * r['bursts_spread']:8.2f}% {r['host_bytes_per_push_bursts']:11d} "
+                   f"{r['host_bytes_per_push_events']:9d}")
+    out.append("the pack alone (eager, three launches) with every slot of every channel in use, 24-byte payloads: "
+               + ", ".join(f"{r['shape']} {r['pack_all_slots_records']} records {r['pack_all_slots_us']:.1f} us"
+                           for r in recs))
+    return out
+
+
 def ragged_windows(torch, samples, lens):
     """The pushes of a ragged schedule as buffers: [P, n, T] where row c of push p holds channel c's next lens[p, c]
     samples of `samples` (and what follows them in the stream beyond: never read)."""
@@ -530,6 +662,11 @@ def main():
     ap.add_argument("--ragged", action="store_true",
                     help="the ragged push and pull against the plain ones, and the plain ones against --parent")
     ap.add_argument("--ragged-shape", default="65536x8192")
+    ap.add_argument("--events", action="store_true",
+                    help="the push with and without the device-side pack, and the host's read of the slot arrays "
+                         "against its read of the packed list, per --shapes entry")
+    ap.add_argument("--events-max-burst", type=int, default=96000,
+                    help="with --events: the stored receiver's max_burst_len (default: the receiver's own, 2 s)")
     args = ap.parse_args()
     if args.kernel_stats:
         rows = list(csv.DictReader(open(args.kernel_stats)))
@@ -552,6 +689,21 @@ def main():
         return
     import torch
     res = []
+    if args.events:
+        for shape in args.shapes.split(","):
+            n, T = (int(x) for x in shape.split("x"))
+            rec = events_ab(torch, n, T, args.seconds, args.reps, args.seed, args.events_max_burst)
+            print(json.dumps(rec), flush=True)
+            res.append(rec)
+        lines = events_lines(res)
+        print("\n".join(lines))
+        for path, text in ((args.json, json.dumps(dict(tool="tools/live_bench.py --events", seconds=args.seconds,
+                                                       reps=args.reps, results=res), indent=1)),
+                           (args.txt, "\n".join(lines) + "\n")):
+            if path:
+                with open(path, "w") as f:
+                    f.write(text)
+        return
     if args.ragged:
         n, T = (int(x) for x in args.ragged_shape.split("x"))
         rec = ragged_ab(torch, n, T, args.seconds, args.reps, args.seed, load_build(args.parent) if args.parent else None)
