@@ -202,6 +202,14 @@ LIVE_EVENT_SIGNATURES = {
                                  C.c_int32, C.c_int64, C.c_void_p]),
 }
 
+# The packed segment list of a progressive push (afsk_live_segments_layout, afsk_live_pack_tap), likewise.
+LIVE_SEGMENT_SIGNATURES = {
+    "afsk_live_segments_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, _i64p, _i64p]),
+    "afsk_live_pack_tap": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -216,7 +224,8 @@ def lib() -> C.CDLL:
                                   *LIVE_TX_SIGNATURES.items(), *LIVE_MIXED_SIGNATURES.items(),
                                   *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
                                   *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
-                                  *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items()):
+                                  *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
+                                  *LIVE_SEGMENT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

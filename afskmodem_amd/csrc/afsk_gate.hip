@@ -151,3 +151,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // The packed event list of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into
 // a count, records and payload bytes), for the same reason.
 #include "afsk_live_events.hip"
+// The packed segment list of a progressive push (afsk_live_segments_layout / afsk_live_pack_tap: what the payload tap
+// handed out compacted into a count, records and bytes), last: it uses the event list's scan helpers.
+#include "afsk_live_segments.hip"

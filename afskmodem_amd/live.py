@@ -10,7 +10,9 @@ for every chunk.  ``flush`` ends every stream (a burst still recording is report
 channels without reporting.  A ``progressive`` streaming receiver also returns, push by push, the payload bytes decoded
 during each push (``LiveResult.partials``, ``PayloadAssembler``).  ``push(..., events=ev)`` also packs the bursts the push
 reported into one compact list on the device (``LiveEvents``, ``afsk_live_pack``): the host then copies a header, the
-records and the payload bytes of what closed instead of every slot of every channel.
+records and the payload bytes of what closed instead of every slot of every channel.  ``push(..., segments=sg)`` of a
+progressive receiver does the same one level down: it packs what the tap handed out (``LiveSegments``,
+``afsk_live_pack_tap``), and ``PayloadAssembler.feed`` takes that list in place of the result.
 Any sequence of pushes followed by a flush reports what ``gate_batch`` +
 ``Receiver.decode_captures`` report on the concatenated capture.
 
@@ -438,47 +440,190 @@ class LiveEvents:
                  b"" if over[i] else _text_or_bytes(data[i], string)) for i, r in enumerate(recs)]
 
 
+# afsk_live_segment (include/afsk_amd.h), field for field: 32 bytes, no padding
+SEGMENT_DTYPE = np.dtype([("channel", "<i4"), ("slot", "<i4"), ("burst_start", "<i8"), ("burst_len", "<i4"),
+                          ("flags", "<i4"), ("offset", "<i4"), ("length", "<i4")])
+
+
+def segments_layout(n_channels: int, slots: int, max_segments: int, max_bytes: int) -> tuple[int, int, int]:
+    """``(records_offset, data_offset, total_bytes)`` of the segments buffer of ``afsk_live_pack_tap`` for
+    ``max_segments`` records and ``max_bytes`` data bytes (``afsk_live_segments_layout``: host-only)."""
+    ro, do, total = C.c_int64(), C.c_int64(), C.c_int64()
+    _native.check(_native.lib().afsk_live_segments_layout(int(n_channels), int(slots), int(max_segments),
+                                                          int(max_bytes), C.byref(ro), C.byref(do), C.byref(total)))
+    return int(ro.value), int(do.value), int(total.value)
+
+
+class LiveSegments:
+    """The packed segment list of one progressive push (``afsk_live_pack_tap``): ``buffer`` is the segments buffer -- a
+    uint8 CUDA tensor (``LiveReceiver.alloc_segments``) or a numpy uint8 array laid out the same way -- holding the
+    32-byte header of an events buffer (``EVENTS_HEADER_DTYPE``), up to ``max_segments`` records of ``SEGMENT_DTYPE``
+    from ``records_offset`` on, in the order of ``LiveResult.partials()``, and up to ``max_bytes`` data bytes from
+    ``data_offset`` on, back to back in record order.  ``result`` is the ``LiveResult`` that was packed: when anything
+    did not fit the buffer, ``partials()`` is read from its tap arrays, so it is always complete.  Reading copies the
+    header, then only the records and data bytes the header counts."""
+
+    def __init__(self, buffer, max_segments: int, max_bytes: int, records_offset: int | None = None,
+                 data_offset: int | None = None, result: "LiveResult | None" = None):
+        self.buffer = buffer
+        self.max_segments, self.max_bytes = int(max_segments), int(max_bytes)
+        self.records_offset = EVENTS_HEADER_DTYPE.itemsize if records_offset is None else int(records_offset)
+        self.data_offset = self.records_offset + SEGMENT_DTYPE.itemsize * self.max_segments \
+            if data_offset is None else int(data_offset)
+        self.result = result
+        # what the last header() / records() / partials() -- or the PayloadAssembler.feed that took this list --
+        # copied to the host, the tap arrays read when something did not fit the buffer included
+        self.copied_bytes = 0
+
+    # the header and the way parts of the buffer reach the host are the events buffer's
+    _read = LiveEvents._read
+    header = LiveEvents.header
+
+    @property
+    def count(self) -> int:
+        """Segments of the push, over all channels (may exceed ``max_segments``)."""
+        return int(self.header()["count"])
+
+    @property
+    def stored(self) -> int:
+        """Records in the buffer: ``min(count, max_segments)``."""
+        return int(self.header()["stored"])
+
+    @property
+    def overflowed(self) -> bool:
+        """Whether a record or its data did not fit the buffer (``partials()`` then reads the tap arrays)."""
+        return self._short(self.header())
+
+    @staticmethod
+    def _short(h) -> bool:
+        return bool(h["count"] > h["stored"] or h["n_bytes"] > h["stored_bytes"])
+
+    def _records(self, h) -> np.ndarray:
+        n = int(h["stored"])
+        return self._read(self.records_offset, self.records_offset + SEGMENT_DTYPE.itemsize * n).view(SEGMENT_DTYPE)
+
+    def records(self) -> np.ndarray:
+        """The first ``stored`` records as a numpy array of ``SEGMENT_DTYPE``."""
+        return self._records(self.header())
+
+    def _result(self) -> "LiveResult":
+        if self.result is None:
+            raise ValueError("the segments buffer is too small for this push and no LiveResult is referenced to read "
+                             "the rest from")
+        return self.result
+
+    def _parsed(self):
+        """``(records, their data as a list of bytes)`` of a push that fits the buffer; None when something did not
+        fit."""
+        h = self.header()
+        if self._short(h):
+            return None
+        recs = self._records(h)
+        data = self._read(self.data_offset, self.data_offset + int(h["stored_bytes"])).tobytes()
+        end = np.cumsum(recs["length"].astype(np.int64))
+        return recs, [data[a:b] for a, b in zip((end - recs["length"]).tolist(), end.tolist())]
+
+    def partials(self) -> list[tuple[int, int, int, bytes, bool]]:
+        """What ``result.partials()`` returns -- ``(channel, burst_start, offset, data, final)`` per payload segment,
+        channel by channel and in time order -- from the header, the ``stored`` records and the ``stored_bytes`` data
+        bytes.  When a record or its data did not fit the buffer, the list is ``result.partials()`` itself."""
+        parsed = self._parsed()
+        if parsed is None:
+            res = self._result()
+            tap = res.tap
+            self.copied_bytes += sum(_nbytes(t) for t in (res.n_closed, res.burst_start, res.demod.nbytes, tap.bytes,
+                                                          tap.n, tap.len, tap.open_start, tap.open_nbytes))
+            return res.partials()
+        recs, data = parsed
+        return list(zip(recs["channel"].tolist(), recs["burst_start"].tolist(), recs["offset"].tolist(), data,
+                        (recs["slot"] >= 0).tolist()))
+
+    def _open_start(self, chans: list[int]) -> np.ndarray:
+        """``result.tap.open_start`` at ``chans`` alone: one indexed gather and one small copy."""
+        t = self._result().tap.open_start
+        self.copied_bytes += 8 * len(chans)
+        if hasattr(t, "is_cuda"):
+            torch = batch._torch()
+            return t[torch.as_tensor(chans, dtype=torch.int64).to(t.device)].cpu().numpy()
+        return np.asarray(t)[chans]
+
+
+def _nbytes(t) -> int:
+    """The bytes a torch tensor or a numpy array holds."""
+    return int(t.numel() * t.element_size()) if hasattr(t, "element_size") else int(np.asarray(t).nbytes)
+
+
 class PayloadAssembler:
     """Puts the payload segments of a progressive receiver's pushes back together (host only).  ``feed(result)`` takes
     the ``LiveResult`` of every push, in order, and returns ``(channel, start, length, payload)`` for the bursts that
     push reported -- what ``LiveResult.bursts()`` returns, with the WHOLE payload whatever ``max_payload_len`` is
-    (b"" for an overflowed burst, as there).  ``pending()`` shows the payloads of the bursts still recording."""
+    (b"" for an overflowed burst, as there).  ``pending()`` shows the payloads of the bursts still recording.
+
+    ``feed`` also takes the ``LiveSegments`` of a push (``push(..., segments=sg)``) in place of its result, with the
+    same return value and the same ``pending()``: it then reads the packed list -- a final segment's length and flags
+    come from its record -- and, of the whole-channel arrays, only ``open_start`` at the channels it holds a burst
+    of that had no open segment in the push.  Results and segment lists may alternate from push to push."""
 
     def __init__(self, string: bool = False):
         self.string = string
         self._open: dict[int, tuple[int, bytearray]] = {}      # channel -> (burst_start, payload so far)
 
-    def feed(self, result: LiveResult) -> list[tuple[int, int, int, "bytes | str"]]:
-        events = result.partials()
-        nc, bs, bl, fl = (_host(t) for t in (result.n_closed, result.burst_start, result.burst_len, result.flags))
-        used = {c: 0 for c in np.nonzero(nc)[0].tolist()}
+    def feed(self, x: "LiveResult | LiveSegments") -> list[tuple[int, int, int, "bytes | str"]]:
+        parsed = x._parsed() if isinstance(x, LiveSegments) else None
+        if parsed is not None:
+            recs, data = parsed
+            events = zip(recs["channel"].tolist(), recs["burst_start"].tolist(), recs["offset"].tolist(), data,
+                         (recs["slot"] >= 0).tolist(), recs["burst_len"].tolist(), recs["flags"].tolist())
+            out = self._assemble(events)
+            # a burst that is held but no longer recording was dropped by a reset; a channel with an open segment in
+            # this push is recording the burst that segment names
+            named = set(recs["channel"][recs["slot"] < 0].tolist())
+            held = [c for c in self._open if c not in named]
+            if held:
+                for c, start in zip(held, x._open_start(held).tolist()):
+                    if self._open[c][0] != start:
+                        del self._open[c]
+            return out
+        if isinstance(x, LiveSegments):                             # something did not fit: the tap arrays have it all
+            result = x._result()
+            events = x.partials()
+            x.copied_bytes += sum(_nbytes(t) for t in (result.burst_len, result.flags, result.tap.open_start))
+        else:
+            result = x
+            events = result.partials()
+        nc, bl, fl = (_host(t) for t in (result.n_closed, result.burst_len, result.flags))
+        # the final segments come channel by channel and slot by slot: their slots' lengths and flags in that order
+        closed = iter([(int(bl[c, k]), int(fl[c, k])) for c in np.nonzero(nc)[0].tolist() for k in range(int(nc[c]))])
+        out = self._assemble((*e, *(next(closed) if e[4] else (0, 0))) for e in events)
+        open_start = _host(result.tap.open_start)
+        for c in [c for c, (start, _) in self._open.items() if open_start[c] != start]:
+            del self._open[c]
+        return out
+
+    def _assemble(self, events) -> list[tuple[int, int, int, "bytes | str"]]:
+        """Take ``(channel, burst_start, offset, data, final, burst_len, flags)`` per segment of one push, in order;
+        return the bursts that closed."""
         out = []
-        for c, start, offset, data, final in events:
+        for c, start, offset, data, final, length, flags in events:
             held = self._open.get(c)
             if held is None or held[0] != start:                    # a new burst (a reset dropped the one held)
                 held = (start, bytearray())
                 self._open[c] = held
             if final:
-                k = used[c]
-                used[c] = k + 1
                 del self._open[c]
-                if fl[c, k] & _native.LIVE_OVERFLOW:
+                if flags & _native.LIVE_OVERFLOW:
                     payload = b""
                 else:
                     if offset != len(held[1]):
                         raise ValueError(f"channel {c}, burst at {start}: a segment at offset {offset} follows "
                                          f"{len(held[1])} bytes -- a push is missing or out of order")
                     payload = bytes(held[1] + data)
-                out.append((c, start, int(bl[c, k]), _text_or_bytes(payload, self.string)))
+                out.append((c, start, length, _text_or_bytes(payload, self.string)))
             else:
                 if offset != len(held[1]):
                     raise ValueError(f"channel {c}, burst at {start}: a segment at offset {offset} follows "
                                      f"{len(held[1])} bytes -- a push is missing or out of order")
                 held[1].extend(data)
-        # a burst that is held but no longer recording was dropped by a reset
-        open_start = _host(result.tap.open_start)
-        for c in [c for c, (start, _) in self._open.items() if open_start[c] != start]:
-            del self._open[c]
         return out
 
     def pending(self) -> dict[int, tuple[int, bytes]]:
@@ -678,6 +823,56 @@ class LiveReceiver(batch._NativePlan):
         out.result = result
         return out
 
+    def alloc_segments(self, max_segments: int | None = None, max_bytes: int | None = None) -> LiveSegments:
+        """A segments buffer for ``push(segments=...)`` / ``pack_tap`` of a progressive receiver: one uint8 device
+        allocation (``segments_layout``) for ``max_segments`` records and ``max_bytes`` data bytes.  The defaults never
+        overflow: ``n_channels * (slots + 1)`` records and ``n_channels * tap_cap`` bytes (capped below 2^31); callers
+        who know their traffic pass smaller ones -- when something does not fit, ``LiveSegments.partials`` reads the
+        tap arrays."""
+        torch = batch._torch()
+        if not self.progressive:
+            raise ValueError("alloc_segments() needs a progressive receiver (LiveReceiver(..., progressive=True))")
+        if max_segments is None:
+            max_segments = min(self.n_channels * (self.slots + 1), 2 ** 31 - 1)
+        if max_bytes is None:
+            max_bytes = min(self.n_channels * self.tap_cap, 2 ** 31 - 1)
+        ro, do, total = segments_layout(self.n_channels, self.slots, max_segments, max_bytes)
+        return LiveSegments(torch.zeros(total, dtype=torch.uint8, device=self.device), max_segments, max_bytes, ro, do)
+
+    def pack_tap(self, result: LiveResult, out: LiveSegments | None = None, stream=None) -> LiveSegments:
+        """Pack the payload segments ``result`` holds (a progressive push's) into ``out`` (``alloc_segments``; None: a
+        new one of the default size) with ``afsk_live_pack_tap``: three launches on ``stream`` (default: torch's
+        current stream), behind the push that writes ``result`` when that ran on the same stream.  Nothing
+        synchronises, so push + pack of fixed buffers can be captured into one graph.  ``out.result`` is ``result``
+        from then on."""
+        torch = batch._torch()
+        dev = self.device
+        tap = result.tap
+        if tap is None:
+            raise ValueError("pack_tap() needs the result of a progressive receiver's push (LiveReceiver(..., "
+                             "progressive=True))")
+        fresh = out is None
+        if fresh:
+            out = self.alloc_segments()
+        n, s, cap = int(result.n_closed.numel()), result.slots, int(tap.bytes.shape[1])
+        buf = out.buffer
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device != dev \
+                or not buf.is_contiguous():
+            raise ValueError("out= was not allocated by this receiver's alloc_segments")
+        ro, do, total = segments_layout(n, s, out.max_segments, out.max_bytes)
+        if (out.records_offset, out.data_offset) != (ro, do) or int(buf.numel()) < total:
+            raise ValueError("out= was not allocated by this receiver's alloc_segments")
+        with torch.cuda.device(dev):
+            if fresh:
+                batch._order_after_current(stream, dev)
+            _native.check(_native.lib().afsk_live_pack_tap(
+                n, s, cap, result.n_closed.data_ptr(), result.burst_start.data_ptr(), result.burst_len.data_ptr(),
+                result.flags.data_ptr(), result.demod.nbytes.data_ptr(), tap.bytes.data_ptr(), tap.n.data_ptr(),
+                tap.len.data_ptr(), tap.open_start.data_ptr(), tap.open_nbytes.data_ptr(), buf.data_ptr(),
+                out.max_segments, out.max_bytes, batch._stream_ptr(stream, dev)))
+        out.result = result
+        return out
+
     def assembler(self, string: bool = False) -> PayloadAssembler:
         """A ``PayloadAssembler`` for this (progressive) receiver's pushes."""
         if not self.progressive:
@@ -703,7 +898,7 @@ class LiveReceiver(batch._NativePlan):
         return chunk, False
 
     def push(self, chunk, stream=None, out: LiveResult | None = None, flush=False, lengths=None,
-             events: LiveEvents | None = None) -> LiveResult:
+             events: LiveEvents | None = None, segments: LiveSegments | None = None) -> LiveResult:
         """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
         column window of a [channels, time] buffer, no copy -- or a numpy array, uploaded with one copy; None = T 0)
         to every channel's stream and return the bursts that closed, demodulated.  ``flush``: then end every stream
@@ -719,8 +914,15 @@ class LiveReceiver(batch._NativePlan):
         the plain one.
 
         ``events`` (``alloc_events``): also ``pack`` the result into it, right behind the push on the same stream; the
-        returned result then carries it as ``.events``.  Without it the call launches and sets nothing more."""
+        returned result then carries it as ``.events``.  Without it the call launches and sets nothing more.
+
+        ``segments`` (``alloc_segments``; a progressive receiver only, ValueError otherwise): also ``pack_tap`` the
+        result into it, behind the push (and behind the event pack) on the same stream; the returned result then
+        carries it as ``.segments``.  Without it the call launches and sets nothing more."""
         torch = batch._torch()
+        if segments is not None and not self.progressive:
+            raise ValueError("segments= needs a progressive receiver (LiveReceiver(..., progressive=True)): only its "
+                             "pushes hand out payload segments")
         chunk, uploaded = self._chunk(chunk)
         dev = self.device
         lens = mask = None
@@ -776,16 +978,18 @@ class LiveReceiver(batch._NativePlan):
         out._chunk_keepalive = (chunk, lens, mask)  # type: ignore[attr-defined]
         if events is not None:
             out.events = self.pack(out, out=events, stream=stream)  # type: ignore[attr-defined]
+        if segments is not None:
+            out.segments = self.pack_tap(out, out=segments, stream=stream)  # type: ignore[attr-defined]
         return out
 
     def flush(self, chunk=None, stream=None, out: LiveResult | None = None, mask=None, lengths=None,
-              events: LiveEvents | None = None) -> LiveResult:
+              events: LiveEvents | None = None, segments: LiveSegments | None = None) -> LiveResult:
         """``push(chunk, flush=True)``: end every channel's stream.  A burst still recording is reported (whole blocks,
         ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0.  ``mask``
-        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths`` and ``events``: as
-        ``push``."""
+        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths``, ``events`` and
+        ``segments``: as ``push``."""
         return self.push(chunk, stream=stream, out=out, flush=True if mask is None else mask, lengths=lengths,
-                         events=events)
+                         events=events, segments=segments)
 
     def reset(self, mask=None, stream=None) -> None:
         """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /

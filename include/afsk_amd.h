@@ -852,6 +852,87 @@ extern int afsk_live_pack(int32_t n_channels, int32_t slots, const int32_t *n_cl
                           int64_t max_bytes, void *hip_stream);
 
 /*
+ * The packed segment list of a progressive push (added after ABI version 2; the version is unchanged).  The payload tap
+ * answers in whole arrays too: reading what one push decoded means copying tap_bytes, tap_n, tap_len, open_start and
+ * open_nbytes of every channel.  afsk_live_pack_tap turns the outputs of ONE tapped push (afsk_live_push_tap, or
+ * afsk_live_push_ragged with the tap pointers given) into a compact list on the device, so that the host copies a
+ * 32-byte header, `stored` records and `stored_bytes` data bytes: a cost in proportion to what decoded.  It reads the
+ * push's outputs and writes only into the segments buffer, one caller-provided DEVICE allocation of out_total_bytes,
+ * 16-byte aligned:
+ *
+ *   [0, 32)                                  the header of the events buffer, field for field
+ *        int32 count         segments of the push, over all channels; may exceed max_segments (exact while
+ *                            n_channels * (slots + 1) < 2^31, held at 2^31 - 1 beyond)
+ *        int32 stored        min(count, max_segments): the records written
+ *        int64 n_bytes       data bytes of all `count` segments
+ *        int64 stored_bytes  data bytes actually written
+ *        8 bytes reserved, written as 0
+ *   [records_offset, + 32 * max_segments)    afsk_live_segment records (records_offset = 32)
+ *   [data_offset, + max_bytes)               the records' data back to back in record order
+ *   [.., out_total_bytes)                    scratch of the scan: 16 bytes per AFSK_LIVE_EVENTS_SPAN channels
+ *
+ * The per-channel rule.  For channel c: nc = clamp(n_closed[c], 0, slots) and tn = clamp(tap_n[c], 0, tap_cap); with
+ * at = 0, every slot k < nc in turn takes ln_k = clamp(tap_len[c, k], 0, tn - at) bytes and at += ln_k; rest = tn - at.
+ * The channel has an OPEN segment iff rest > 0 and open_start[c] >= 0.  It contributes nc FINAL records -- one per burst
+ * the push reported, with length 0 where the burst closed without new bytes -- and then the open record if it has one:
+ *
+ *   offset  0  int32 channel       c
+ *           4  int32 slot          k: a final segment, of slot (c, k); -1: the open segment
+ *           8  int64 burst_start   burst_start[c, k]                  open: open_start[c]
+ *          16  int32 burst_len     burst_len[c, k]                    open: 0
+ *          20  int32 flags         flags[c, k]                        open: 0
+ *          24  int32 offset        nbytes[c * slots + k] - ln_k       open: open_nbytes[c] - rest
+ *                                  (where in the burst's payload the data belong)
+ *          28  int32 length        ln_k                               open: rest
+ *
+ * Its data are tap_bytes[c, 0 : at] and, with an open segment, [at : at + rest]: one contiguous run of the tap row that
+ * lands as one contiguous run of the data part.  On the outputs of a real push the clamps change nothing.
+ *
+ * Record order is channel ascending, then the slots ascending, then the open segment, and is the same on every replay.
+ * The data lie back to back in record order; a record holds no data offset: its data start at the sum of the lengths of
+ * all records before it.  A record's data are written iff the record is stored (its index is below max_segments) and its
+ * start plus its length is at most max_bytes; stored_bytes is the start of the first record whose data are not written,
+ * or n_bytes when all are.  The header always holds the true count and n_bytes, so the host sees that the list is short
+ * and reads the tap arrays.  Nothing is written outside the header, the first `stored` records, the first stored_bytes
+ * data bytes and the scratch, also when a channel's run straddles max_bytes.  n_channels * (slots + 1) records and
+ * n_channels * tap_cap bytes never overflow.  For every channel only n_closed and tap_n are read; tap_len for k < nc
+ * alone; open_start and open_nbytes only where rest > 0; the slot arrays and the tap rows only for what is written.
+ *
+ *  afsk_live_segments_layout  host-only, needs no device: the offsets of the records and of the data part and the size
+ *                             of the segments buffer (records_offset = 32, data_offset = 32 + 32 * max_segments,
+ *                             out_total_bytes = data_offset + max_bytes rounded up to 16,
+ *                             + 16 * AFSK_LIVE_EVENTS_BLOCKS(n_channels)).
+ *  afsk_live_pack_tap         packs the outputs of one tapped push: n_closed [n_channels]; burst_start, burst_len, flags
+ *                             [n_channels, slots]; nbytes [n_channels * slots]; tap_bytes [n_channels, tap_cap]; tap_n
+ *                             [n_channels]; tap_len [n_channels, slots]; open_start, open_nbytes [n_channels] -- all
+ *                             DEVICE pointers, as the push wrote them.  It takes no receiver: it is a function of the
+ *                             arrays.  Three launches in order on hip_stream (totals per span of channels, one block's
+ *                             scan of those totals, then a thread per channel writes its records and copies its bytes);
+ *                             no block waits for another.  No allocation, no synchronisation, no host read: capturable
+ *                             into a graph behind the push.
+ * Both: AFSK_E_INVALID_ARG for what afsk_live_events_layout refuses (max_segments in the place of max_events) or a NULL
+ * pointer.  afsk_live_pack_tap alone: AFSK_E_INVALID_ARG also for tap_cap < 1 and for a segments buffer that is not
+ * 16-byte aligned (the records are written with 16-byte stores), and AFSK_E_NO_DEVICE without a device.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_SEGMENT_SIGNATURES.)
+ */
+typedef struct afsk_live_segment {
+    int32_t channel;
+    int32_t slot;
+    int64_t burst_start;
+    int32_t burst_len;
+    int32_t flags;
+    int32_t offset;
+    int32_t length;
+} afsk_live_segment;
+extern int afsk_live_segments_layout(int32_t n_channels, int32_t slots, int32_t max_segments, int64_t max_bytes,
+                                     int64_t *out_records_offset, int64_t *out_data_offset, int64_t *out_total_bytes);
+extern int afsk_live_pack_tap(int32_t n_channels, int32_t slots, int32_t tap_cap, const int32_t *n_closed,
+                              const int64_t *burst_start, const int32_t *burst_len, const int32_t *flags,
+                              const int32_t *nbytes, const uint8_t *tap_bytes, const int32_t *tap_n,
+                              const int32_t *tap_len, const int64_t *open_start, const int32_t *open_nbytes,
+                              void *segments, int32_t max_segments, int64_t max_bytes, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,

@@ -7,6 +7,7 @@
     python tools/live_bench.py --tap [--parent PARENT.so] [--tap-cases 65536x8192@1200,...] [--json OUT] [--txt OUT]
     python tools/live_bench.py --ragged [--parent PARENT.so] [--ragged-shape 65536x8192] [--json OUT] [--txt OUT]
     python tools/live_bench.py --events [--shapes ...] [--events-max-burst 96000] [--json OUT] [--txt OUT]
+    python tools/live_bench.py --segments [--shapes 65536x8192,65536x2048] [--sparse-every 64] [--json OUT] [--txt OUT]
 
 --stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
 (stream_ab below).  --tap times the streaming receiver's push with and without the payload tap (progressive=True) on the
@@ -19,6 +20,11 @@ tapped receiver and of the transmitter against the plain calls, and the plain ca
 --events times what it costs to learn which bursts a push closed (events_ab below): the push alone, the push with the
 device-side pack (LiveReceiver.push(events=), afsk_live_pack), and both followed by the host's read -- LiveResult.bursts()
 over every slot array against LiveEvents.bursts() over the packed list -- with the bytes each read copies.
+
+--segments times what it costs to put a progressive receiver's payloads together push by push (segments_ab below): the
+tapped push alone, the push with the device-side pack (LiveReceiver.push(segments=), afsk_live_pack_tap), and both
+followed by the host's PayloadAssembler.feed -- of the result's whole arrays against the packed list -- with the bytes
+each copies, on the workload below and on a sparse one where only one channel in --sparse-every carries signal.
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -488,6 +494,167 @@ def events_lines(recs):
     return out
 
 
+def segments_ab(torch, n, T, seconds, reps, seed, keep_every):
+    """What it costs to put a progressive receiver's payloads together push by push, on run_shape's workload
+    (keep_every 1: seven channels in eight carry two bursts) or with only one channel in keep_every left and the
+    others silent: per push, the variants taking turns pass by pass after one warm-up pass each,
+      a  the tapped push alone, replayed from a graph (HIP events around the replay)
+      b  push + afsk_live_pack_tap in one graph (likewise)
+      c  the replay of a, then PayloadAssembler.feed(result) on the host (wall clock until the bursts are there)
+      d  the replay of b, then PayloadAssembler.feed(segments) on the host (likewise)
+    and the bytes c and d copy to the host per push.  c is the path that existed before the pack and the only baseline:
+    the spread of its passes, (max - min) / mean, is the margin d's difference has to exceed either way."""
+    from afskmodem_amd.live import _nbytes
+    total = int(seconds * 48000)
+    n_push = total // T
+    total = n_push * T
+    samples, _ = synth.live_channels(n, total, BAUD, seed, bursts_per_channel=2, payload_lens=(4, 12, 24),
+                                     silent_every=8, device="cuda")
+    if keep_every > 1:
+        # (channel 1 of every keep_every: the workload's silent channels are those at multiples of eight)
+        samples[torch.arange(n, device="cuda") % keep_every != 1] = 0
+    rx = [LiveReceiver(n, BF, max_burst_len=None, max_payload_len=256, max_chunk_len=T, progressive=True)
+          for _ in range(2)]
+    out = [r.alloc_result() for r in rx]
+    sg = rx[1].alloc_segments()
+    # eager pass: the packed list is the tap arrays' list, and both assemblers return the same bursts
+    asm = [r.assembler() for r in rx]
+    n_bursts = payload = n_segments = busy_channels = 0
+    for p in range(n_push):
+        w = samples[:, p * T: (p + 1) * T]
+        res = rx[0].push(w, out=out[0], flush=p == n_push - 1)
+        rx[1].push(w, out=out[1], flush=p == n_push - 1, segments=sg)
+        parts = res.partials()
+        assert sg.partials() == parts, f"push {p}: the packed list differs from the tap arrays"
+        want, got = asm[0].feed(res), asm[1].feed(sg)
+        assert got == want and asm[0].pending() == asm[1].pending(), f"push {p}: the assemblers differ"
+        n_bursts += len(want)
+        payload += sum(len(b[3]) for b in want)
+        n_segments += len(parts)
+        busy_channels += len({e[0] for e in parts})
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graphs = [[], []]
+    with torch.cuda.stream(side):
+        for p in range(n_push):
+            for i in range(2):
+                gph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gph, stream=side):
+                    rx[i].push(samples[:, p * T: (p + 1) * T], out=out[i], segments=sg if i else None)
+                graphs[i].append(gph)
+    torch.cuda.synchronize()
+    # what feed(result) copies, derived from its tensors' sizes (it does not count its copies; LiveSegments does):
+    # partials() -- n_closed, burst_start, nbytes and the five tap tensors -- then n_closed, burst_len, flags, open_start
+    o, t = out[0], out[0].tap
+    whole = sum(_nbytes(x) for x in (o.n_closed, o.burst_start, o.demod.nbytes, t.bytes, t.n, t.len, t.open_start,
+                                     t.open_nbytes, o.n_closed, o.burst_len, o.flags, t.open_start))
+
+    def host_pass(i):
+        rx[i].flush()
+        torch.cuda.synchronize()
+        a = rx[i].assembler()
+        us, copied, bursts = [], [], 0
+        for p in range(n_push):
+            t0 = time.perf_counter()
+            graphs[i][p].replay()
+            bursts += len(a.feed(sg if i else out[0]))
+            us.append((time.perf_counter() - t0) * 1e6)
+            copied.append(sg.copied_bytes if i else whole)
+        return us, copied, bursts
+
+    passes = dict(a=[], b=[], c=[], d=[])
+    per_push = dict(a=[], b=[], c=[], d=[])
+    copied = dict(c=[], d=[])
+    for r in range(reps + 1):
+        for k, i in (("a", 0), ("b", 1)):
+            t = timed_pass(torch, rx[i], graphs[i])
+            if r:
+                passes[k].append(float(np.mean(t)))
+                per_push[k] += t
+        for k, i in (("c", 0), ("d", 1)):
+            t, by, _ = host_pass(i)
+            if r:
+                passes[k].append(float(np.mean(t)))
+                per_push[k] += t
+                copied[k] = by
+    cell = lambda k: dict(us_mean=round(float(np.mean(per_push[k])), 2),  # noqa: E731
+                          us_median=round(float(np.median(per_push[k])), 2),
+                          us_passes=[round(x, 2) for x in passes[k]],
+                          spread=round((max(passes[k]) - min(passes[k])) / float(np.mean(passes[k])), 4))
+    rec = dict(shape=f"{n}x{T}", channels=n, T=T, workload="all" if keep_every <= 1 else f"1_in_{keep_every}",
+               signal_fraction=round(1.0 / max(keep_every, 1), 6), pushes=n_push, reps=reps, slots=rx[0].slots,
+               tap_cap=rx[0].tap_cap, bursts=n_bursts, payload_bytes=payload,
+               segments_per_push=round(n_segments / n_push, 1), busy_channels_per_push=round(busy_channels / n_push, 1),
+               segments_buffer_bytes=int(sg.buffer.numel()), push=cell("a"), push_pack=cell("b"),
+               push_feed_result=cell("c"), push_pack_feed_segments=cell("d"),
+               host_bytes_per_push_result=int(np.mean(copied["c"])), host_bytes_per_push_segments=int(np.mean(copied["d"])))
+    a, b, c, d = (rec[k]["us_mean"] for k in ("push", "push_pack", "push_feed_result", "push_pack_feed_segments"))
+    rec["pack_us"] = round(b - a, 2)
+    rec["pack_over_push"] = round((b - a) / a, 4)
+    rec["push_spread"] = rec["push"]["spread"]
+    rec["segments_over_result"] = round(d / c, 4)
+    rec["result_spread"] = rec["push_feed_result"]["spread"]
+    rec["segments_faster_beyond_spread"] = bool(d < c * (1 - rec["result_spread"]))
+    rec["segments_slower_beyond_spread"] = bool(d > c * (1 + rec["result_spread"]))
+    # the pack alone at its densest, on hand-made arrays in the result's own tensors: every channel with an open segment
+    # of min(14, tap_cap) bytes (14: what a busy 1200-baud channel decodes in 8192 samples), then every slot in use as
+    # well (final segments of length 0)
+    o, t = out[1], out[1].tap
+    k = min(14, rx[1].tap_cap)
+    for name, closed in (("pack_all_open", 0), ("pack_all_slots_open", rx[1].slots)):
+        o.n_closed.fill_(closed)
+        o.flags.zero_()
+        o.demod.nbytes.fill_(k)
+        t.n.fill_(k)
+        t.len.zero_()
+        t.open_start.fill_(2048)
+        t.open_nbytes.fill_(k)
+        us = []
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rx[1].pack_tap(o, out=sg)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        rec[name + "_us"] = round(float(np.mean(us[1:])), 2)
+        rec[name + "_records"] = int(sg.count)
+    rec["pack_all_open_bytes_per_channel"] = k
+    del graphs, samples
+    torch.cuda.synchronize()
+    for r in rx:
+        r.close()
+    torch.cuda.empty_cache()
+    return rec
+
+
+def segments_lines(recs):
+    out = ["us per push, mean / median over every push of every timed pass; host bytes copied per push (mean): d bytes are "
+           "counted at LiveSegments' copies, c bytes are derived from the sizes of the tensors feed(result) copies; "
+           "workload: all = the tool's channels (7 in 8 carry two bursts), 1_in_K = only one channel in K keeps its signal",
+           f"{'shape':>12s} {'workload':>9s} {'seg/push':>9s} {'a push':>17s} {'b push+pack':>17s} {'(b-a)/a':>8s} "
+           f"{'a spread':>9s} {'c push+feed(result)':>21s} {'d push+pack+feed(segments)':>27s} {'d/c':>7s} "
+           f"{'c spread':>9s} {'c bytes':>10s} {'d bytes':>9s}"]
+    for r in recs:
+        f = lambda k, w: f"{r[k]['us_mean']:.1f} / {r[k]['us_median']:.1f}".rjust(w)  # noqa: E731
+        out.append(f"{r['shape']:>12s} {r['workload']:>9s} {r['segments_per_push']:9.1f} {f('push', 17)} "
+                   f"{f('push_pack', 17)} {r['pack_over_push']:8.4f} {100 * r['push_spread']:8.2f}% "
+                   f"{f('push_feed_result', 21)} {f('push_pack_feed_segments', 27)} {r['segments_over_result']:7.4f} "
+                   f"{100 * r['result_spread']:8.2f}% {r['host_bytes_per_push_result']:10d} "
+                   f"{r['host_bytes_per_push_segments']:9d}")
+    seen = set()
+    dense = []
+    for r in recs:
+        if r["shape"] not in seen:
+            seen.add(r["shape"])
+            dense.append(f"{r['shape']} ({r['pack_all_open_bytes_per_channel']} bytes) open only "
+                         f"{r['pack_all_open_records']} records {r['pack_all_open_us']:.1f} us, "
+                         f"all slots + open {r['pack_all_slots_open_records']} records {r['pack_all_slots_open_us']:.1f} us")
+    out.append("the pack alone (eager, three launches; a thread per channel) with an open segment of min(14, tap_cap) bytes "
+               "on every channel: " + "; ".join(dense))
+    return out
+
+
 def ragged_windows(torch, samples, lens):
     """The pushes of a ragged schedule as buffers: [P, n, T] where row c of push p holds channel c's next lens[p, c]
     samples of `samples` (and what follows them in the stream beyond: never read)."""
@@ -667,6 +834,11 @@ def main():
                          "against its read of the packed list, per --shapes entry")
     ap.add_argument("--events-max-burst", type=int, default=96000,
                     help="with --events: the stored receiver's max_burst_len (default: the receiver's own, 2 s)")
+    ap.add_argument("--segments", action="store_true",
+                    help="the tapped push with and without the device-side segment pack, and the assembler fed results "
+                         "against the assembler fed packed lists, per --shapes entry, dense and sparse")
+    ap.add_argument("--sparse-every", type=int, default=64,
+                    help="with --segments: the sparse workload keeps the signal of one channel in this many")
     args = ap.parse_args()
     if args.kernel_stats:
         rows = list(csv.DictReader(open(args.kernel_stats)))
@@ -699,6 +871,23 @@ def main():
         print("\n".join(lines))
         for path, text in ((args.json, json.dumps(dict(tool="tools/live_bench.py --events", seconds=args.seconds,
                                                        reps=args.reps, results=res), indent=1)),
+                           (args.txt, "\n".join(lines) + "\n")):
+            if path:
+                with open(path, "w") as f:
+                    f.write(text)
+        return
+    if args.segments:
+        for shape in args.shapes.split(","):
+            n, T = (int(x) for x in shape.split("x"))
+            for keep_every in (1, args.sparse_every):
+                rec = segments_ab(torch, n, T, args.seconds, args.reps, args.seed, keep_every)
+                print(json.dumps(rec), flush=True)
+                res.append(rec)
+        lines = segments_lines(res)
+        print("\n".join(lines))
+        for path, text in ((args.json, json.dumps(dict(tool="tools/live_bench.py --segments", seconds=args.seconds,
+                                                       reps=args.reps, sparse_every=args.sparse_every, results=res),
+                                                  indent=1)),
                            (args.txt, "\n".join(lines) + "\n")):
             if path:
                 with open(path, "w") as f:
