@@ -14,7 +14,8 @@ sharding in ``afskmodem_amd.dist``; synthetic workloads in ``afskmodem_amd.synth
 LOG_LEVEL = 0
 
 from .modem import ECC, Log, Receiver, SoundInput, SoundOutput, Transmitter, Waveforms, load_batch  # noqa: E402
+from .modem import detect_baud, load_batch_auto  # noqa: E402
 from .live import LiveReceiver, LiveTransmitter  # noqa: E402
 
 __all__ = ["ECC", "Log", "LiveReceiver", "LiveTransmitter", "Receiver", "SoundInput", "SoundOutput", "Transmitter",
-           "Waveforms", "LOG_LEVEL", "load_batch"]
+           "Waveforms", "LOG_LEVEL", "load_batch", "detect_baud", "load_batch_auto"]

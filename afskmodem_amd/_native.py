@@ -210,6 +210,13 @@ LIVE_SEGMENT_SIGNATURES = {
                                      C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
 }
 
+# The rate detector (afsk_detect_rate_batch), likewise.
+DETECT_SIGNATURES = {
+    "afsk_detect_rate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _i32p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+DETECT_MAX_CANDIDATES = 36                   # AFSK_DETECT_MAX_CANDIDATES
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -225,7 +232,7 @@ def lib() -> C.CDLL:
                                   *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
                                   *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
-                                  *LIVE_SEGMENT_SIGNATURES.items()):
+                                  *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

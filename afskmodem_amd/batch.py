@@ -556,6 +556,117 @@ def demod_batch(samples, stream_offset, stream_len, bit_frames, amp_end_threshol
     return out
 
 
+# every bit_frames value a Receiver can have (``validate_bit_frames``): the divisors of 48000 that are multiples of 4
+# with 2 * bf < 4096, ascending -- 12000 baud down to 24 baud; AFSK_DETECT_MAX_CANDIDATES of them
+VALID_BIT_FRAMES = tuple(bf for bf in range(4, SYNC_WINDOW // 2, 4) if SAMPLE_RATE % bf == 0)
+assert len(VALID_BIT_FRAMES) == _native.DETECT_MAX_CANDIDATES
+
+
+@dataclass
+class HostRateResult:
+    bit_frames: np.ndarray   # int32 [n]; 0 = not examined (shorter than 4096 samples, or a refused length)
+    score: np.ndarray        # int32 [n]; -1 = not examined
+    runner_up: np.ndarray    # int32 [n]; -1 = not examined, or one candidate
+    clock_idx: np.ndarray    # int32 [n]; -1 = not examined
+    scores: "np.ndarray | None"   # int32 [n, K]
+    candidates: tuple
+
+    def bauds(self) -> list:
+        """48000 // bit_frames per stream, None where nothing was detected."""
+        return [SAMPLE_RATE // int(bf) if bf > 0 else None for bf in self.bit_frames]
+
+
+@dataclass
+class RateResult:
+    """Device-resident outputs of one ``detect_rates`` launch (all torch tensors; ``candidates`` a host tuple)."""
+    bit_frames: "object"     # int32 [n]: the argument ``demod_batch(bit_frames=)`` takes as it is
+    score: "object"
+    runner_up: "object"
+    clock_idx: "object"
+    scores: "object" = None  # int32 [n, K], with scores=True
+    candidates: tuple = ()
+
+    def cpu(self) -> HostRateResult:
+        h = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+        return HostRateResult(h(self.bit_frames), h(self.score), h(self.runner_up), h(self.clock_idx), h(self.scores),
+                              self.candidates)
+
+    def bauds(self) -> list:
+        return self.cpu().bauds()
+
+
+def check_candidates(candidates) -> tuple:
+    """The candidate list of a detection as a tuple of ints (None: all of ``VALID_BIT_FRAMES``): 1 ... 36 values, each
+    one ``validate_bit_frames`` accepts; duplicates and any order are allowed."""
+    if candidates is None:
+        return VALID_BIT_FRAMES
+    cands = tuple(int(c) for c in np.asarray(candidates).reshape(-1).tolist())
+    if not 1 <= len(cands) <= _native.DETECT_MAX_CANDIDATES:
+        raise ValueError(f"{len(cands)} candidates (1 ... {_native.DETECT_MAX_CANDIDATES} expected)")
+    validate_bit_frames(cands)
+    return cands
+
+
+def detect_rates(samples, stream_offset, stream_len, candidates=None, out: RateResult | None = None, stream=None,
+                 scores: bool = False) -> RateResult:
+    """Which rate each of n streams resident in HBM was sent at: one kernel launch (``afsk_detect_rate_batch``) that
+    reads the first 4096 samples of every stream.
+
+    samples, stream_offset, stream_len   as for ``demod_batch``
+    candidates   the bit_frames values to tell apart (1 ... 36 valid ones, any order, duplicates allowed);
+                 None = all of ``VALID_BIT_FRAMES``.  They travel in the launch arguments: no upload
+    out          a RateResult to reuse (no allocation in the call; its ``scores`` must match ``candidates``)
+    scores       also return every candidate's score, int32 [n, K]
+
+    Per candidate the score is the mean absolute difference per sample between the raw samples and the rate's training
+    cycle, over every whole cycle from the Receiver's clock index (ref:327-337) to the end of the 4096-sample window
+    (include/afsk_amd.h has the integer definition).  The smallest score wins, the earliest candidate on a tie;
+    ``runner_up`` is the best score among the other candidates, ``clock_idx`` the winner's clock index.  A stream
+    shorter than 4096 samples (or of a refused length) gets bit_frames 0 and -1 elsewhere.  Rates below 48 baud
+    (bit_frames >= 1200) are legal candidates but are not reliably told apart: one or two of their cycles fit the window.
+
+    The chain: ``r = detect_rates(samples, off, ln); demod_batch(samples, off, ln, bit_frames=r.bit_frames, ...)`` --
+    ``r.bit_frames`` is a device tensor, so the demodulation takes the per-stream ("mixed") entry and nothing is copied
+    to the host in between; streams the detector gave 0 come back with status 3 (ST_INVALID_BAUD) and no bytes.  Both
+    launches capture into one graph.  Asynchronous on ``stream`` (default: torch's current stream)."""
+    torch = _torch()
+    cands = check_candidates(candidates)
+    _native.require_device()
+    if not (isinstance(samples, torch.Tensor) and samples.is_cuda and samples.dtype == torch.int16):
+        raise TypeError("samples must be an int16 CUDA tensor (HBM resident)")
+    if not samples.is_contiguous():
+        raise ValueError("samples must be contiguous")
+    n = int(stream_offset.numel())
+    dev = samples.device
+    _check_index_tensors(dev, stream_offset, stream_len)
+    if int(stream_len.numel()) != n:
+        raise ValueError(f"{n} stream offsets for {int(stream_len.numel())} stream lengths")
+    fresh = out is None
+    if out is None:
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        out = RateResult(i32(n), i32(n), i32(n), i32(n), i32(n, len(cands)) if scores else None, cands)
+    else:
+        want = {"bit_frames": (n,), "score": (n,), "runner_up": (n,), "clock_idx": (n,)}
+        if scores or out.scores is not None:
+            want["scores"] = (n, len(cands))
+        for name, shape in want.items():
+            t = getattr(out, name)
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape
+                    and t.is_contiguous()):
+                raise ValueError(f"out.{name} must be a contiguous int32 tensor of shape {shape}")
+        _same_device(dev, **{"out_" + name: getattr(out, name) for name in want})
+        out.candidates = cands
+    c_arr = (C.c_int32 * len(cands))(*cands)
+    with torch.cuda.device(dev):
+        if fresh:
+            _order_after_current(stream, dev)
+        _native.check(_native.lib().afsk_detect_rate_batch(
+            samples.data_ptr(), stream_offset.data_ptr(), stream_len.data_ptr(), n, c_arr, len(cands),
+            out.bit_frames.data_ptr(), out.score.data_ptr(), out.runner_up.data_ptr(), out.clock_idx.data_ptr(),
+            None if out.scores is None else out.scores.data_ptr(), _stream_ptr(stream, dev)))
+    return out
+
+
 def _split_host_arrays(stream_len_host, bit_frames, segment_symbols):
     """The host-side arguments of a split plan as contiguous int32 arrays, checked before any device is touched."""
     lens = np.ascontiguousarray(np.asarray(stream_len_host, dtype=np.int64).reshape(-1))

@@ -154,3 +154,6 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
 // The packed segment list of a progressive push (afsk_live_segments_layout / afsk_live_pack_tap: what the payload tap
 // handed out compacted into a count, records and bytes), last: it uses the event list's scan helpers.
 #include "afsk_live_segments.hip"
+// The rate detector (afsk_detect_rate_batch: which candidate bit_frames a stream was sent at, from its first 4096
+// samples), for the same reason.
+#include "afsk_detect.hip"

@@ -503,6 +503,62 @@ def load_batch(receivers, filenames, string: bool = False):
     return out
 
 
+def _ingest_sources(sources, device=None):
+    """File names (through ``batch.load_wav_batch``) or int16 arrays (through ``batch.upload_streams``) as the device
+    layout; a mix of the two is refused."""
+    from . import batch
+    srcs = list(sources)
+    is_name = [isinstance(s, (str, bytes, os.PathLike)) for s in srcs]
+    if any(is_name) and not all(is_name):
+        raise TypeError("sources must be all file names or all int16 arrays")
+    if srcs and all(is_name):
+        return batch.load_wav_batch(srcs, device)
+    return batch.upload_streams([np.ascontiguousarray(s, dtype=np.int16) for s in srcs], device)
+
+
+def detect_baud(sources, candidates=None, device=None) -> list:
+    """The baud rate of every source -- .wav file names or int16 arrays -- detected on the GPU from its first 4096
+    samples (``batch.detect_rates``); None for a source shorter than that.  ``candidates``: the bit_frames values
+    (48000 // baud) to tell apart, default all 36 of ``batch.VALID_BIT_FRAMES``."""
+    from . import batch
+    cands = batch.check_candidates(candidates)
+    srcs = list(sources)
+    if not srcs:
+        return []
+    samples, off, ln, _ = _ingest_sources(srcs, device)
+    return batch.detect_rates(samples, off, ln, cands).bauds()
+
+
+def load_batch_auto(filenames, candidates=None, string: bool = False, amp_end_threshold=14000, max_score=None):
+    """``Receiver.load`` for many files of UNKNOWN baud rate: one parallel .wav ingest, one detection launch
+    (``batch.detect_rates``) and one demodulation launch that takes the detected rates straight from device memory.
+    Returns ``(baud, payload)`` per file; ``(None, b"")`` for a file shorter than 4096 samples, or whose detection
+    score exceeds ``max_score`` (the mean absolute difference per sample from the detected rate's training cycle,
+    0 ... 65535; None = accept every detection).  Rates below 48 baud are not reliably told apart."""
+    import torch
+    from . import batch
+    cands = batch.check_candidates(candidates)
+    if max_score is not None and not isinstance(max_score, (int, float, np.integer, np.floating)):
+        raise TypeError("max_score must be a number or None")
+    names = list(filenames)
+    if not names:
+        return []
+    samples, off, ln, max_len = batch.load_wav_batch(names)
+    rates = batch.detect_rates(samples, off, ln, cands)
+    # (a row sized from the smallest candidate holds whatever rate is detected)
+    stride = batch.out_stride_for(max_len, min(cands))
+    res = batch.demod_batch(samples, off, ln, rates.bit_frames, amp_end_threshold, out_stride=stride)
+    torch.cuda.synchronize()
+    found = rates.cpu()
+    out = []
+    for bf, score, data in zip(found.bit_frames, found.score, res.payloads()):
+        if bf <= 0 or (max_score is not None and score > max_score):
+            out.append((None, _text_or_bytes(b"", string)))
+        else:
+            out.append((SAMPLE_RATE // int(bf), _text_or_bytes(data, string)))
+    return out
+
+
 _MAX_STREAM_LEN = (1 << 30) - (1 << 15)      # AFSK_MAX_STREAM_LEN of the C-ABI
 
 

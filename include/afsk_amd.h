@@ -933,6 +933,49 @@ extern int afsk_live_pack_tap(int32_t n_channels, int32_t slots, int32_t tap_cap
                               void *segments, int32_t max_segments, int64_t max_bytes, void *hip_stream);
 
 /*
+ * Rate detection (an addition, no reference counterpart: the reference's Receiver is told its baud rate): which of
+ * n_cand candidate bit_frames values each stream was sent at, decided on the device from the stream's first
+ * AFSK_SYNC_WINDOW samples, so that out_bit_frames feeds the bit_frames argument of afsk_demod_batch / _ex directly --
+ * both launches on one stream, nothing copied to the host in between.
+ *
+ * For a stream with stream_len[s] >= 4096, x = its first 4096 raw samples, and a candidate bf with tc = the training
+ * cycle of that rate (mark ++ space, 2 bf samples, :88-91), all in integers:
+ *   total(i) = sum_{j < 2bf} |tc[j] - x[i + j]|       for i in [0, 4096 - 2bf)   (the sums of :327-331)
+ *   d(i)     = total(i) / (2bf);  ci(bf) = the first i with minimal d(i)         (the Receiver's clock index, :332-337)
+ *   n        = (4096 - 2bf - 1 - ci) / (2bf) + 1                                 (the whole cycles at ci, ci + 2bf, ...
+ *                                                                                 that start inside the search range)
+ *   score(bf) = (sum_{k < n} total(ci + k 2bf)) / (n 2bf)                        (0 ... 65535: the mean absolute
+ *                                                                                 difference per sample over them)
+ * The detected rate is the candidate of smallest score; on a tie the earliest position of the list wins (so duplicate
+ * candidates are legal).  The minimum d(ci) of ONE cycle is not enough: a short window (8 samples at bf = 4) matches
+ * noise somewhere among 4088 offsets.  Candidates with bf >= 1200 (below 48 baud) are legal but not reliably told
+ * apart: at most one or two of their cycles fit the window.
+ *
+ *  cand_bit_frames_host  [n_cand] HOST array, copied into the launch arguments before the call returns (no upload, no
+ *                        allocation: the launch captures into a graph); 1 <= n_cand <= AFSK_DETECT_MAX_CANDIDATES
+ *  out_bit_frames   [n] the detected candidate; 0 for a stream that is not examined
+ *  out_score        [n] its score; -1 for such a stream
+ *  out_runner_up    [n] the smallest score among the OTHER positions of the list; -1 with one candidate or for such a
+ *                       stream
+ *  out_clock_idx    [n] ci of the detected candidate; -1 for such a stream
+ *  out_scores       [n, n_cand] every candidate's score (-1 for such a stream), or NULL
+ * A stream shorter than 4096 samples, or of a length outside 0 ... AFSK_MAX_STREAM_LEN, is not examined and nothing of
+ * it is read; afsk_demod_batch answers its bit_frames of 0 with AFSK_ST_INVALID_BAUD and no bytes.  Streams may start
+ * at any sample offset, as for afsk_demod_batch.  All arrays but the candidates are DEVICE pointers.
+ *
+ * One launch, a workgroup per stream (afsk_detect.hip), asynchronous on hip_stream.  AFSK_E_INVALID_ARG for n_cand
+ * outside 1 ... 36, a negative n_streams or a NULL pointer (out_scores excepted); AFSK_E_INVALID_BAUD for a candidate
+ * afsk_demod_batch_uniform would refuse; n_streams == 0 returns AFSK_OK without a launch; AFSK_E_NO_DEVICE without a
+ * device.  (Declared `extern int`: afskmodem_amd/_native.py binds it from a table of its own, DETECT_SIGNATURES.)
+ */
+#define AFSK_DETECT_MAX_CANDIDATES 36 /* every bit_frames value with a Receiver: the multiples of 4 below 2048 that divide 48000 */
+extern int afsk_detect_rate_batch(const int16_t *samples, const int64_t *stream_offset, const int32_t *stream_len,
+                                  int32_t n_streams, const int32_t *cand_bit_frames_host, int32_t n_cand,
+                                  int32_t *out_bit_frames, int32_t *out_score, int32_t *out_runner_up,
+                                  int32_t *out_clock_idx, int32_t *out_scores /* [n, n_cand] or NULL */,
+                                  void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
