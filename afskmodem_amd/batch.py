@@ -159,7 +159,8 @@ class DemodResult:
     term_frame: "object"
     status: "object"
     # soft outputs, present only for demod_batch(..., diagnostics=True)
-    corrected: "object" = None   # int32 [n] codewords with a non-zero Hamming syndrome
+    corrected: "object" = None   # int32 [n] codewords with a non-zero Hamming syndrome; 0 for a stream the demodulator
+                                 # refuses (status TOO_SHORT, INVALID_BAUD, BAD_LENGTH), also when ``out=`` is reused
     margins: "object" = None     # int32 [n, margin_stride] space_diff - mark_diff per symbol
 
     def symbols_demodulated(self, bit_frames) -> "object":

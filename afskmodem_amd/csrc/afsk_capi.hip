@@ -899,6 +899,7 @@ int afsk_demod_batch_ex(const int16_t* samples, const int64_t* stream_offset,
     if (!samples || !stream_offset || !stream_len || !bit_frames || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
+    if (int rc = afsk::clear_corrected(o.corrected, n_streams, (hipStream_t)hip_stream)) return rc;
     afsk::DemodArgs a = o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold, n_streams);
     a.bit_frames = bit_frames;
     hipError_t e = afsk::launch_demod(a, (hipStream_t)hip_stream);
@@ -920,6 +921,7 @@ int afsk_demod_batch_uniform(const int16_t* samples, const int64_t* stream_offse
     if (!samples || !stream_offset || !stream_len || o.missing())
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
+    if (int rc = afsk::clear_corrected(o.corrected, n_streams, (hipStream_t)hip_stream)) return rc;
     afsk::DemodArgs a = o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold, n_streams);
     a.uniform_bit_frames = bit_frames;
     hipError_t e = afsk::launch_demod_uniform(a, (hipStream_t)hip_stream);
@@ -981,6 +983,7 @@ int afsk_demod_batch_grouped(const afsk_group_plan* plan, const int16_t* samples
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
     if (int rc = require_device()) return rc;
     if (int rc = afsk::plan_on_current_device(plan->p.device)) return rc;
+    if (int rc = afsk::clear_corrected(o.corrected, plan->p.n, (hipStream_t)hip_stream)) return rc;
     hipError_t e = plan->p.launch(o.args<afsk::DemodArgs>(samples, stream_offset, stream_len, amp_end_threshold,
                                                           plan->p.n), (hipStream_t)hip_stream);
     return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch demod_kernel (grouped)");

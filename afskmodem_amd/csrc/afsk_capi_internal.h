@@ -77,6 +77,21 @@ struct DemodOutputs {
     }
 };
 
+// out[i] = 0 for i < n: one small kernel on `stream` (afsk_gate.hip).  A weak reference: a host-only test build of
+// afsk_capi.hip alone links stub launchers for the kernels of afsk_kernels.h and may not know this one; the library
+// always holds it, and a call without it is an error, never a silent skip.
+hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t stream) __attribute__((weak));
+
+// out_corrected[s] is 0 for a stream the demodulator refuses, and the one-wave kernels' refusal branch stores the five
+// int32 fields only: zero the n entries on the launch's stream ahead of the launch (capture-safe: one more kernel node
+// in front of the demod kernel's).  Nothing for a launch without soft outputs.
+inline int clear_corrected(int32_t* corrected, int64_t n, hipStream_t stream) {
+    if (!corrected || n <= 0) return AFSK_OK;
+    if (&launch_clear_i32 == nullptr) return fail(AFSK_E_HOST, "out_corrected: clear_i32_kernel is not linked into this build");
+    hipError_t e = launch_clear_i32(corrected, n, stream);
+    return e == hipSuccess ? AFSK_OK : hip_fail(e, "launch clear_i32_kernel (out_corrected)");
+}
+
 // The device state of a handle (a split plan, a live receiver or transmitter): one allocation on the device that was
 // current at creation, freed with the handle (whose launches the caller has synchronised).  afsk_capi.hip includes
 // this header but calls none of it: its test build runs against a fake runtime without hipMemsetAsync.

@@ -11,6 +11,7 @@
 //                     (ref:316), repeat for the next receive() call; optionally (r6) it also lays the
 //                     bursts out as fixed demodulator slots (absolute offset + length per slot).
 #include "afsk_kernels.h"
+#include "afsk_capi_internal.h"      // (declares launch_clear_i32, defined below)
 
 namespace afsk {
 
@@ -128,6 +129,22 @@ hipError_t launch_gate(const GateArgs& a, hipStream_t stream) {
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(gate_scan_kernel, dim3((a.n_streams + 255) / 256), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// out[i] = 0 for i < n (clear_corrected, afsk_capi_internal.h).  A kernel and not hipMemsetAsync: the memset node of a
+// captured push replayed with garbage in the array on the MI355X runtime (tests/test_gpu_live_threshold.py:
+// test_graph_captured_push_matches_eager), a kernel node replays like every other launch of the library.
+__global__ __launch_bounds__(256) void clear_i32_kernel(int32_t* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = 0;
+}
+
+hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(clear_i32_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, out, n);
     return hipGetLastError();
 }
 

@@ -456,6 +456,10 @@ int live_stored_demod(afsk_live* live, const LiveArgs& g, const DemodOutputs& o,
     const LiveLayout& L = live->L;
     uint8_t* d = live->state.ptr();
     hipError_t e;
+    // an unused slot reports 0 corrected codewords; once for all classes, which share the arrays through their index
+    // lists (the grouped entry below clears them itself)
+    if (!live->classes.empty() || !live->plan)
+        if (int rc = clear_corrected(o.corrected, L.n * L.slots, st)) return rc;
     // two or more squelch classes: the demod kernels once per class, each over its own list of slots
     for (const SquelchClasses::Class& k : live->classes) {
         DemodArgs a = o.args<DemodArgs>(g.rows, g.slot_off, g.slot_len, k.amp_end, k.count);

@@ -97,6 +97,7 @@ __global__ __launch_bounds__(64) void split_clock_kernel(SplitArgs a) {
         if (lane == 0) {
             a.out_nbytes[s] = 0; a.out_nbits[s] = 0; a.out_clock_idx[s] = -1;
             a.out_term_frame[s] = -1; a.out_status[s] = status;
+            if (a.out_corrected) a.out_corrected[s] = 0;
             a.ci[s] = -1;
         }
         return;

@@ -115,7 +115,10 @@ int afsk_demod_batch(const int16_t *samples, const int64_t *stream_offset,
  * reference computes and discards:
  *
  *  out_corrected  [n] codewords of ECC.decode's input (floor(nbits/7) of them, :156-157) whose
- *                 syndrome (:146-147) was non-zero, i.e. single-bit corrections applied
+ *                 syndrome (:146-147) was non-zero, i.e. single-bit corrections applied.  0 for a
+ *                 stream the demodulator refuses (status AFSK_ST_TOO_SHORT, AFSK_ST_INVALID_BAUD or
+ *                 AFSK_ST_BAD_LENGTH), whatever the array held before the call -- in every entry
+ *                 that takes out_corrected
  *  out_margins    [n, margin_stride] per demodulated symbol k (sample clock_idx + k*bf),
  *                 space_diff - mark_diff of __decodeBit (:348-349): > 0 decodes as 1, <= 0
  *                 as 0 (:350-351).  Written for the symbols the reference demodulated:
@@ -158,7 +161,7 @@ int afsk_demod_batch_uniform(const int16_t *samples, const int64_t *stream_offse
  * 8192 for a ragged plan, so that the streams in flight stay close in memory), so that the wavefronts resident on a
  * compute unit run the same rate's code: 3 - 12 % faster than stream order when four or more rates are mixed
  * (below that the plan keeps stream order; one rate: the kernel of afsk_demod_batch_uniform).  Nothing but a
- * kernel launch: asynchronous on hip_stream like every device entry, safe inside a stream capture, and
+ * kernel launch (with out_corrected: a small kernel that zeroes it first): asynchronous on hip_stream like every device entry, safe inside a stream capture, and
  * calls may share a plan freely.  Outputs land at the ORIGINAL stream numbers, bit for bit what
  * afsk_demod_batch_ex writes for the same bit_frames[] (a stream with an invalid bit_frames gets status
  * AFSK_ST_INVALID_BAUD).  afsk_demod_batch (bit_frames[] in device memory, streams in the caller's order)
@@ -453,7 +456,8 @@ int afsk_gate_batch_slots(const int16_t *samples, const int64_t *stream_offset,
  *                       out_flags       int32 [n_channels, slots] AFSK_LIVE_* bits
  *                       out_bytes ... margin_stride  the DemodOutputs of afsk_demod_batch_uniform over the
  *                                       n_channels * slots slots (rows / arrays indexed by slot)
- *                     An unused slot has length 0 (flags 0) and demod status AFSK_ST_TOO_SHORT.  A burst longer than
+ *                     An unused slot has length 0 (flags 0), demod status AFSK_ST_TOO_SHORT and, like every
+ *                     stream the demodulator refuses, 0 in out_corrected whatever the push before left there.  A burst longer than
  *                     max_burst_len is gated exactly like any other; the samples beyond the capacity are not stored,
  *                     and when it closes it is reported with its true start and length (at most 2^31 - 2048),
  *                     AFSK_LIVE_OVERFLOW and status AFSK_ST_TOO_SHORT: not demodulated.  chunk_len > max_chunk_len, a

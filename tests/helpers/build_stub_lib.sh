@@ -12,6 +12,8 @@ cat > "$W/stubs.hip" <<S
 #include <mutex>
 namespace afsk {
 hipError_t launch_gate(const GateArgs&, hipStream_t) { return hipSuccess; }
+// (clear_corrected: the one launcher that does its work here, on the "device" memory that is host memory)
+hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t) { for (int64_t i = 0; i < n; i++) out[i] = 0; return hipSuccess; }
 // the demod launchers remember what they were asked to launch ("device" memory is host memory here): the test reads
 // the walk order of a plan back through afsk_stub_last_launch
 static DemodArgs g_last; static int g_last_kind = 0;        // 1 = per-stream kernel, 2 = uniform kernel

@@ -250,6 +250,36 @@ def test_group_plan_buckets(stub):
     assert stub.afsk_group_plan_destroy(h) == 0
 
 
+def test_device_entries_clear_corrected_ahead_of_the_launch(stub):
+    """out_corrected[s] is 0 for a refused stream, and the one-wave kernels' refusal branch does not store it: the three
+    device entries zero exactly its n int32 ahead of their launch (clear_corrected; the stub demod launchers write
+    nothing, so what is left is its work); the other arrays, and a call without soft outputs, are left alone."""
+    n = 12
+    bf = np.array([40, 160, 40, 20, 7, 160, 40, 0, 128, 500, 40, 160], np.int32)
+    h = C.c_void_p()
+    assert stub.afsk_group_plan_create(p32(bf), n, C.byref(h)) == 0
+    x = np.zeros(64, np.int16); off = np.zeros(n, np.int64); ln = np.zeros(n, np.int32)
+    head = (x.ctypes.data, off.ctypes.data, ln.ctypes.data)
+    for entry in ("ex", "uniform", "grouped"):
+        i32 = [np.full(n, 77, np.int32) for _ in range(5)]
+        corr = np.full(n + 4, 77, np.int32)                     # two guard elements on either side
+        margins = np.full((n, 3), 77, np.int32)
+        for soft in ((corr[2:].ctypes.data, margins.ctypes.data, 3), (corr[2:].ctypes.data, None, 0), (None, None, 0)):
+            corr[:] = 77
+            outs = (None, 0, *(a.ctypes.data for a in i32), *soft, None)
+            if entry == "ex":
+                rc = stub.afsk_demod_batch_ex(*head, bf.ctypes.data, 14000, n, *outs)
+            elif entry == "uniform":
+                rc = stub.afsk_demod_batch_uniform(*head, 40, 14000, n, *outs)
+            else:
+                rc = stub.afsk_demod_batch_grouped(h, *head, 14000, *outs)
+            assert rc == 0 and stub.afsk_sync(None) == 0, entry
+            want = 77 if soft[0] is None else 0
+            assert (corr[2: n + 2] == want).all() and (corr[:2] == 77).all() and (corr[n + 2:] == 77).all(), (entry, soft)
+            assert all((a == 77).all() for a in i32) and (margins == 77).all(), entry
+    assert stub.afsk_group_plan_destroy(h) == 0
+
+
 def _walk(stub, n):
     """(kind, index list or None, uniform bit_frames) of the last demod launch of the stub library."""
     idx = np.full(n, -1, np.int32)

@@ -241,8 +241,10 @@ def test_soft_outputs_golden_cases(golden, torch_cuda):
 
 def test_soft_outputs_noise_vs_oracle(torch_cuda):
     """Soft outputs on noisy 1 s streams at every fast-path baud plus two generic ones; the
-    margins row is compared over exactly the symbols the reference demodulated, and a narrow
-    margin_stride truncates rows without touching the neighbours."""
+    margins row is compared over exactly the symbols the reference demodulated, also with a narrow
+    margin_stride that truncates the rows.  (That a truncated row leaves its neighbours alone is not visible here --
+    the buffers start zero-filled and only the leading symbols are compared: tests/test_gpu_soft_large.py checks the
+    write footprint against sentinels.)"""
     torch = torch_cuda
     for bauds, snrs in (((1200,), [20, 8, 5, 3, 0]), ((2400,), [12, 6, 2]), ((300,), [12, 6, 2]),
                         ((600, 4000), [10, 4]), ((300, 1200, 2400, 600), [9, 5]),

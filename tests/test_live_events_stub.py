@@ -160,7 +160,9 @@ def test_the_push_entry_then_the_pack_entry_launch_the_pushs_kernels_then_the_pa
     alone = launches(logged)
     sink = "stored" if kind == "stored" else "stream"
     assert push_cell(alone[0]) == (sink, False, False)
-    assert alone[1:] == (["demod"] if kind == "stored" else [])
+    # (a stored push with out_corrected zeroes that array ahead of its demod launch: clear_corrected)
+    rest = ["clear" if "clear_i32_kernel" in k else k for k in alone[1:]]
+    assert rest == (["clear", "demod"] if kind == "stored" else [])
     # push, then pack: the push's launches followed by the pack's
     assert logged.afsk_live_push(*b.push_args(h)) == 0
     assert logged.afsk_live_pack(*b.pack_args()) == 0

@@ -136,9 +136,11 @@ def test_a_ragged_push_launches_the_ragged_kernel_and_as_many_launches_as_the_pl
     launches(stub)
     assert stub.afsk_live_push(*b.plain(h)) == 0
     first = launches(stub)
-    assert first[0] == plain and set(first[1:]) <= {"demod"}
-    # two launches for a stored push (one more per further squelch class), one for a streaming push
-    assert len(first) == {"stored": 2, "stored_thr": 3, "stored_mixed": 2}.get(kind, 1)
+    assert first[0] == plain and set(first[2:]) <= {"demod"}
+    # three launches for a stored push with out_corrected -- the push kernel, the kernel that zeroes that array
+    # (clear_corrected), the demod -- and one more demod per further squelch class; one for a streaming push
+    assert len(first) == {"stored": 3, "stored_thr": 4, "stored_mixed": 3}.get(kind, 1)
+    assert first[1:2] == (["clear_i32_kernel"] if kind.startswith("stored") else [])
     for lens, mask, flush in ((True, True, 0), (True, False, 1), (False, True, 0), (False, False, 0)):
         assert stub.afsk_live_push_ragged(*b.ragged(h, lens=lens, mask=mask, flush=flush)) == 0
         assert launches(stub) == [ragged] + first[1:], (lens, mask, flush)

@@ -11,6 +11,7 @@ cat > "$W/stubs.hip" <<S
 #include "$ROOT/afskmodem_amd/csrc/afsk_kernels.h"
 namespace afsk {
 hipError_t launch_gate(const GateArgs&, hipStream_t) { return hipErrorUnknown; }
+hipError_t launch_clear_i32(int32_t*, int64_t, hipStream_t) { return hipErrorUnknown; }
 hipError_t launch_demod(const DemodArgs&, hipStream_t) { return hipErrorUnknown; }
 hipError_t launch_demod_uniform(const DemodArgs&, hipStream_t) { return hipErrorUnknown; }
 hipError_t launch_modulate(ModulateArgs, int32_t, hipStream_t) { return hipErrorUnknown; }
