@@ -813,6 +813,8 @@ extern int afsk_live_tx_pull_ragged(afsk_live_tx *tx, int16_t *out, int64_t out_
  * still holds the true count and n_bytes, so the host sees that the list is short and reads the slot arrays.  Nothing is
  * written outside the header, the first `stored` records, the first stored_bytes payload bytes and the scratch.
  * Only n_closed is read for every channel: the slot arrays and the rows are read for slots k < n_closed[c] alone.
+ * Channel c reports clamp(n_closed[c], 0, slots) bursts: a value outside [0, slots] counts as the nearer end, in count
+ * and in the records alike.  On the outputs of a real push the clamp changes nothing.
  *
  *  afsk_live_events_layout  host-only, needs no device: the offsets of the records and of the payload part and the size
  *                           of the events buffer for max_events records and max_bytes payload bytes

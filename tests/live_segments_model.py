@@ -13,6 +13,10 @@ that order.  The header holds the true ``count`` and ``n_bytes``; ``stored = min
 are written iff the record is stored and its start plus its length is at most ``max_bytes``; ``stored_bytes`` is the
 start of the first record whose data are not written, or ``n_bytes`` when all are.
 
+``pack`` walks the segments in Python and is the plain statement of the rules; ``pack_fast`` is the same function of
+the same arrays by cumulative sums, for pushes of more channels and wider tap rows than a Python loop or a host copy of
+the rows could take (tests/test_live_segments_host.py holds the two equal, field for field and byte for byte).
+
 It is the expected value of the GPU tests and the source of the hand-built buffers of the host tests.  It never sees a
 kernel's output."""
 import numpy as np
@@ -74,6 +78,63 @@ def pack(arrays, max_segments, max_bytes):
     return header, np.array(recs, SEGMENT), bytes(data)
 
 
+def pack_fast(arrays, max_segments, max_bytes):
+    """``pack`` without a loop over the channels and without the tap bytes: ``arrays`` in the order of NAMES, where
+    ``tap_bytes`` is the tap rows or their ``tap_cap`` alone.  Returns ``(header, records, copies)``: the header and the
+    records are ``pack``'s; ``copies`` is int64 [stored, 4], per stored record ``(source row, source start, length,
+    destination offset)`` of the data bytes that are written -- ``tap_bytes[row, start : start + length]`` lands at
+    ``destination`` of the data part -- with length 0 and destination -1 where the record's data are not written
+    (``gather`` makes ``pack``'s data of it)."""
+    n_closed, burst_start, burst_len, flags, nbytes, tap_bytes, tap_n, tap_len, open_start, open_nbytes = arrays
+    n, slots = tap_len.shape
+    cap = tap_bytes if isinstance(tap_bytes, (int, np.integer)) else tap_bytes.shape[1]
+    nc = np.clip(np.asarray(n_closed, np.int64), 0, slots)
+    tn = np.clip(np.asarray(tap_n, np.int64), 0, cap)
+    # a table of n rows and slots + 1 columns: the final segments' columns, then the open segment's
+    ln = np.zeros((n, slots + 1), np.int64)
+    at = np.zeros(n, np.int64)
+    for k in range(slots):
+        ln[:, k] = np.where(k < nc, np.clip(tap_len[:, k].astype(np.int64), 0, tn - at), 0)
+        at += ln[:, k]
+    has_open = (tn - at > 0) & (np.asarray(open_start) >= 0)
+    ln[:, slots] = np.where(has_open, tn - at, 0)
+    valid = np.concatenate([np.arange(slots)[None, :] < nc[:, None], has_open[:, None]], axis=1)
+    pick = np.flatnonzero(valid.reshape(-1))                        # channel ascending, slots ascending, the open one
+    c, k = pick // (slots + 1), pick % (slots + 1)
+    fin = k < slots
+    kf = np.where(fin, k, 0)
+    length = ln.reshape(-1)[pick]
+    src = (np.cumsum(ln, axis=1) - ln).reshape(-1)[pick]
+    end = np.cumsum(length)
+    off = end - length
+    count = pick.size
+    stored = min(count, max_segments)
+    sl = slice(0, stored)
+    recs = np.zeros(stored, SEGMENT)
+    recs["channel"], recs["slot"] = c[sl], np.where(fin, k, -1)[sl]
+    recs["burst_start"] = np.where(fin, burst_start[c, kf], np.asarray(open_start)[c])[sl]
+    recs["burst_len"] = np.where(fin, burst_len[c, kf], 0)[sl]
+    recs["flags"] = np.where(fin, flags[c, kf], 0)[sl]
+    before = np.where(fin, np.asarray(nbytes, np.int64)[c * slots + kf], np.asarray(open_nbytes, np.int64)[c]) - length
+    recs["offset"] = ((before + 2 ** 31) % 2 ** 32 - 2 ** 31)[sl]      # (as the device's 32-bit subtraction leaves it)
+    recs["length"] = length[sl]
+    written = (end <= max_bytes)[sl]
+    copies = np.stack([c[sl], src[sl], np.where(written, length[sl], 0), np.where(written, off[sl], -1)],
+                      axis=1).astype(np.int64).reshape(stored, 4)
+    header = np.array([(count, stored, int(end[-1]) if count else 0, int(copies[:, 2].sum()), 0)], HEADER)
+    return header, recs, copies
+
+
+def gather(tap_bytes, copies):
+    """The bytes a list of ``copies`` (``pack_fast``) writes, in the order of their destinations: the written data
+    part.  The written runs lie back to back from 0 on."""
+    c = copies[copies[:, 2] > 0]
+    end = np.cumsum(c[:, 2])
+    assert np.array_equal(c[:, 3], end - c[:, 2])
+    within = np.arange(int(end[-1]) if c.size else 0) - np.repeat(end - c[:, 2], c[:, 2])
+    return tap_bytes[np.repeat(c[:, 0], c[:, 2]), np.repeat(c[:, 1], c[:, 2]) + within].tobytes()
+
+
 def buffer(header, records, data, max_segments, max_bytes, fill=0x5A):
     """The segments buffer a pack of these capacities leaves behind, without the scratch: header, ``max_segments``
     record places, ``max_bytes`` data places; what was not written holds ``fill``."""
@@ -130,9 +191,8 @@ def random_tap(rng, n, slots, cap, pattern, marker=0xEE, span=256):
         if rest > 0:
             open_start[c] = -1 if pattern == "orphan" and rng.integers(0, 2) == 0 else int(rng.integers(0, 1 << 40)) * 2048
             open_nbytes[c] = rest + int(rng.integers(0, 1 << 16))
-    tap_bytes = np.full((n, cap), marker, np.uint8)
-    for c in np.nonzero(tap_n)[0].tolist():
-        tap_bytes[c, : tap_n[c]] = rng.integers(0, marker, int(tap_n[c]))
+    tap_bytes = rng.integers(0, marker, (n, cap), dtype=np.uint8)
+    tap_bytes[np.arange(cap)[None, :] >= tap_n[:, None]] = marker
     used = np.arange(slots)[None, :] < nc[:, None]
     burst_start = np.where(used, rng.integers(0, 1 << 40, (n, slots)) * 2048, -7).astype(np.int64)
     burst_len = np.where(used, rng.integers(1, 64, (n, slots)) * 2048, -7).astype(np.int32)

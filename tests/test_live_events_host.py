@@ -170,3 +170,69 @@ def test_live_events_returns_text_like_bursts():
     ev = live.LiveEvents(M.buffer(h, recs, pay, 4, 32), 4, 32)
     assert ev.bursts(string=True) == [(1, 2048, 4096, "hello"), (1, 8192, 2048, b"")]
     assert ev.bursts() == [(1, 2048, 4096, b"hello"), (1, 8192, 2048, b"")]
+
+
+# ------------------------------------------------------------------------------------- the model's two forms agree
+
+def same_pack(arrays, max_events, max_bytes, tag):
+    """``pack_fast`` -- over the rows, and over their stride alone -- is ``pack``: header, records, payload."""
+    h, recs, pay = M.pack(*arrays, max_events, max_bytes)
+    stride = arrays[4].shape[1]
+    for rows in (arrays[4], stride):
+        fh, frecs, copies = M.pack_fast(*arrays[:4], rows, arrays[5], max_events, max_bytes)
+        assert fh.dtype == M.HEADER and fh.tobytes() == h.tobytes(), (tag, fh, h)
+        assert frecs.dtype == M.EVENT and frecs.tobytes() == recs.tobytes(), tag
+        for f in M.EVENT.names:
+            assert np.array_equal(frecs[f], recs[f]), (tag, f)
+        assert copies.shape == (recs.size, 4) and copies.dtype == np.int64
+        assert M.gather(arrays[4], copies) == pay, tag
+        written = copies[:, 2] > 0
+        assert np.array_equal(copies[written, 3], recs["payload_offset"][written])
+        assert np.array_equal(copies[:, 0], recs["channel"].astype(np.int64) * arrays[2].shape[1] + recs["slot"])
+        assert (copies[:, 1] == 0).all() and (copies[~written, 2] == 0).all()
+    return h[0], recs
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 775])
+@pytest.mark.parametrize("pattern", ["zero", "full", "sparse", "last", "first", "wild"])
+def test_pack_fast_is_pack(n, pattern):
+    rng = np.random.default_rng(1000 + n)
+    for slots in (1, 2, 3):
+        for stride in (0, 12, 172):
+            arrays = M.random_push(rng, n, slots, stride, pattern)
+            same_pack(arrays, n * slots, n * slots * stride, (slots, stride, "room"))
+            same_pack(arrays, n, 40, (slots, stride, "short"))
+
+
+def test_the_wild_pattern_meets_both_ends_of_the_clamp():
+    rng = np.random.default_rng(4)
+    n, slots, stride = 775, 2, 12
+    arrays = M.random_push(rng, n, slots, stride, "wild")
+    nc = arrays[0]
+    below, above = nc < 0, nc > slots
+    assert below.sum() > 3 and above.sum() > 3 and ((nc > 0) & ~above).sum() > 3
+    assert set(nc[below].tolist()) <= {-3, -2, -1} and set(nc[above].tolist()) <= {slots + 1, slots + 2, slots + 3}
+    h, recs = same_pack(arrays, n * slots, n * slots * stride, "wild")
+    assert h["count"] == np.clip(nc, 0, slots).sum() < np.abs(nc).sum()
+    assert not set(recs["channel"].tolist()) & set(np.nonzero(below)[0].tolist())
+    for c in np.nonzero(above)[0].tolist():                                     # every slot, and none beyond
+        assert recs["slot"][recs["channel"] == c].tolist() == list(range(slots))
+    assert (recs["burst_len"] > 0).all() and (recs["flags"] <= 3).all()        # (only slots that hold a burst)
+    assert [b[0] for b in M.slot_bursts(*arrays)] == recs["channel"].tolist()
+
+
+def test_pack_fast_is_pack_at_every_capacity_edge():
+    """The capacities of the GPU module's test_capacities_bound_what_is_written."""
+    rng = np.random.default_rng(9)
+    n, slots, stride = 2 * SPAN + 150, 2, 172
+    arrays = M.random_push(rng, n, slots, stride, "sparse")
+    full, all_recs, _ = M.pack(*arrays, n * slots, n * slots * stride)
+    count, kept = int(full["count"][0]), int(full["n_bytes"][0])
+    assert count > 8 and kept > 400
+    for max_events in (count - 1, count, count + 1):
+        for max_bytes in (kept - 1, kept, kept + 1):
+            same_pack(arrays, max_events, max_bytes, (max_events, max_bytes))
+    h, recs = same_pack(arrays, count, int(all_recs["payload_offset"][count // 2]), "cut")
+    assert (recs["payload_offset"] == -1).any() and (recs["payload_offset"] >= 0).any()
+    h, recs = same_pack(arrays, 0, 0, "nothing")
+    assert (h["count"], h["stored"], h["n_bytes"], h["stored_bytes"]) == (count, 0, kept, 0)

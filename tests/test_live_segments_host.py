@@ -260,3 +260,63 @@ def test_results_and_segments_may_alternate():
         x = result if p % 2 else host_segments(arrays, result, 3 * N, N * CAP)[0]
         assert mixed.feed(x) == text(WANT[p]), p
         assert mixed.pending() == PENDING[p], p
+
+
+# ------------------------------------------------------------------------------------- the model's two forms agree
+
+def same_pack(arrays, max_segments, max_bytes, tag):
+    """``pack_fast`` -- over the tap rows, and over their width alone -- is ``pack``: header, records, data."""
+    h, recs, data = M.pack(arrays, max_segments, max_bytes)
+    cap = arrays[5].shape[1]
+    for rows in (arrays[5], cap):
+        fh, frecs, copies = M.pack_fast((*arrays[:5], rows, *arrays[6:]), max_segments, max_bytes)
+        assert fh.dtype == M.HEADER and fh.tobytes() == h.tobytes(), (tag, fh, h)
+        assert frecs.dtype == M.SEGMENT and frecs.tobytes() == recs.tobytes(), tag
+        for f in M.SEGMENT.names:
+            assert np.array_equal(frecs[f], recs[f]), (tag, f)
+        assert copies.shape == (recs.size, 4) and copies.dtype == np.int64
+        assert M.gather(arrays[5], copies) == data, tag
+        written = copies[:, 3] >= 0
+        assert np.array_equal(copies[:, 0], recs["channel"]) and (copies[~written, 2] == 0).all()
+        assert np.array_equal(copies[written, 2], recs["length"][written])
+        assert ((copies[:, 1] >= 0) & (copies[:, 1] + recs["length"] <= cap)).all()
+    return h[0], recs
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 775])
+@pytest.mark.parametrize("pattern", M.PATTERNS)
+def test_pack_fast_is_pack(n, pattern):
+    rng = np.random.default_rng(2000 + n)
+    for slots in (1, 2, 3):
+        for cap in (1, 19, 183):
+            arrays = M.random_tap(rng, n, slots, cap, pattern)
+            same_pack(arrays, n * (slots + 1), n * cap, (slots, cap, "room"))
+            same_pack(arrays, n, 40, (slots, cap, "short"))
+
+
+def test_pack_fast_is_pack_at_every_capacity_edge():
+    """The capacities of the GPU module's test_capacities_bound_what_is_written."""
+    rng = np.random.default_rng(9)
+    n, slots, cap = 2 * SPAN + 150, 2, 19
+    arrays = M.random_tap(rng, n, slots, cap, "random")
+    segs = M.segments(*arrays)
+    count, nb = len(segs), sum(len(d) for _, d in segs)
+    assert count > 100 and nb > 400
+    for max_segments in (count - 1, count, count + 1):
+        for max_bytes in (nb - 1, nb, nb + 1):
+            same_pack(arrays, max_segments, max_bytes, (max_segments, max_bytes))
+    off = 0
+    for i, (r, d) in enumerate(segs):                       # a data part that ends inside ONE channel's run
+        nxt = segs[i + 1] if i + 1 < count else None
+        if i > count // 2 and r[1] >= 0 and len(d) > 0 and nxt and nxt[0][0] == r[0] and len(nxt[1]) > 1:
+            cut = off + len(d) + 1
+            break
+        off += len(d)
+    else:
+        raise AssertionError("no channel with two segments that hold bytes")
+    h, _ = same_pack(arrays, count, cut, "straddle")
+    assert h["stored_bytes"] == cut - 1 and h["stored"] == count
+    h, recs = same_pack(arrays, i + 1, nb, "records straddle")
+    assert h["stored_bytes"] == cut - 1 and recs["channel"][-1] == segs[i + 1][0][0]
+    h, _ = same_pack(arrays, 0, 0, "nothing")
+    assert (h["count"], h["stored"], h["n_bytes"], h["stored_bytes"]) == (count, 0, nb, 0)
