@@ -48,6 +48,8 @@ def import_reference():
 
         def read(self, n):
             f = _Stream.FEED
+            if f.get("limit") is not None and f["served"] >= f["limit"]:
+                raise EOFError("the replayed capture and its trailing silence are used up")
             lo = f["served"] * 2
             chunk = f["data"][lo: lo + 2 * n]
             f["served"] += n
@@ -496,41 +498,105 @@ def main():
                             ["burst", pb_, 1200, 0.1, None], ["zeros", 7000]],
         "partial_last_block": [["zeros", 2048], ["burst", pc, 1200, 0.1, None], ["zeros", 2048 + 777]],
     }
-    captures = {k: build_capture(v) for k, v in recipes.items()}
+    PAIRS = ((18000, 14000), (9000, 2500))
+    listen_recipes = [(name, recipe, PAIRS, False) for name, recipe in recipes.items()]
+
+    # appended: block amplitudes ON the thresholds.  ref:306 opens on amp > amp_start, ref:316 closes on amp < amp_end,
+    # and getAmplitude truncates (ref:94-98: int(sum / 2048), abs(-32768) == 32768).  A square wave of level a has
+    # amplitude a exactly; "square_adj" moves one sample so that the block sum is 2048 * a + delta.  Every recipe ends
+    # in a partial block of 777 zeros and carries its own threshold pairs; these cases also record the reference's
+    # getAmplitude of every whole block ("block_amp").  They go to a file of their own, reference_listen_edges.json
+    # (one case per line), which tests/golden_inputs.listen_cases appends to the cases above: the main fixture is one
+    # line of JSON, and it stays byte for byte what it was.
+    Z, TAIL = ["zeros", 2048], ["zeros", 777]
+
+    def sq(a):
+        return ["square", 2048, a]
+
+    ladder = [Z] + [sq(a) for a in (15999, 16000, 16001, 17999, 18000, 18001)] + [Z, Z, TAIL]
+    edge_recipes = [
+        ("start_at_threshold", [Z, sq(18000), sq(18000), sq(18001), sq(14000), sq(14001), sq(13999), Z, Z, TAIL],
+         ((18000, 14000),)),
+        ("amp_truncates", [Z, ["square_adj", 2048, 18001, 700, -1], sq(18001), ["square_adj", 2048, 14000, 1301, -1],
+                           Z, TAIL], ((18000, 14000),)),
+        ("full_scale_negative", [Z, ["const", 2048, -32768], Z, Z, TAIL], ((32767, 14000), (32768, 14000))),
+        ("inverted_pair", ladder, ((14000, 18000),)),
+        ("equal_pair", ladder, ((16000, 16000),)),
+        ("zero_thresholds", [Z, Z, sq(1), Z, Z, sq(1), Z, TAIL], ((0, 0), (0, 1))),
+        # open / close / discard with the narrowest margins: a burst every third block (the live receiver's
+        # 1 + K / 3 slot bound); the discarded block (ref:303) is loud
+        ("densest_at_threshold", [Z] + [sq(18001), sq(13999), sq(18001)] * 7 + [Z, TAIL], ((18000, 14000),)),
+    ]
+    listen_recipes += [(name, recipe, pairs, True) for name, recipe, pairs in edge_recipes]
+
     listen_cases = []
-    for name, cap in captures.items():
-        cap = np.ascontiguousarray(cap, dtype=np.int16)
+    for name, recipe, pairs, with_amps in listen_recipes:
+        cap = np.ascontiguousarray(build_capture(recipe), dtype=np.int16)
         nb = len(cap) // 2048
-        for (a_start, a_end) in ((18000, 14000), (9000, 2500)):
+        for (a_start, a_end) in pairs:
             stream_cls.FEED["data"] = cap.astype("<i2").tobytes()
             stream_cls.FEED["served"] = 0
+            # a pair whose burst no silence closes (amp < 0 never holds): the replay ends with an EOFError from the
+            # stub stream 8 blocks into the virtual silence, and the burst's first block is the one the reference
+            # had read when it logged "Recording started" (ref:307)
+            stream_cls.FEED["limit"] = (nb + 8) * 2048 if a_end <= 0 else None
+            started = []
+            real_debug = ref.Log.debug
+
+            def debug(self, message, _started=started, _real=real_debug):
+                if message == "Recording started":
+                    _started.append(stream_cls.FEED["served"] // 2048 - 1)
+                return _real(self, message)
+
+            ref.Log.debug = debug
             r = ref.Receiver(1200, a_start, a_end)
             bursts = []
             open_end = 0
-            for _ in range(16):
-                served_blocks = stream_cls.FEED["served"] // 2048
-                if served_blocks >= nb:
-                    break
-                rec = r._Receiver__listen((nb - served_blocks + 4) * 2048)
-                if rec == []:
-                    break
-                end_block = stream_cls.FEED["served"] // 2048        # blocks consumed so far
-                start_block = end_block - len(rec) // 2048
-                length = len(rec)
-                if end_block > nb:                                   # ran into the virtual silence
-                    length = (nb - start_block) * 2048
-                    open_end = 1
-                bits = r._Receiver__decodeBits(rec)
-                data = b"" if bits == "" else r._Receiver__bitsToBytes(ref.ECC.decode(bits))
-                bursts.append({"start": start_block * 2048, "len": length, "ref_len": len(rec),
-                               "bytes_hex": data.hex()})
-                if open_end:
-                    break
-            listen_cases.append({"name": name, "amp_start": a_start, "amp_end": a_end,
-                                 "n_samples": len(cap), "capture_sha256": sha(cap),
-                                 "recipe": recipes[name],
-                                 "bursts": bursts, "open_end": open_end})
-    G["listen_cases"] = listen_cases
+            try:
+                for _ in range(64):
+                    served_blocks = stream_cls.FEED["served"] // 2048
+                    if served_blocks >= nb:
+                        break
+                    n_started = len(started)
+                    try:
+                        rec = r._Receiver__listen((nb - served_blocks + 4) * 2048)
+                    except EOFError:
+                        assert stream_cls.FEED["limit"] is not None and len(started) == n_started + 1
+                        bursts.append({"start": started[-1] * 2048, "len": (nb - started[-1]) * 2048, "ref_len": None,
+                                       "bytes_hex": ""})
+                        open_end = 1
+                        break
+                    if rec == []:
+                        break
+                    end_block = stream_cls.FEED["served"] // 2048        # blocks consumed so far
+                    start_block = end_block - len(rec) // 2048
+                    assert started[-1] == start_block
+                    length = len(rec)
+                    if end_block > nb:                                   # ran into the virtual silence
+                        length = (nb - start_block) * 2048
+                        open_end = 1
+                    bits = r._Receiver__decodeBits(rec)
+                    data = b"" if bits == "" else r._Receiver__bitsToBytes(ref.ECC.decode(bits))
+                    bursts.append({"start": start_block * 2048, "len": length, "ref_len": len(rec),
+                                   "bytes_hex": data.hex()})
+                    if open_end:
+                        break
+                else:
+                    raise AssertionError(f"{name}: more receive() calls than the replay allows")
+            finally:
+                ref.Log.debug = real_debug
+                stream_cls.FEED["limit"] = None
+            case = {"name": name, "amp_start": a_start, "amp_end": a_end,
+                    "n_samples": len(cap), "capture_sha256": sha(cap),
+                    "recipe": recipe,
+                    "bursts": bursts, "open_end": open_end}
+            if with_amps:
+                case["block_amp"] = [ref.Waveforms.getAmplitude([int(v) for v in cap[2048 * b: 2048 * b + 2048]])
+                                     for b in range(nb)]
+            listen_cases.append(case)
+    G["listen_cases"] = [c for c in listen_cases if "block_amp" not in c]
+    edge_cases = [c for c in listen_cases if "block_amp" in c]
+    assert len(G["listen_cases"]) == 2 * len(recipes) and len(edge_cases) == sum(len(p) for _, _, p in edge_recipes)
 
     # ---- 5c. .wav ingest (SoundInput.loadFromFile ref:213-217 is header-agnostic)
     import wave
@@ -661,6 +727,11 @@ def main():
     with open(out, "w") as f:
         json.dump(G, f, separators=(",", ":"))
     print("wrote", out, os.path.getsize(out), "bytes;", len(cases), "decode cases")
+    out = os.path.join(HERE, "reference_listen_edges.json")
+    with open(out, "w") as f:
+        f.write('{"generator":' + json.dumps(G["generator"]) + ',"reference":' + json.dumps(G["reference"])
+                + ',"listen_cases":[\n' + ",\n".join(json.dumps(c, separators=(",", ":")) for c in edge_cases) + "\n]}\n")
+    print("wrote", out, os.path.getsize(out), "bytes;", len(edge_cases), "listen cases on the thresholds")
 
 
 if __name__ == "__main__":

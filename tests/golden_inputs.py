@@ -56,6 +56,16 @@ def build_input(case: dict) -> np.ndarray:
     return x
 
 
+def listen_cases(golden: dict) -> list:
+    """The reference's listen recordings: those of the main fixture (``golden``: reference_vectors.json, eight captures
+    at two threshold pairs), then the cases whose block amplitudes sit on a threshold
+    (tests/golden/reference_listen_edges.json: each with its own pair and the reference's ``block_amp`` per block)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_listen_edges.json")) as f:
+        return list(golden["listen_cases"]) + json.load(f)["listen_cases"]
+
+
 def build_capture(recipe) -> np.ndarray:
     """A long capture from a list of segments (used by the live-gate cases):
     ["zeros", n] | ["noise", n, seed, scale_q24] (oracle integer noise on silence) |
@@ -63,6 +73,9 @@ def build_capture(recipe) -> np.ndarray:
     ["frames", payload_hex, baud, training_time, keep] (the ideal Transmitter frames: 12000 baud, whose mark tone
     the wav writer's decimate / duplicate quirk destroys) |
     ["square", n, amplitude] (+a, -a, +a, ...) |
+    ["const", n, value] (n samples of one value) |
+    ["square_adj", n, amplitude, pos, delta] (the square wave with |x[pos]| changed by delta: a block whose sum of
+    |x| is n * amplitude + delta) |
     ["burst_level", payload_hex, baud, training_time, keep, level] (the burst with +level / -level
     instead of full scale; silence stays 0) |
     ["burst_dc", payload_hex, baud, training_time, keep, num, den, dc] (burst * num // den + dc, clipped
@@ -82,6 +95,13 @@ def build_capture(recipe) -> np.ndarray:
             parts.append(w if seg[4] is None else w[: seg[4]])
         elif kind == "square":
             parts.append(np.tile(np.array([seg[2], -seg[2]], np.int16), seg[1] // 2))
+        elif kind == "const":
+            parts.append(np.full(seg[1], seg[2], np.int16))
+        elif kind == "square_adj":
+            w = np.tile(np.array([seg[2], -seg[2]], np.int32), seg[1] // 2)
+            w[seg[3]] += int(seg[4]) if w[seg[3]] >= 0 else -int(seg[4])
+            assert -32768 <= w[seg[3]] <= 32767
+            parts.append(w.astype(np.int16))
         elif kind == "burst_level":
             w = _wav(seg[1], seg[2], seg[3])
             w = w if seg[4] is None else w[: seg[4]]

@@ -11,7 +11,7 @@ import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, batch, synth
 from afskmodem_amd.live import LiveReceiver
 from oracle import afsk_oracle as O
-from tests.golden_inputs import build_capture
+from tests.golden_inputs import build_capture, listen_cases
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -102,8 +102,9 @@ def check_demod_against_batch(torch, d_host, rows, bf, amp_end, stride):
 def test_reference_listen_cases_in_every_chunking(golden, torch_cuda, pair):
     torch = torch_cuda
     a_start, a_end = pair
-    cases = [c for c in golden["listen_cases"] if c["amp_start"] == a_start]
-    assert len(cases) == 8
+    cases = [c for c in listen_cases(golden) if c["amp_start"] == a_start]
+    # (the eight captures at both pairs, and three whose block amplitudes sit on 18000 / 14000)
+    assert len(cases) == (11 if a_start == 18000 else 8)
     caps = [build_capture(c["recipe"]) for c in cases]
     rng = np.random.default_rng(11)
     # the open-ended case alone (no padding may close its burst), all others side by side, zero padded: after their
@@ -238,7 +239,7 @@ def test_overflow_is_flagged_and_not_decoded(torch_cuda):
 
 def test_flush_starts_new_streams_and_masked_reset(golden, torch_cuda):
     torch = torch_cuda
-    cases = [c for c in golden["listen_cases"] if c["amp_start"] == 18000 and not c["open_end"]][:4]
+    cases = [c for c in listen_cases(golden) if c["amp_start"] == 18000 and not c["open_end"]][:4]
     caps = [build_capture(c["recipe"]) for c in cases]
     host, dev = padded(torch, caps)
     rx = LiveReceiver(len(caps), 40, max_burst_len=65536, max_chunk_len=5000)

@@ -100,10 +100,12 @@ def test_modulator_every_quarter_width(torch_cuda, wav_quirk):
 def test_listen_gate_vs_reference_and_oracle(golden, torch_cuda):
     """Row f2: the block-amplitude gate on the GPU against the reference-recorded burst boundaries
     (golden) and the oracle, then gate -> demod end to end through Receiver.decode_captures."""
-    from tests.golden_inputs import build_capture
+    from tests.golden_inputs import build_capture, listen_cases
     torch = torch_cuda
     for a_start, a_end in ((18000, 14000), (9000, 2500)):
-        cases = [c for c in golden["listen_cases"] if c["amp_start"] == a_start]
+        cases = [c for c in listen_cases(golden) if c["amp_start"] == a_start]
+        # (at 18000 / 14000 also the three captures whose block amplitudes sit on the thresholds)
+        assert len(cases) == (11 if a_start == 18000 else 8) and all(c["amp_end"] == a_end for c in cases)
         caps = [build_capture(c["recipe"]) for c in cases]
         samples, off, ln, max_len = batch.upload_streams(caps)
         g = batch.gate_batch(samples, off, ln, max_len, a_start, a_end, 16)
@@ -125,6 +127,8 @@ def test_listen_gate_vs_reference_and_oracle(golden, torch_cuda):
             assert got == O.gate_stream(caps[i], a_start, a_end, 16)[0]
             for b in range(len(caps[i]) // 2048):
                 assert amp[i, b] == O.get_amplitude(caps[i][2048 * b: 2048 * b + 2048]), (c["name"], b)
+            if "block_amp" in c:                                       # the reference's own getAmplitude per block
+                assert amp[i, : len(caps[i]) // 2048].tolist() == c["block_amp"], c["name"]
         r = afskmodem.Receiver(1200, a_start, a_end)
         decoded = r.decode_captures(caps)
         for c, payloads in zip(cases, decoded):
@@ -399,11 +403,11 @@ def test_gate_to_demod_chain_without_host_sync_and_as_a_graph(golden, torch_cuda
     has fewer bursts) -> demod_batch gives, slot by slot, what the compacting route (burst_streams: a nonzero, i.e. a
     synchronisation) gives burst by burst -- which the reference-recorded listen cases pin -- and the whole chain
     is captured into ONE HIP graph and replayed on new captures in the same buffer."""
-    from tests.golden_inputs import build_capture
+    from tests.golden_inputs import build_capture, listen_cases
     if entry != "uniform":
         pytest.skip("entry-independent: runs once")
     torch = torch_cuda
-    cases = [c for c in golden["listen_cases"] if c["amp_start"] == 18000]
+    cases = [c for c in listen_cases(golden) if c["amp_start"] == 18000]
     caps = [build_capture(c["recipe"]) for c in cases]
     samples, off, ln, max_len = batch.upload_streams(caps)
     mb = 4

@@ -99,8 +99,9 @@ class Model:
     """The chunked gate of live_gate_kernel over per-block amplitudes: amp(b) is the amplitude of stream block b
     (only asked for once the block is complete).  push(T) -> [(start, len, flags)] reported in that push."""
 
-    def __init__(self, amp):
+    def __init__(self, amp, amp_start=18000, amp_end=14000):
         self.amp = amp
+        self.amp_start, self.amp_end = amp_start, amp_end
         self.pos = self.mode = self.rec_start = self.rec_len = 0
 
     def push(self, T, flush=False):
@@ -112,11 +113,11 @@ class Model:
             if self.mode == 0:
                 self.mode = 1
             elif self.mode == 1:
-                if a > 18000:
+                if a > self.amp_start:
                     self.mode, self.rec_start, self.rec_len = 2, b * BLOCK, BLOCK
             else:
                 self.rec_len += BLOCK
-                if a < 14000:
+                if a < self.amp_end:
                     out.append((self.rec_start, self.rec_len, 0))
                     self.mode = 0
         self.pos += T

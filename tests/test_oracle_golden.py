@@ -147,6 +147,55 @@ def test_listen_gate_cases(golden):
                 assert O.load_frames(cap[st: st + ln], 1200, c["amp_end"]).hex() == b["bytes_hex"], c["name"]
 
 
+EDGE_LISTEN_CASES = [("start_at_threshold", 18000, 14000), ("amp_truncates", 18000, 14000),
+                     ("full_scale_negative", 32767, 14000), ("full_scale_negative", 32768, 14000),
+                     ("inverted_pair", 14000, 18000), ("equal_pair", 16000, 16000), ("zero_thresholds", 0, 0),
+                     ("zero_thresholds", 0, 1), ("densest_at_threshold", 18000, 14000)]
+
+
+def test_listen_gate_cases_on_the_thresholds(golden):
+    """The listen cases whose block amplitudes sit ON a threshold (ref:306 opens on >, ref:316 closes on <, ref:94-98
+    truncates): per block the oracle's amplitude against the reference's recorded one, the oracle's whole-capture
+    gate and the chunked Python model of the live walk (tests/test_live_host.py) in several chunkings against the
+    recorded bursts and open_end, each under the case's own pair."""
+    from tests.golden_inputs import build_capture, listen_cases
+    from afskmodem_amd import _native
+    from tests.test_live_host import Model
+    assert len(golden["listen_cases"]) == 16 and len(listen_cases(golden)) == 16 + len(EDGE_LISTEN_CASES)
+    assert listen_cases(golden)[:16] == golden["listen_cases"]
+    cases = listen_cases(golden)[16:]
+    assert [(c["name"], c["amp_start"], c["amp_end"]) for c in cases] == EDGE_LISTEN_CASES
+    for c in cases:
+        tag = (c["name"], c["amp_start"], c["amp_end"])
+        cap = build_capture(c["recipe"])
+        assert len(cap) == c["n_samples"] and sha_i16(cap) == c["capture_sha256"], tag
+        nb = len(cap) // 2048
+        assert len(cap) % 2048 == 777 and len(c["block_amp"]) == nb, tag
+        amps = [O.get_amplitude(cap[2048 * b: 2048 * b + 2048]) for b in range(nb)]
+        assert amps == c["block_amp"], tag
+        want = [(b["start"], b["len"]) for b in c["bursts"]]
+        flags = [0] * (len(want) - c["open_end"]) + [_native.LIVE_OPEN_END] * c["open_end"]
+        assert O.gate_stream(cap, c["amp_start"], c["amp_end"], 64) == (want, c["open_end"]), tag
+        for mb in (1, 2):                                   # max_bursts clamps: the first mb of them
+            got, oe = O.gate_stream(cap, c["amp_start"], c["amp_end"], mb)
+            assert got == want[:mb] and oe == (c["open_end"] if len(want) <= mb else 0), (tag, mb)
+        for T in (1, 777, 2047, 2048, 2049, 3000, len(cap)):
+            model = Model(lambda b: c["block_amp"][b], c["amp_start"], c["amp_end"])
+            got = []
+            for p in range(0, len(cap), T):
+                got += model.push(min(T, len(cap) - p), flush=p + T >= len(cap))
+            assert [(s, n) for s, n, _ in got] == want and [f for _, _, f in got] == flags, (tag, T)
+    # what the recordings must show: 18000 does not open and 14000 does not close, a sum one short of 2048 * 18001
+    # does not open, -32768 counts 32768, a pair of zeros never closes
+    by = {(c["name"], c["amp_start"], c["amp_end"]): c for c in cases}
+    spans = lambda key: [(b["start"] // 2048, b["len"] // 2048) for b in by[key]["bursts"]]  # noqa: E731
+    assert spans(("start_at_threshold", 18000, 14000)) == [(3, 4)]
+    assert spans(("amp_truncates", 18000, 14000)) == [(2, 2)]
+    assert spans(("full_scale_negative", 32767, 14000)) == [(1, 2)] and spans(("full_scale_negative", 32768, 14000)) == []
+    assert spans(("zero_thresholds", 0, 0)) == [(2, 5)] and by[("zero_thresholds", 0, 0)]["open_end"] == 1
+    assert spans(("densest_at_threshold", 18000, 14000)) == [(1 + 3 * k, 2) for k in range(7)]
+
+
 def test_pure_python_restatement_matches_reference_vectors(golden):
     """oracle/pyref.py (the interpreter-speed twin timed by bench.py) on a spread of the
     reference-generated decode cases."""
