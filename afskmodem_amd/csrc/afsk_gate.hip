@@ -165,12 +165,10 @@ hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t stream) {
 // Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged: the one kernel template over the
 // three sinks, its table of instantiations and the one host path), last: it needs all three sinks.
 #include "afsk_live_push.hip"
-// The packed event list of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into
-// a count, records and payload bytes), for the same reason.
-#include "afsk_live_events.hip"
-// The packed segment list of a progressive push (afsk_live_segments_layout / afsk_live_pack_tap: what the payload tap
-// handed out compacted into a count, records and bytes), last: it uses the event list's scan helpers.
-#include "afsk_live_segments.hip"
+// The packed lists of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into a
+// count, records and payload bytes; afsk_live_segments_layout / afsk_live_pack_tap: likewise what the payload tap of a
+// progressive push handed out; one header, scan, layout and launch path under both), for the same reason.
+#include "afsk_live_pack.hip"
 // The rate detector (afsk_detect_rate_batch: which candidate bit_frames a stream was sent at, from its first 4096
 // samples), for the same reason.
 #include "afsk_detect.hip"

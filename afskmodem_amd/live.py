@@ -310,38 +310,53 @@ def _slot_bursts(result: "LiveResult", string: bool = False, only=None, copied=N
 EVENT_DTYPE = np.dtype([("channel", "<i4"), ("slot", "<i4"), ("burst_start", "<i8"), ("burst_len", "<i4"),
                         ("flags", "<i4"), ("status", "<i4"), ("nbytes", "<i4"), ("nbits", "<i4"), ("clock_idx", "<i4"),
                         ("term_frame", "<i4"), ("payload_offset", "<i4")])
-# the 32-byte header of an events buffer
+# afsk_live_segment (include/afsk_amd.h), field for field: 32 bytes, no padding
+SEGMENT_DTYPE = np.dtype([("channel", "<i4"), ("slot", "<i4"), ("burst_start", "<i8"), ("burst_len", "<i4"),
+                          ("flags", "<i4"), ("offset", "<i4"), ("length", "<i4")])
+# the 32-byte header of an events or a segments buffer
 EVENTS_HEADER_DTYPE = np.dtype([("count", "<i4"), ("stored", "<i4"), ("n_bytes", "<i8"), ("stored_bytes", "<i8"),
                                 ("reserved", "<i8")])
+
+
+def _packed_layout(entry: str, n_channels: int, slots: int, max_records: int, max_bytes: int) -> tuple[int, int, int]:
+    """``(records_offset, bytes_offset, total_bytes)`` of a packed buffer from the C layout entry named ``entry``."""
+    ro, bo, total = C.c_int64(), C.c_int64(), C.c_int64()
+    _native.check(getattr(_native.lib(), entry)(int(n_channels), int(slots), int(max_records), int(max_bytes),
+                                                C.byref(ro), C.byref(bo), C.byref(total)))
+    return int(ro.value), int(bo.value), int(total.value)
 
 
 def events_layout(n_channels: int, slots: int, max_events: int, max_bytes: int) -> tuple[int, int, int]:
     """``(records_offset, payload_offset, total_bytes)`` of the events buffer of ``afsk_live_pack`` for ``max_events``
     records and ``max_bytes`` payload bytes (``afsk_live_events_layout``: host-only)."""
-    ro, po, total = C.c_int64(), C.c_int64(), C.c_int64()
-    _native.check(_native.lib().afsk_live_events_layout(int(n_channels), int(slots), int(max_events), int(max_bytes),
-                                                        C.byref(ro), C.byref(po), C.byref(total)))
-    return int(ro.value), int(po.value), int(total.value)
+    return _packed_layout("afsk_live_events_layout", n_channels, slots, max_events, max_bytes)
 
 
-class LiveEvents:
-    """The packed event list of one push (``afsk_live_pack``): ``buffer`` is the events buffer -- a uint8 CUDA tensor
-    (``LiveReceiver.alloc_events``) or a numpy uint8 array laid out the same way -- holding a 32-byte header, up to
-    ``max_events`` records of ``EVENT_DTYPE`` from ``records_offset`` on, in the order of ``LiveResult.bursts()``, and
-    up to ``max_bytes`` payload bytes from ``payload_offset`` on.  ``result`` is the ``LiveResult`` that was packed:
-    what did not fit the buffer is read from its slot arrays, so ``bursts()`` is always complete.  Reading copies the
-    header, then only the records and payload bytes the header counts."""
+def segments_layout(n_channels: int, slots: int, max_segments: int, max_bytes: int) -> tuple[int, int, int]:
+    """``(records_offset, data_offset, total_bytes)`` of the segments buffer of ``afsk_live_pack_tap`` for
+    ``max_segments`` records and ``max_bytes`` data bytes (``afsk_live_segments_layout``: host-only)."""
+    return _packed_layout("afsk_live_segments_layout", n_channels, slots, max_segments, max_bytes)
 
-    def __init__(self, buffer, max_events: int, max_bytes: int, records_offset: int | None = None,
-                 payload_offset: int | None = None, result: "LiveResult | None" = None):
+
+class _PackedList:
+    """A packed list of one push, as ``LiveEvents`` and ``LiveSegments`` hold it: ``buffer`` -- a uint8 CUDA tensor or
+    a numpy uint8 array laid out the same way -- holds a 32-byte header (``EVENTS_HEADER_DTYPE``), up to ``max_records``
+    records of the subclass's ``RECORD_DTYPE`` from ``records_offset`` on and up to ``max_bytes`` bytes of theirs, back
+    to back in record order, from ``bytes_offset`` on.  ``result`` is the ``LiveResult`` that was packed: what did not
+    fit the buffer is read from its arrays.  Reading copies the header, then only the records and bytes the header
+    counts; ``copied_bytes`` is what the last public read -- or the ``PayloadAssembler.feed`` that took the list --
+    brought to the host, the result's arrays read for what did not fit included."""
+    RECORD_DTYPE: np.dtype
+    NOUN: str                # "events" / "segments": alloc_<NOUN> allocates the buffer, errors name it so
+
+    def __init__(self, buffer, max_records: int, max_bytes: int, records_offset: int | None,
+                 bytes_offset: int | None, result: "LiveResult | None"):
         self.buffer = buffer
-        self.max_events, self.max_bytes = int(max_events), int(max_bytes)
+        self.max_records, self.max_bytes = int(max_records), int(max_bytes)
         self.records_offset = EVENTS_HEADER_DTYPE.itemsize if records_offset is None else int(records_offset)
-        self.payload_offset = self.records_offset + EVENT_DTYPE.itemsize * self.max_events \
-            if payload_offset is None else int(payload_offset)
+        self.bytes_offset = self.records_offset + self.RECORD_DTYPE.itemsize * self.max_records \
+            if bytes_offset is None else int(bytes_offset)
         self.result = result
-        # what the last header() / records() / payload() / bursts() copied to the host, the slot arrays read for what
-        # did not fit the buffer included
         self.copied_bytes = 0
 
     def _read(self, lo: int, hi: int) -> np.ndarray:
@@ -358,27 +373,53 @@ class LiveEvents:
 
     @property
     def count(self) -> int:
-        """Bursts the push reported, over all channels (may exceed ``max_events``)."""
+        """Records of the push, over all channels (may exceed ``max_records``)."""
         return int(self.header()["count"])
 
     @property
     def stored(self) -> int:
-        """Records in the buffer: ``min(count, max_events)``."""
+        """Records in the buffer: ``min(count, max_records)``."""
         return int(self.header()["stored"])
 
     @property
     def overflowed(self) -> bool:
-        """Whether a record or a payload did not fit the buffer (``bursts()`` then reads the slot arrays for it)."""
-        h = self.header()
+        """Whether a record or its bytes did not fit the buffer (the result's arrays are then read for it)."""
+        return self._short(self.header())
+
+    @staticmethod
+    def _short(h) -> bool:
         return bool(h["count"] > h["stored"] or h["n_bytes"] > h["stored_bytes"])
 
     def _records(self, h) -> np.ndarray:
-        n = int(h["stored"])
-        return self._read(self.records_offset, self.records_offset + EVENT_DTYPE.itemsize * n).view(EVENT_DTYPE)
+        n, dt = int(h["stored"]), self.RECORD_DTYPE
+        return self._read(self.records_offset, self.records_offset + dt.itemsize * n).view(dt)
 
     def records(self) -> np.ndarray:
-        """The first ``stored`` records as a numpy array of ``EVENT_DTYPE``."""
+        """The first ``stored`` records as a numpy array of ``RECORD_DTYPE``."""
         return self._records(self.header())
+
+    def _result(self) -> "LiveResult":
+        if self.result is None:
+            raise ValueError(f"the {self.NOUN} buffer is too small for this push and no LiveResult is referenced to "
+                             "read the rest from")
+        return self.result
+
+
+class LiveEvents(_PackedList):
+    """The packed event list of one push (``afsk_live_pack``): ``buffer`` is the events buffer -- a uint8 CUDA tensor
+    (``LiveReceiver.alloc_events``) or a numpy uint8 array laid out the same way -- holding a 32-byte header, up to
+    ``max_events`` records of ``EVENT_DTYPE`` from ``records_offset`` on, in the order of ``LiveResult.bursts()``, and
+    up to ``max_bytes`` payload bytes from ``payload_offset`` on.  ``result`` is the ``LiveResult`` that was packed:
+    what did not fit the buffer is read from its slot arrays, so ``bursts()`` is always complete.  Reading copies the
+    header, then only the records and payload bytes the header counts."""
+    RECORD_DTYPE, NOUN = EVENT_DTYPE, "events"
+    _layout = staticmethod(events_layout)
+    max_events = property(lambda self: self.max_records)
+    payload_offset = property(lambda self: self.bytes_offset)
+
+    def __init__(self, buffer, max_events: int, max_bytes: int, records_offset: int | None = None,
+                 payload_offset: int | None = None, result: "LiveResult | None" = None):
+        super().__init__(buffer, max_events, max_bytes, records_offset, payload_offset, result)
 
     def _payloads(self, h, recs) -> list:
         """The payload bytes of every record in ``recs``; None where the buffer does not hold them."""
@@ -391,11 +432,8 @@ class LiveEvents:
 
     def _from_slots(self, string: bool, only=None):
         """``_slot_bursts`` over the referenced result, its copies counted."""
-        if self.result is None:
-            raise ValueError("the events buffer is too small for this push and no LiveResult is referenced to read "
-                             "the rest from")
         copied = [0]
-        out = _slot_bursts(self.result, string, only, copied)
+        out = _slot_bursts(self._result(), string, only, copied)
         self.copied_bytes += copied[0]
         return out
 
@@ -440,21 +478,7 @@ class LiveEvents:
                  b"" if over[i] else _text_or_bytes(data[i], string)) for i, r in enumerate(recs)]
 
 
-# afsk_live_segment (include/afsk_amd.h), field for field: 32 bytes, no padding
-SEGMENT_DTYPE = np.dtype([("channel", "<i4"), ("slot", "<i4"), ("burst_start", "<i8"), ("burst_len", "<i4"),
-                          ("flags", "<i4"), ("offset", "<i4"), ("length", "<i4")])
-
-
-def segments_layout(n_channels: int, slots: int, max_segments: int, max_bytes: int) -> tuple[int, int, int]:
-    """``(records_offset, data_offset, total_bytes)`` of the segments buffer of ``afsk_live_pack_tap`` for
-    ``max_segments`` records and ``max_bytes`` data bytes (``afsk_live_segments_layout``: host-only)."""
-    ro, do, total = C.c_int64(), C.c_int64(), C.c_int64()
-    _native.check(_native.lib().afsk_live_segments_layout(int(n_channels), int(slots), int(max_segments),
-                                                          int(max_bytes), C.byref(ro), C.byref(do), C.byref(total)))
-    return int(ro.value), int(do.value), int(total.value)
-
-
-class LiveSegments:
+class LiveSegments(_PackedList):
     """The packed segment list of one progressive push (``afsk_live_pack_tap``): ``buffer`` is the segments buffer -- a
     uint8 CUDA tensor (``LiveReceiver.alloc_segments``) or a numpy uint8 array laid out the same way -- holding the
     32-byte header of an events buffer (``EVENTS_HEADER_DTYPE``), up to ``max_segments`` records of ``SEGMENT_DTYPE``
@@ -462,55 +486,14 @@ class LiveSegments:
     ``data_offset`` on, back to back in record order.  ``result`` is the ``LiveResult`` that was packed: when anything
     did not fit the buffer, ``partials()`` is read from its tap arrays, so it is always complete.  Reading copies the
     header, then only the records and data bytes the header counts."""
+    RECORD_DTYPE, NOUN = SEGMENT_DTYPE, "segments"
+    _layout = staticmethod(segments_layout)
+    max_segments = property(lambda self: self.max_records)
+    data_offset = property(lambda self: self.bytes_offset)
 
     def __init__(self, buffer, max_segments: int, max_bytes: int, records_offset: int | None = None,
                  data_offset: int | None = None, result: "LiveResult | None" = None):
-        self.buffer = buffer
-        self.max_segments, self.max_bytes = int(max_segments), int(max_bytes)
-        self.records_offset = EVENTS_HEADER_DTYPE.itemsize if records_offset is None else int(records_offset)
-        self.data_offset = self.records_offset + SEGMENT_DTYPE.itemsize * self.max_segments \
-            if data_offset is None else int(data_offset)
-        self.result = result
-        # what the last header() / records() / partials() -- or the PayloadAssembler.feed that took this list --
-        # copied to the host, the tap arrays read when something did not fit the buffer included
-        self.copied_bytes = 0
-
-    # the header and the way parts of the buffer reach the host are the events buffer's
-    _read = LiveEvents._read
-    header = LiveEvents.header
-
-    @property
-    def count(self) -> int:
-        """Segments of the push, over all channels (may exceed ``max_segments``)."""
-        return int(self.header()["count"])
-
-    @property
-    def stored(self) -> int:
-        """Records in the buffer: ``min(count, max_segments)``."""
-        return int(self.header()["stored"])
-
-    @property
-    def overflowed(self) -> bool:
-        """Whether a record or its data did not fit the buffer (``partials()`` then reads the tap arrays)."""
-        return self._short(self.header())
-
-    @staticmethod
-    def _short(h) -> bool:
-        return bool(h["count"] > h["stored"] or h["n_bytes"] > h["stored_bytes"])
-
-    def _records(self, h) -> np.ndarray:
-        n = int(h["stored"])
-        return self._read(self.records_offset, self.records_offset + SEGMENT_DTYPE.itemsize * n).view(SEGMENT_DTYPE)
-
-    def records(self) -> np.ndarray:
-        """The first ``stored`` records as a numpy array of ``SEGMENT_DTYPE``."""
-        return self._records(self.header())
-
-    def _result(self) -> "LiveResult":
-        if self.result is None:
-            raise ValueError("the segments buffer is too small for this push and no LiveResult is referenced to read "
-                             "the rest from")
-        return self.result
+        super().__init__(buffer, max_segments, max_bytes, records_offset, data_offset, result)
 
     def _parsed(self):
         """``(records, their data as a list of bytes)`` of a push that fits the buffer; None when something did not
@@ -779,49 +762,61 @@ class LiveReceiver(batch._NativePlan):
         return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod,
                           tap)
 
+    def _alloc_packed(self, kind, max_records: int, max_bytes: int):
+        """A ``kind`` (``LiveEvents`` / ``LiveSegments``) over one zeroed uint8 device allocation of its layout."""
+        torch = batch._torch()
+        ro, bo, total = kind._layout(self.n_channels, self.slots, max_records, max_bytes)
+        return kind(torch.zeros(total, dtype=torch.uint8, device=self.device), max_records, max_bytes, ro, bo)
+
+    def _pack(self, kind, result: LiveResult, out, stream, alloc, call):
+        """What ``pack`` and ``pack_tap`` share: ``out`` (None: ``alloc()``) checked as a ``kind`` of this receiver's
+        for ``result``'s sizes, then ``call(n_channels, slots, buffer, max_records, max_bytes, stream)`` -- the native
+        pack entry -- on ``stream`` (behind torch's current stream when ``out`` is new), and ``out.result = result``."""
+        torch = batch._torch()
+        dev = self.device
+        fresh = out is None
+        if fresh:
+            out = alloc()
+        n, s = int(result.n_closed.numel()), result.slots
+        buf = out.buffer
+        refused = f"out= was not allocated by this receiver's alloc_{kind.NOUN}"
+        if not isinstance(out, kind) or not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 \
+                or buf.device != dev or not buf.is_contiguous():
+            raise ValueError(refused)
+        ro, bo, total = kind._layout(n, s, out.max_records, out.max_bytes)
+        if (out.records_offset, out.bytes_offset) != (ro, bo) or int(buf.numel()) < total:
+            raise ValueError(refused)
+        with torch.cuda.device(dev):
+            if fresh:
+                batch._order_after_current(stream, dev)
+            _native.check(call(n, s, buf.data_ptr(), out.max_records, out.max_bytes, batch._stream_ptr(stream, dev)))
+        out.result = result
+        return out
+
     def alloc_events(self, max_events: int | None = None, max_bytes: int | None = None) -> LiveEvents:
         """An events buffer for ``push(events=...)`` / ``pack``: one uint8 device allocation (``events_layout``) for
         ``max_events`` records and ``max_bytes`` payload bytes.  The defaults never overflow: ``n_channels * slots``
         records and ``max_events * out_stride`` bytes (capped below 2^31); callers who know their traffic pass
         smaller ones -- what does not fit is read from the slot arrays by ``LiveEvents.bursts``.  ``max_bytes=0`` is
         valid (a progressive receiver with ``max_payload_len=0`` has no payload rows)."""
-        torch = batch._torch()
         if max_events is None:
             max_events = self.n_channels * self.slots
         if max_bytes is None:
             max_bytes = min(int(max_events) * self.out_stride, 2 ** 31 - 1)
-        ro, po, total = events_layout(self.n_channels, self.slots, max_events, max_bytes)
-        return LiveEvents(torch.zeros(total, dtype=torch.uint8, device=self.device), max_events, max_bytes, ro, po)
+        return self._alloc_packed(LiveEvents, max_events, max_bytes)
 
     def pack(self, result: LiveResult, out: LiveEvents | None = None, stream=None) -> LiveEvents:
         """Pack the bursts ``result`` reports into ``out`` (``alloc_events``; None: a new one of the default size) with
         ``afsk_live_pack``: three launches on ``stream`` (default: torch's current stream), behind the push that
         writes ``result`` when that ran on the same stream.  Nothing synchronises, so push + pack of fixed buffers can
         be captured into one graph.  ``out.result`` is ``result`` from then on."""
-        torch = batch._torch()
-        dev = self.device
-        fresh = out is None
-        if fresh:
-            out = self.alloc_events()
-        n, s, d = int(result.n_closed.numel()), result.slots, result.demod
-        buf = out.buffer
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device != dev \
-                or not buf.is_contiguous():
-            raise ValueError("out= was not allocated by this receiver's alloc_events")
-        ro, po, total = events_layout(n, s, out.max_events, out.max_bytes)
-        if (out.records_offset, out.payload_offset) != (ro, po) or int(buf.numel()) < total:
-            raise ValueError("out= was not allocated by this receiver's alloc_events")
+        d = result.demod
         stride = int(d.bytes.shape[1])
-        with torch.cuda.device(dev):
-            if fresh:
-                batch._order_after_current(stream, dev)
-            _native.check(_native.lib().afsk_live_pack(
+        return self._pack(LiveEvents, result, out, stream, self.alloc_events, lambda n, s, *buffer: (
+            _native.lib().afsk_live_pack(
                 n, s, result.n_closed.data_ptr(), result.burst_start.data_ptr(), result.burst_len.data_ptr(),
                 result.flags.data_ptr(), d.bytes.data_ptr() if stride else None, stride, d.nbytes.data_ptr(),
-                d.nbits.data_ptr(), d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(),
-                buf.data_ptr(), out.max_events, out.max_bytes, batch._stream_ptr(stream, dev)))
-        out.result = result
-        return out
+                d.nbits.data_ptr(), d.clock_idx.data_ptr(), d.term_frame.data_ptr(), d.status.data_ptr(), *buffer)))
 
     def alloc_segments(self, max_segments: int | None = None, max_bytes: int | None = None) -> LiveSegments:
         """A segments buffer for ``push(segments=...)`` / ``pack_tap`` of a progressive receiver: one uint8 device
@@ -829,15 +824,13 @@ class LiveReceiver(batch._NativePlan):
         overflow: ``n_channels * (slots + 1)`` records and ``n_channels * tap_cap`` bytes (capped below 2^31); callers
         who know their traffic pass smaller ones -- when something does not fit, ``LiveSegments.partials`` reads the
         tap arrays."""
-        torch = batch._torch()
         if not self.progressive:
             raise ValueError("alloc_segments() needs a progressive receiver (LiveReceiver(..., progressive=True))")
         if max_segments is None:
             max_segments = min(self.n_channels * (self.slots + 1), 2 ** 31 - 1)
         if max_bytes is None:
             max_bytes = min(self.n_channels * self.tap_cap, 2 ** 31 - 1)
-        ro, do, total = segments_layout(self.n_channels, self.slots, max_segments, max_bytes)
-        return LiveSegments(torch.zeros(total, dtype=torch.uint8, device=self.device), max_segments, max_bytes, ro, do)
+        return self._alloc_packed(LiveSegments, max_segments, max_bytes)
 
     def pack_tap(self, result: LiveResult, out: LiveSegments | None = None, stream=None) -> LiveSegments:
         """Pack the payload segments ``result`` holds (a progressive push's) into ``out`` (``alloc_segments``; None: a
@@ -845,33 +838,16 @@ class LiveReceiver(batch._NativePlan):
         current stream), behind the push that writes ``result`` when that ran on the same stream.  Nothing
         synchronises, so push + pack of fixed buffers can be captured into one graph.  ``out.result`` is ``result``
         from then on."""
-        torch = batch._torch()
-        dev = self.device
         tap = result.tap
         if tap is None:
             raise ValueError("pack_tap() needs the result of a progressive receiver's push (LiveReceiver(..., "
                              "progressive=True))")
-        fresh = out is None
-        if fresh:
-            out = self.alloc_segments()
-        n, s, cap = int(result.n_closed.numel()), result.slots, int(tap.bytes.shape[1])
-        buf = out.buffer
-        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.device != dev \
-                or not buf.is_contiguous():
-            raise ValueError("out= was not allocated by this receiver's alloc_segments")
-        ro, do, total = segments_layout(n, s, out.max_segments, out.max_bytes)
-        if (out.records_offset, out.data_offset) != (ro, do) or int(buf.numel()) < total:
-            raise ValueError("out= was not allocated by this receiver's alloc_segments")
-        with torch.cuda.device(dev):
-            if fresh:
-                batch._order_after_current(stream, dev)
-            _native.check(_native.lib().afsk_live_pack_tap(
-                n, s, cap, result.n_closed.data_ptr(), result.burst_start.data_ptr(), result.burst_len.data_ptr(),
-                result.flags.data_ptr(), result.demod.nbytes.data_ptr(), tap.bytes.data_ptr(), tap.n.data_ptr(),
-                tap.len.data_ptr(), tap.open_start.data_ptr(), tap.open_nbytes.data_ptr(), buf.data_ptr(),
-                out.max_segments, out.max_bytes, batch._stream_ptr(stream, dev)))
-        out.result = result
-        return out
+        return self._pack(LiveSegments, result, out, stream, self.alloc_segments, lambda n, s, *buffer: (
+            _native.lib().afsk_live_pack_tap(
+                n, s, int(tap.bytes.shape[1]), result.n_closed.data_ptr(), result.burst_start.data_ptr(),
+                result.burst_len.data_ptr(), result.flags.data_ptr(), result.demod.nbytes.data_ptr(),
+                tap.bytes.data_ptr(), tap.n.data_ptr(), tap.len.data_ptr(), tap.open_start.data_ptr(),
+                tap.open_nbytes.data_ptr(), *buffer)))
 
     def assembler(self, string: bool = False) -> PayloadAssembler:
         """A ``PayloadAssembler`` for this (progressive) receiver's pushes."""

@@ -17,8 +17,8 @@ from tests.live_push_cells import push_cell
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, T, SLOTS, STRIDE = 600, 6144, 2, 24
-PACK_KERNELS = ["_ZN4afsk24live_events_total_kernelENS_14LiveEventsArgsE",
-                "_ZN4afsk23live_events_scan_kernelENS_14LiveEventsArgsE",
+PACK_KERNELS = ["_ZN4afsk22live_pack_total_kernelINS_14LiveEventsArgsEEEvT_",
+                "_ZN4afsk21live_pack_scan_kernelENS_16LivePackScanArgsE",
                 "_ZN4afsk24live_events_write_kernelENS_14LiveEventsArgsE"]
 BAD = _native.E_INVALID_ARG
 
@@ -137,6 +137,9 @@ def test_a_pack_launches_its_three_kernels_in_order_and_nothing_else(logged):
     one = Push(logged, n=1, slots=3, stride=0, max_events=0, max_bytes=0)
     assert logged.afsk_live_pack(*one.pack_args(out_bytes=None)) == 0
     assert launches(logged) == PACK_KERNELS
+    # the total and the write kernel are the event packer's own, the scan between them is neither packer's
+    assert ["LiveEventsArgs" in k for k in PACK_KERNELS] == [True, False, True]
+    assert not any("LiveSegmentsArgs" in k for k in PACK_KERNELS)
 
 
 @pytest.mark.parametrize("kind", ["stored", "stream", "tap"])

@@ -16,8 +16,8 @@ from tests.test_live_events_stub import PACK_KERNELS as EVENT_KERNELS
 from tests.test_live_events_stub import Push, build, last_kernel, launches
 
 N, T, SLOTS, STRIDE, CAP = 600, 6144, 2, 24, 19
-PACK_KERNELS = ["_ZN4afsk26live_segments_total_kernelENS_16LiveSegmentsArgsE",
-                "_ZN4afsk25live_segments_scan_kernelENS_16LiveSegmentsArgsE",
+PACK_KERNELS = ["_ZN4afsk22live_pack_total_kernelINS_16LiveSegmentsArgsEEEvT_",
+                "_ZN4afsk21live_pack_scan_kernelENS_16LivePackScanArgsE",
                 "_ZN4afsk26live_segments_write_kernelENS_16LiveSegmentsArgsE"]
 BAD = _native.E_INVALID_ARG
 
@@ -119,6 +119,11 @@ def test_a_pack_launches_its_three_kernels_in_order_and_nothing_else(logged):
     one = TapPush(logged, n=1, slots=3, cap=1, max_segments=0, max_bytes=0)
     assert logged.afsk_live_pack_tap(*one.seg_args()) == 0
     assert launches(logged) == PACK_KERNELS
+    # the two packers share the scan kernel and nothing else: neither launches the other's total or write kernel
+    assert PACK_KERNELS[1] == EVENT_KERNELS[1]
+    assert PACK_KERNELS[0] != EVENT_KERNELS[0] and PACK_KERNELS[2] != EVENT_KERNELS[2]
+    assert ["LiveSegmentsArgs" in k for k in PACK_KERNELS] == [True, False, True]
+    assert not any("LiveEventsArgs" in k for k in PACK_KERNELS)
 
 
 @pytest.mark.parametrize("ragged", [False, True])

@@ -8,6 +8,7 @@
     python tools/live_bench.py --ragged [--parent PARENT.so] [--ragged-shape 65536x8192] [--json OUT] [--txt OUT]
     python tools/live_bench.py --events [--shapes ...] [--events-max-burst 96000] [--json OUT] [--txt OUT]
     python tools/live_bench.py --segments [--shapes 65536x8192,65536x2048] [--sparse-every 64] [--json OUT] [--txt OUT]
+    python tools/live_bench.py --events | --segments --parent PARENT.so [--shapes ...] [--json OUT] [--txt OUT]
 
 --stream times the stored and the streaming receiver (max_burst_len=None) on the same pushes, alternately, per case
 (stream_ab below).  --tap times the streaming receiver's push with and without the payload tap (progressive=True) on the
@@ -25,6 +26,10 @@ over every slot array against LiveEvents.bursts() over the packed list -- with t
 tapped push alone, the push with the device-side pack (LiveReceiver.push(segments=), afsk_live_pack_tap), and both
 followed by the host's PayloadAssembler.feed -- of the result's whole arrays against the packed list -- with the bytes
 each copies, on the workload below and on a sparse one where only one channel in --sparse-every carries signal.
+
+--events / --segments with --parent time only the rows of the pack alone (the eager three launches at their densest:
+pack_all_slots_us; pack_all_open_us, pack_all_slots_open_us), the parent build's twice and this build's in turn
+(pack_alone_ab below).
 
 Per shape (channels x T samples per push, 1200 baud): the channels are synthesized on the device (modulator + oracle
 noise at 30 dB, two bursts per channel with payloads of 4 / 12 / 24 bytes at random leads, every eighth channel
@@ -57,6 +62,7 @@ from afskmodem_amd.live import LiveReceiver  # noqa: E402
 
 PEAK = 8.0e12
 BAUD, BF = 1200, 40
+PACK_AB_PASSES = 5      # timed passes per variant of the pack-alone rows against --parent
 BLOCK = 2048
 
 
@@ -368,6 +374,100 @@ def tap_ab(torch, n, T, seconds, baud, reps, seed, long_messages, parent):
     return rec
 
 
+def pack_alone_us(torch, pack, reps, parent):
+    """Mean us of one eager pack (``pack()``: three launches, HIP events around them) over ``reps`` calls after one
+    warm-up call.  With ``parent`` (a loaded library of the parent commit) instead a dict: the variants parent,
+    parent_again and this build take turns pass by pass, each pass ``reps`` calls after a warm-up call; the margin is the
+    spread between the two parent variants (as tap_ab's), and this build is inside when its mean is at most the mean of
+    the two parent variants plus that margin."""
+    def one_pass():
+        us = []
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            pack()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        return float(np.mean(us[1:]))
+
+    if parent is None:
+        return round(one_pass(), 2)
+    variants = (("parent", parent), ("parent_again", parent), ("this", None))
+    passes = {name: [] for name, _ in variants}
+    for r in range(PACK_AB_PASSES + 1):
+        for name, lib in variants:
+            with using(lib):
+                t = one_pass()
+            if r:
+                passes[name].append(t)
+    V = {name: dict(us_mean=round(float(np.mean(p)), 2), us_passes=[round(x, 2) for x in p],
+                    spread=round((max(p) - min(p)) / float(np.mean(p)), 4)) for name, p in passes.items()}
+    a, b = V["parent"]["us_mean"], V["parent_again"]["us_mean"]
+    margin = max(abs(a - b) / min(a, b), V["parent"]["spread"], V["parent_again"]["spread"])
+    return dict(variants=V, margin=round(margin, 4), this_over_parent=round(V["this"]["us_mean"] / (0.5 * (a + b)), 4),
+                this_inside_margin=bool(V["this"]["us_mean"] <= 0.5 * (a + b) * (1 + margin)))
+
+
+def events_pack_alone(torch, rx, o, events, reps, parent, rec):
+    """The event pack alone at its densest: every slot of every channel in use with a 24-byte payload (hand-made arrays
+    in the result's own tensors; the pack visits a wave's 64 channels one after the other)."""
+    o.n_closed.fill_(rx.slots)
+    o.flags.zero_()
+    o.demod.nbytes.fill_(min(24, int(o.demod.bytes.shape[1])))
+    rec["pack_all_slots_us"] = pack_alone_us(torch, lambda: rx.pack(o, out=events), reps, parent)
+    rec["pack_all_slots_records"] = int(events.count)
+
+
+def segments_pack_alone(torch, rx, o, sg, reps, parent, rec):
+    """The segment pack alone at its densest, on hand-made arrays in the result's own tensors: every channel with an
+    open segment of min(14, tap_cap) bytes (14: what a busy 1200-baud channel decodes in 8192 samples), then every slot
+    in use as well (final segments of length 0)."""
+    t = o.tap
+    k = min(14, rx.tap_cap)
+    for name, closed in (("pack_all_open", 0), ("pack_all_slots_open", rx.slots)):
+        o.n_closed.fill_(closed)
+        o.flags.zero_()
+        o.demod.nbytes.fill_(k)
+        t.n.fill_(k)
+        t.len.zero_()
+        t.open_start.fill_(2048)
+        t.open_nbytes.fill_(k)
+        rec[name + "_us"] = pack_alone_us(torch, lambda: rx.pack_tap(o, out=sg), reps, parent)
+        rec[name + "_records"] = int(sg.count)
+    rec["pack_all_open_bytes_per_channel"] = k
+
+
+def pack_alone_ab(torch, n, T, reps, parent, segments, max_burst):
+    """--events / --segments with --parent: the pack-alone rows only, this build against the parent's in one process.
+    The pack entries take no receiver handle, so one receiver of this build holds the arrays for every variant."""
+    if segments:
+        rx = LiveReceiver(n, BF, max_burst_len=None, max_payload_len=256, max_chunk_len=T, progressive=True)
+        rec = dict(shape=f"{n}x{T}", slots=rx.slots, tap_cap=rx.tap_cap, reps=reps, passes=PACK_AB_PASSES)
+        segments_pack_alone(torch, rx, rx.alloc_result(), rx.alloc_segments(), reps, parent, rec)
+    else:
+        rx = LiveReceiver(n, BF, max_burst_len=max_burst, max_chunk_len=T)
+        rec = dict(shape=f"{n}x{T}", slots=rx.slots, out_stride=rx.out_stride, reps=reps, passes=PACK_AB_PASSES)
+        events_pack_alone(torch, rx, rx.alloc_result(), rx.alloc_events(), reps, parent, rec)
+    torch.cuda.synchronize()
+    rx.close()
+    torch.cuda.empty_cache()
+    return rec
+
+
+def pack_alone_lines(recs):
+    out = ["the pack alone (eager, three launches), us per pack: the parent build twice and this build, taking turns pass "
+           "by pass; margin = the larger of the two parent variants' difference and their own spreads"]
+    for r in recs:
+        for row in [k for k in r if k.endswith("_us")]:
+            c, V = r[row], r[row]["variants"]
+            out.append(f"{r['shape']:>12s} {row:>24s} {r[row[:-3] + '_records']:9d} records  "
+                       + "  ".join(f"{k} {V[k]['us_mean']:8.1f}" for k in ("parent", "parent_again", "this"))
+                       + f"  this/parent x{c['this_over_parent']:.4f} (margin {100 * c['margin']:.2f} %: "
+                       f"{'inside' if c['this_inside_margin'] else 'OUTSIDE'})")
+    return out
+
+
 def events_ab(torch, n, T, seconds, reps, seed, max_burst):
     """What it costs to learn which bursts a push closed, on run_shape's workload with a stored receiver
     (max_burst_len = max_burst): per push, the variants taking turns pass by pass after one warm-up pass each,
@@ -452,22 +552,7 @@ def events_ab(torch, n, T, seconds, reps, seed, max_burst):
     rec["events_over_bursts"] = round(d / c, 4)
     rec["bursts_spread"] = rec["push_bursts"]["spread"]
     rec["events_faster_beyond_spread"] = bool(d < c * (1 - rec["bursts_spread"]))
-    # the pack alone at its densest: every slot of every channel in use with a 24-byte payload (hand-made arrays in the
-    # result's own tensors; the pack visits a wave's 64 channels one after the other)
-    o = out[1]
-    o.n_closed.fill_(rx[1].slots)
-    o.flags.zero_()
-    o.demod.nbytes.fill_(min(24, stride))
-    t = []
-    for _ in range(reps + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rx[1].pack(o, out=events)
-        e1.record()
-        torch.cuda.synchronize()
-        t.append(e0.elapsed_time(e1) * 1e3)
-    rec["pack_all_slots_us"] = round(float(np.mean(t[1:])), 2)
-    rec["pack_all_slots_records"] = int(events.count)
+    events_pack_alone(torch, rx[1], out[1], events, reps, None, rec)
     del graphs, samples
     torch.cuda.synchronize()
     for r in rx:
@@ -596,30 +681,7 @@ def segments_ab(torch, n, T, seconds, reps, seed, keep_every):
     rec["result_spread"] = rec["push_feed_result"]["spread"]
     rec["segments_faster_beyond_spread"] = bool(d < c * (1 - rec["result_spread"]))
     rec["segments_slower_beyond_spread"] = bool(d > c * (1 + rec["result_spread"]))
-    # the pack alone at its densest, on hand-made arrays in the result's own tensors: every channel with an open segment
-    # of min(14, tap_cap) bytes (14: what a busy 1200-baud channel decodes in 8192 samples), then every slot in use as
-    # well (final segments of length 0)
-    o, t = out[1], out[1].tap
-    k = min(14, rx[1].tap_cap)
-    for name, closed in (("pack_all_open", 0), ("pack_all_slots_open", rx[1].slots)):
-        o.n_closed.fill_(closed)
-        o.flags.zero_()
-        o.demod.nbytes.fill_(k)
-        t.n.fill_(k)
-        t.len.zero_()
-        t.open_start.fill_(2048)
-        t.open_nbytes.fill_(k)
-        us = []
-        for _ in range(reps + 1):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rx[1].pack_tap(o, out=sg)
-            e1.record()
-            torch.cuda.synchronize()
-            us.append(e0.elapsed_time(e1) * 1e3)
-        rec[name + "_us"] = round(float(np.mean(us[1:])), 2)
-        rec[name + "_records"] = int(sg.count)
-    rec["pack_all_open_bytes_per_channel"] = k
+    segments_pack_alone(torch, rx[1], out[1], sg, reps, None, rec)
     del graphs, samples
     torch.cuda.synchronize()
     for r in rx:
@@ -824,7 +886,8 @@ def main():
     ap.add_argument("--tap", action="store_true",
                     help="the streaming push with and without the payload tap, alternating, per --tap-cases entry")
     ap.add_argument("--tap-cases", default="65536x8192@1200,65536x2048@1200,16384x8192@long")
-    ap.add_argument("--parent", help="with --tap / --ragged: libafsk_amd.so of the parent commit, timed in the same run")
+    ap.add_argument("--parent", help="with --tap / --ragged: libafsk_amd.so of the parent commit, timed in the same run; "
+                                     "with --events / --segments: the pack-alone rows only, against that build's")
     ap.add_argument("--txt", help="with --tap / --ragged: the table as text")
     ap.add_argument("--ragged", action="store_true",
                     help="the ragged push and pull against the plain ones, and the plain ones against --parent")
@@ -861,6 +924,23 @@ def main():
         return
     import torch
     res = []
+    if (args.events or args.segments) and args.parent:
+        parent = load_build(args.parent)
+        for shape in args.shapes.split(","):
+            n, T = (int(x) for x in shape.split("x"))
+            rec = pack_alone_ab(torch, n, T, args.reps, parent, args.segments, args.events_max_burst)
+            print(json.dumps(rec), flush=True)
+            res.append(rec)
+        lines = pack_alone_lines(res)
+        print("\n".join(lines))
+        mode = "--segments" if args.segments else "--events"
+        for path, text in ((args.json, json.dumps(dict(tool=f"tools/live_bench.py {mode} --parent", reps=args.reps,
+                                                       results=res), indent=1)),
+                           (args.txt, "\n".join(lines) + "\n")):
+            if path:
+                with open(path, "w") as f:
+                    f.write(text)
+        return
     if args.events:
         for shape in args.shapes.split(","):
             n, T = (int(x) for x in shape.split("x"))
