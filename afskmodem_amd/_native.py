@@ -217,6 +217,15 @@ DETECT_SIGNATURES = {
 }
 DETECT_MAX_CANDIDATES = 36                   # AFSK_DETECT_MAX_CANDIDATES
 
+# The auto-rate streaming live receiver (afsk_live_create_stream_auto, afsk_live_push_auto), likewise.
+LIVE_AUTO_SIGNATURES = {
+    "afsk_live_create_stream_auto": (C.c_int, [C.c_int32, _i32p, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int32,
+                                               C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    # afsk_live_push_ragged's arguments, the two rate outputs in front of the stream
+    "afsk_live_push_auto": (C.c_int, LIVE_RAGGED_SIGNATURES["afsk_live_push_ragged"][1][:-1]
+                            + [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -232,7 +241,8 @@ def lib() -> C.CDLL:
                                   *LIVE_STREAM_SIGNATURES.items(), *LIVE_THRESHOLD_SIGNATURES.items(),
                                   *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
-                                  *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items()):
+                                  *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
+                                  *LIVE_AUTO_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

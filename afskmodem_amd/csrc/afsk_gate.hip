@@ -162,8 +162,11 @@ hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t stream) {
 #include "afsk_live_stream.hip"
 // The streaming receiver's payload tap (afsk_live_tap_layout / afsk_live_create_stream_tap), for the same reason.
 #include "afsk_live_tap.hip"
-// Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged: the one kernel template over the
-// three sinks, its table of instantiations and the one host path), last: it needs all three sinks.
+// The auto-rate streaming receiver (afsk_live_create_stream_auto: the streaming sink with every burst's rate decided on
+// the device from its first 4096 samples), for the same reason.
+#include "afsk_live_auto.hip"
+// Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged / afsk_live_push_auto: the one kernel
+// template over the sinks, its table of instantiations and the one host path), behind every sink.
 #include "afsk_live_push.hip"
 // The packed lists of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into a
 // count, records and payload bytes; afsk_live_segments_layout / afsk_live_pack_tap: likewise what the payload tap of a

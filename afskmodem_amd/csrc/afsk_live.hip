@@ -413,6 +413,9 @@ struct afsk_live {
     afsk_group_plan* plan = nullptr;    // mixed: the plan over the slots (8 bytes per slot on the device)
     int32_t max_payload_len = -1;       // >= 0: a streaming receiver (afsk_live_stream.hip)
     int32_t tap_cap = 0;                // > 0: a tapped streaming receiver (afsk_live_tap.hip): bytes per tap row
+    // > 0: an auto-rate streaming receiver (afsk_live_auto.hip): the candidate list every push passes by value
+    int32_t auto_n_cand = 0, auto_max_score = -1;
+    int32_t auto_cand[AFSK_DETECT_MAX_CANDIDATES] = {};
     // a threshold pair per channel (afsk_live_create_thresholds / _stream_thresholds): amp_start int32 [n] at o_thr,
     // amp_end int32 [n] behind it; a stored receiver of two or more squelch classes also the classes' slot lists
     // (o_list: int32 [n * slots]) and, with mixed rates, every slot's bit_frames (o_slot_bf: int32 [n * slots])

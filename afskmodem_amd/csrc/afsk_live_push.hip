@@ -1,11 +1,12 @@
 // afsk_live_push.hip -- every live receiver's push (afsk_live_push, afsk_live_push_tap, afsk_live_push_ragged,
-// include/afsk_amd.h): one kernel template, one table of its instantiations, one host path.
+// afsk_live_push_auto, include/afsk_amd.h): one kernel template, one table of its instantiations, one host path.
 //
 // live_push_kernel<Sink, PER_CHANNEL, RAGGED> builds the sink from its argument struct and runs live_gate_walk
 // (afsk_live.hip) with it.  The three sinks -- LiveStoreSink (afsk_live.hip), LiveStreamSinkT<false> and
 // LiveStreamSinkT<true> (afsk_live_stream.hip; the tapped one: afsk_live_tap.hip) -- times the walk's two flags are the
 // twelve cells of kLivePushCells; nothing else calls live_gate_walk.  A further sink or flag is a further index of the
-// table, not a further copy of the path.
+// table, not a further copy of the path: the auto-rate receiver's two sinks, LiveAutoSinkT<false> and LiveAutoSinkT<true>
+// (afsk_live_auto.hip), are sink kinds 3 and 4 -- eight more cells, launched by afsk_live_push_auto alone.
 //
 // afsk::live_push does what the three C entries have in common, once: the argument checks, the receiver's device, the
 // kernel arguments, the choice of the cell from the receiver's kind and the call's form, the launch and, for a stored
@@ -45,11 +46,13 @@ LivePushCell live_push_cell(const char* what) {
       live_push_cell<Sink, false, true>("launch live_push_kernel<" name ", ragged>")},                  \
      {live_push_cell<Sink, true, false>("launch live_push_kernel<" name ", per channel>"),              \
       live_push_cell<Sink, true, true>("launch live_push_kernel<" name ", per channel, ragged>")}}
-enum LiveSinkKind { kLiveStored, kLiveStream, kLiveTapped };
+enum LiveSinkKind { kLiveStored, kLiveStream, kLiveTapped, kLiveAuto, kLiveAutoTapped };
 // [sink kind][a threshold pair per channel][ragged]
-static const LivePushCell kLivePushCells[3][2][2] = {AFSK_LIVE_PUSH_CELLS(LiveStoreSink, "stored"),
+static const LivePushCell kLivePushCells[5][2][2] = {AFSK_LIVE_PUSH_CELLS(LiveStoreSink, "stored"),
                                                      AFSK_LIVE_PUSH_CELLS(LiveStreamSinkT<false>, "streaming"),
-                                                     AFSK_LIVE_PUSH_CELLS(LiveStreamSinkT<true>, "tapped")};
+                                                     AFSK_LIVE_PUSH_CELLS(LiveStreamSinkT<true>, "tapped"),
+                                                     AFSK_LIVE_PUSH_CELLS(LiveAutoSinkT<false>, "auto"),
+                                                     AFSK_LIVE_PUSH_CELLS(LiveAutoSinkT<true>, "auto, tapped")};
 #undef AFSK_LIVE_PUSH_CELLS
 
 template <class Args>
@@ -81,6 +84,7 @@ struct LiveTapOutputs {
 
 // What a push entry asks for.  `ragged`: the ragged cells, with chunk_lens and flush_mask (device arrays, either may be
 // null).  `tap_required`: the entry is the tapped push (else the tap outputs may be all null: an untapped push).
+// `auto_rate`: the entry is afsk_live_push_auto, with the two per-slot rate outputs.
 struct LivePushCall {
     const int16_t* chunk;
     int64_t chunk_row_stride;
@@ -94,6 +98,9 @@ struct LivePushCall {
     LiveTapOutputs tap;
     bool tap_required;
     hipStream_t stream;
+    bool auto_rate = false;
+    int32_t* out_bit_frames = nullptr;
+    int32_t* out_rate_score = nullptr;
 };
 
 // the gate's arguments every receiver has; o_carry: the carry's place in its state
@@ -158,8 +165,16 @@ int live_push(afsk_live* live, const LivePushCall& c) {
     if (c.chunk_len < 0 || c.chunk_row_stride < 0 || o.negative()) return fail(AFSK_E_INVALID_ARG, "negative size");
     if (c.chunk_len > live->max_chunk_len)
         return fail(AFSK_E_INVALID_ARG, "chunk_len exceeds the receiver's max_chunk_len");
-    if ((c.chunk_len > 0 && !c.chunk) || c.gate.missing() || o.missing() || (c.tap_required && n_tap != 5))
+    if ((c.chunk_len > 0 && !c.chunk) || c.gate.missing() || o.missing() || (c.tap_required && n_tap != 5) ||
+        (c.auto_rate && (!c.out_bit_frames || !c.out_rate_score)))
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    const bool is_auto = live->auto_n_cand > 0;
+    if (is_auto && !c.auto_rate)
+        return fail(AFSK_E_INVALID_ARG, "an auto-rate receiver (afsk_live_create_stream_auto) is pushed with "
+                                        "afsk_live_push_auto");
+    if (!is_auto && c.auto_rate)
+        return fail(AFSK_E_INVALID_ARG, "afsk_live_push_auto needs a receiver of afsk_live_create_stream_auto: this one "
+                                        "is pushed with afsk_live_push, afsk_live_push_tap or afsk_live_push_ragged");
     const bool streaming = live->max_payload_len >= 0;
     if (streaming && o.margins)
         return fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
@@ -169,10 +184,13 @@ int live_push(afsk_live* live, const LivePushCall& c) {
     if (tapped && live->tap_cap <= 0)
         return fail(AFSK_E_INVALID_ARG, c.tap_required
                                             ? "afsk_live_push_tap needs a receiver of afsk_live_create_stream_tap"
-                                            : "tap outputs need a receiver of afsk_live_create_stream_tap");
+                                            : is_auto ? "tap outputs need a receiver of afsk_live_create_stream_auto "
+                                                        "with tap = 1"
+                                                      : "tap outputs need a receiver of afsk_live_create_stream_tap");
     if (int rc = live->state.check_current()) return rc;
 
-    const LiveSinkKind kind = tapped ? kLiveTapped : streaming ? kLiveStream : kLiveStored;
+    const LiveSinkKind kind = is_auto ? (tapped ? kLiveAutoTapped : kLiveAuto)
+                                      : tapped ? kLiveTapped : streaming ? kLiveStream : kLiveStored;
     const LivePushCell& cell = kLivePushCells[kind][live->per_channel][c.ragged];
     LivePushPtrs x{};
     if (live->per_channel) {
@@ -192,8 +210,15 @@ int live_push(afsk_live* live, const LivePushCall& c) {
     } else {
         const LiveStreamArgs s = live_stream_args(live, c);
         const LiveTapArgs t{c.tap.bytes, live->tap_cap, c.tap.n, c.tap.len, c.tap.open_start, c.tap.open_nbytes};
-        e = tapped ? live_push_launch(cell, n, c.stream, LiveStreamTapArgs{s, t}, x)
-                   : live_push_launch(cell, n, c.stream, s, x);
+        if (is_auto) {
+            LiveAutoDetect d{c.out_bit_frames, c.out_rate_score, live->auto_max_score, live->auto_n_cand, {}};
+            std::copy(live->auto_cand, live->auto_cand + live->auto_n_cand, d.cand);
+            e = tapped ? live_push_launch(cell, n, c.stream, LiveAutoArgsT<true>{{s, t}, d}, x)
+                       : live_push_launch(cell, n, c.stream, LiveAutoArgsT<false>{s, d}, x);
+        } else {
+            e = tapped ? live_push_launch(cell, n, c.stream, LiveStreamTapArgs{s, t}, x)
+                       : live_push_launch(cell, n, c.stream, s, x);
+        }
     }
     if (e != hipSuccess) return hip_fail(e, cell.what);
     return streaming ? AFSK_OK : live_stored_demod(live, g, o, c.stream);
@@ -242,6 +267,25 @@ int afsk_live_push_ragged(afsk_live* live, const int16_t* chunk, int64_t chunk_r
                                    out_status, out_corrected, out_margins, margin_stride},
                                   {tap_bytes, tap_n, tap_len, open_start, open_nbytes}, false,
                                   (hipStream_t)hip_stream});
+}
+
+int afsk_live_push_auto(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                        const int32_t* d_chunk_lens_or_null, int32_t flush, const uint8_t* d_flush_mask_or_null,
+                        int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len, int32_t* out_flags,
+                        uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes, int32_t* out_nbits,
+                        int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status, int32_t* out_corrected,
+                        int32_t* out_margins, int32_t margin_stride, uint8_t* tap_bytes, int32_t* tap_n,
+                        int32_t* tap_len, int64_t* open_start, int32_t* open_nbytes, int32_t* out_bit_frames,
+                        int32_t* out_rate_score, void* hip_stream) {
+    // null lengths and a null mask: the plain cells
+    const bool ragged = d_chunk_lens_or_null || d_flush_mask_or_null;
+    return afsk::live_push(live, {chunk, chunk_row_stride, chunk_len, flush, ragged, d_chunk_lens_or_null,
+                                  d_flush_mask_or_null,
+                                  {out_n_closed, out_burst_start, out_burst_len, out_flags},
+                                  {out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame,
+                                   out_status, out_corrected, out_margins, margin_stride},
+                                  {tap_bytes, tap_n, tap_len, open_start, open_nbytes}, false,
+                                  (hipStream_t)hip_stream, true, out_bit_frames, out_rate_score});
 }
 
 }  // extern "C"

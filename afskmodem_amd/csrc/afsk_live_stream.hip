@@ -33,6 +33,10 @@
 // state; its push runs the sink's tapped instantiation (LiveStreamSinkT<true>), which also hands out every payload
 // byte in the push that commits it.
 //
+// The auto-rate receiver (afsk_live_auto.hip: afsk_live_create_stream_auto, afsk_live_push_auto) is this receiver with
+// the same state and a sink derived from this one: the sink's steps (set_rate, rows, put, clock, lock, symbols) are
+// members of their own so that it can decide a burst's rate between put and lock; StreamDemod::spare holds that rate.
+//
 // This file is compiled as part of afsk_gate.hip's translation unit (see the #include at its end), after afsk_split.hip
 // (the demod helpers) and afsk_live.hip (the gate walk, LiveChan, LiveArgs).
 
@@ -47,7 +51,7 @@ struct StreamDemod {        // 32 bytes per channel: the open burst's demodulato
     int32_t corrected;      // whole codewords with a non-zero syndrome
     uint32_t bits;          // phase 1: the last three decisions (bit 0 = oldest); phase 2: the nbits % 7 pending
                             // coded bits (bit 0 = oldest) | the high nibble of an unfinished byte << 8
-    int32_t spare;
+    int32_t spare;          // the auto-rate sink (afsk_live_auto.hip): (score << 11) | bit_frames of the open burst
 };
 static_assert(sizeof(StreamDemod) == 32, "StreamDemod layout");
 
@@ -178,14 +182,22 @@ struct LiveStreamSinkT {
         lwin = reinterpret_cast<int16_t*>(lds + (threadIdx.x >> 6) * kStreamWinLds);
         if constexpr (TAP) tp.T = a.t;
     }
-    // amp_end: the channel's squelch threshold (the per-symbol squelch of ref:375)
-    __device__ __forceinline__ void init(const LiveArgs&, int c, int32_t amp_end) {
-        ds = A.dm[c];
-        bf = A.bit_frames[c];
+    // what depends on the burst's rate (b = 0: no rate yet, nothing divides by it)
+    __device__ __forceinline__ void set_rate(int b, int32_t amp_end) {
+        bf = b;
         int l = 0;
         while ((2 << l) * 32 <= bf) l++;                         // lps = largest power of two <= bf / 32
         lsh = l;
         amp_thr = split_amp_thr(amp_end, bf);
+    }
+    // amp_end: the channel's squelch threshold (the per-symbol squelch of ref:375)
+    __device__ __forceinline__ void init(const LiveArgs&, int c, int32_t amp_end) {
+        ds = A.dm[c];
+        set_rate(A.bit_frames[c], amp_end);
+        rows(c);
+    }
+    // the channel's window image, payload row and tap row
+    __device__ __forceinline__ void rows(int c) {
         gwin = A.win + (int64_t)c * kStreamWin;
         pay = A.pay + (int64_t)c * A.max_payload;
         if constexpr (TAP) {
@@ -311,34 +323,40 @@ struct LiveStreamSinkT {
         ds.bits = ((uint32_t)acc & 0x7Fu) | (hi << 8);
     }
 
-    __device__ __forceinline__ void record(const LiveArgs&, const LiveChan& st, const vec16 (&cur)[4], int lane) {
-        if (!live_demod(st) || st.rec_len + kListenBlock > kMaxStreamLen) return;   // stopped, or too long to decode
+    // the block into the window; false: nothing to demodulate (stopped, too long to decode, or the burst's first block)
+    __device__ __forceinline__ bool put(const LiveChan& st, const vec16 (&cur)[4], int lane) {
+        if (!live_demod(st) || st.rec_len + kListenBlock > kMaxStreamLen) return false;   // stopped, or too long to decode
         const int32_t jb = (int32_t)(st.rec_len >> 11);           // the block's index in the burst
         uint8_t* half = reinterpret_cast<uint8_t*>(lwin) + (jb & 1) * (2 * kListenBlock);
         wave_lds_sync();                                           // the previous block's reads are done
 #pragma unroll
         for (int j = 0; j < 4; j++) *reinterpret_cast<vec16*>(half + 1024 * j + 16 * lane) = cur[j];
         wave_lds_sync();
-        if (jb == 0) return;
-        if (ds.phase == 0) {                                       // the first 4096 samples: clock recovery (ref:322-339)
-            FastRing fr;
-            fr.ring = reinterpret_cast<uint8_t*>(lwin);
-            fr.lane = lane;
-            fr.next = 8;
-            fr.warm_ops = 0;
-            int ci;
-            if (bf == 40) {
-                if (clock_index_is_zero<40, 8>(fr)) ci = 0;        // ref:332-337 (no search needed)
-                else ci = recover_clock_index_lanes<40, false, 8>(fr);
-            } else {
-                ci = recover_clock_index_rt(fr, bf);
-            }
-            ds.ci = ci;
-            ds.k = 0;
-            ds.phase = 1;
-            ds.bits = 0;
-            wave_lds_sync();
+        return jb != 0;
+    }
+    // the clock index at bit_frames b of the burst's first 4096 samples, which the window holds (ref:322-339)
+    __device__ __forceinline__ int clock(int b, int lane) const {
+        FastRing fr;
+        fr.ring = reinterpret_cast<uint8_t*>(lwin);
+        fr.lane = lane;
+        fr.next = 8;
+        fr.warm_ops = 0;
+        if (b == 40) {
+            if (clock_index_is_zero<40, 8>(fr)) return 0;          // ref:332-337 (no search needed)
+            return recover_clock_index_lanes<40, false, 8>(fr);
         }
+        return recover_clock_index_rt(fr, b);
+    }
+    // the terminator search starts at symbol 0 of clock index ci
+    __device__ __forceinline__ void lock(int ci) {
+        ds.ci = ci;
+        ds.k = 0;
+        ds.phase = 1;
+        ds.bits = 0;
+        wave_lds_sync();
+    }
+    // the symbols that are complete with the block after st.rec_len and not committed yet
+    __device__ __forceinline__ void symbols(const LiveChan& st, int lane) {
         const int32_t len = (int32_t)st.rec_len + kListenBlock;
         const int32_t k_end = (len - ds.ci - 1) / bf;             // symbols with i < len - bf (ref:362, 372)
         const int spp = 64 >> lsh;
@@ -352,6 +370,11 @@ struct LiveStreamSinkT {
             }
             ds.k += n;
         }
+    }
+    __device__ __forceinline__ void record(const LiveArgs&, const LiveChan& st, const vec16 (&cur)[4], int lane) {
+        if (!put(st, cur, lane)) return;
+        if (ds.phase == 0) lock(clock(bf, lane));                  // the first 4096 samples: clock recovery
+        symbols(st, lane);
     }
     __device__ __forceinline__ int32_t head(const LiveChan&) const { return 0; }
     // what the next push needs of the open burst leaves the window; the demodulator state is stored

@@ -212,10 +212,23 @@ class LiveResult:
     flags: "object"          # int32 [n_channels, slots] LIVE_OPEN_END | LIVE_OVERFLOW
     demod: batch.DemodResult
     tap: "LiveTap | None" = None     # a progressive receiver's push only
+    bit_frames: "object" = None      # int32 [n_channels, slots] an auto receiver's push only: the burst's detected rate
+    rate_score: "object" = None      # int32 [n_channels, slots] likewise: the detector's score of that rate
 
     @property
     def slots(self) -> int:
         return int(self.burst_len.shape[1])
+
+    def rated_bursts(self, string: bool = False) -> list[tuple[int, int, int, "bytes | str", int]]:
+        """``bursts(string)`` with each burst's detected ``bit_frames`` behind its payload: ``(channel, start, length,
+        payload, bit_frames)``, in the order of ``bursts()``; ``bit_frames`` is 0 for a burst that never reached 4096
+        samples or was refused by ``max_score``.  Needs a push of an auto receiver."""
+        if self.bit_frames is None:
+            raise ValueError('rated_bursts() needs the result of an auto receiver\'s push (LiveReceiver(n, "auto", ...))')
+        out = self.bursts(string)
+        nc, bf = _host(self.n_closed), _host(self.bit_frames)
+        rates = [int(bf[c, k]) for c in np.nonzero(nc)[0].tolist() for k in range(int(nc[c]))]
+        return [(*b, r) for b, r in zip(out, rates)]
 
     def partials(self) -> list[tuple[int, int, int, bytes, bool]]:
         """Synchronise and return ``(channel, burst_start, offset, data, final)`` per payload segment of this push,
@@ -457,6 +470,23 @@ class LiveEvents(_PackedList):
             return b""
         return self._from_slots(False, [(int(recs["channel"][0]), int(recs["slot"][0]))])[0]
 
+    def bit_frames(self) -> np.ndarray:
+        """The detected ``bit_frames`` of every record of ``records()``, int32 [stored]: gathered on the device from the
+        referenced result of an auto receiver at each record's ``(channel, slot)``, so ``stored * 4`` bytes are copied
+        on top of the header and the records.  ValueError when no such result is referenced."""
+        res = self.result
+        if res is None or res.bit_frames is None:
+            raise ValueError("bit_frames() needs the events of an auto receiver's push: no LiveResult with bit_frames "
+                             "is referenced")
+        recs = self.records()
+        at = recs["channel"].astype(np.int64) * res.slots + recs["slot"]
+        self.copied_bytes += 4 * int(at.size)
+        t = res.bit_frames
+        if hasattr(t, "is_cuda"):
+            torch = batch._torch()
+            return t.reshape(-1)[torch.from_numpy(at).to(t.device)].cpu().numpy()
+        return np.asarray(t).reshape(-1)[at]
+
     def bursts(self, string: bool = False) -> list[tuple[int, int, int, "bytes | str"]]:
         """What ``result.bursts(string)`` returns -- ``(channel, start, length, payload)`` per reported burst, channel
         by channel and in time order -- from the header, the ``stored`` records and the ``stored_bytes`` payload bytes.
@@ -654,24 +684,50 @@ class LiveReceiver(batch._NativePlan):
     then keeps 16 KiB of state per channel.  ``tap_cap`` is the bytes of a tap row (``tap_layout``; None otherwise).
     The state, the slots and every other output are the streaming receiver's.
 
+    ``bit_frames="auto"`` (streaming only, ValueError otherwise) builds the AUTO receiver
+    (``afsk_live_create_stream_auto``): no channel has a rate; every burst's rate is decided on the device from the
+    burst's first 4096 samples among ``candidates`` (None: all of ``batch.VALID_BIT_FRAMES``; 1 ... 36 valid values,
+    duplicates allowed, the earliest wins a tie) exactly as ``batch.detect_rates`` decides it, and the burst is
+    demodulated at that rate.  ``LiveResult.bit_frames`` / ``rate_score`` report it per slot.  ``max_score`` (None:
+    no limit): a burst whose best score exceeds it is not demodulated (status INVALID_BAUD, no bytes).  ``auto`` is
+    True, ``bit_frames`` None and ``channel_bit_frames`` all 0 on such a receiver; everything else -- ``progressive``,
+    thresholds per channel, ragged pushes, ``events=``, ``segments=``, ``out=`` -- works as on the streaming receiver.
+
     The receiver belongs to the device that was current (or ``device``); ``close()`` only after its pushes have
     completed."""
     _destroy = "afsk_live_destroy"
 
-    def __init__(self, n_channels: int, bit_frames: int, amp_start_threshold=18000, amp_end_threshold=14000,
+    def __init__(self, n_channels: int, bit_frames, amp_start_threshold=18000, amp_end_threshold=14000,
                  max_burst_len: int | None = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN,
-                 device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, progressive: bool = False):
+                 device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, progressive: bool = False,
+                 candidates=None, max_score: int | None = None):
         torch = batch._torch()
         self.n_channels = int(n_channels)
-        rates = _per_channel(bit_frames, self.n_channels, "bit_frames")
-        if rates is None:
-            batch.validate_bit_frames(int(bit_frames))
-            rates = [int(bit_frames)] * max(self.n_channels, 1)
-        elif any(int(b) != b for b in rates):
-            raise ValueError("bit_frames must hold integers")
-        batch.validate_bit_frames(np.asarray(rates, np.int64))
-        self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
-        self.bit_frames = None if len(set(rates)) > 1 else int(rates[0]) if rates else None
+        self.auto = isinstance(bit_frames, str) and bit_frames == "auto"
+        if self.auto:
+            if max_burst_len is not None:
+                raise ValueError('bit_frames="auto" needs the streaming receiver (max_burst_len=None): a burst\'s rate is '
+                                 "decided while it is gated")
+            self.candidates = batch.check_candidates(candidates)
+            if max_score is not None and (int(max_score) != max_score or not 0 <= int(max_score) < 2 ** 31):
+                raise ValueError(f"max_score must be None or an integer in 0 ... 2^31 - 1, got {max_score!r}")
+            self.max_score = None if max_score is None else int(max_score)
+            # no channel has a rate of its own; the tap row is sized by the smallest candidate
+            rates = [min(self.candidates)]
+            self.channel_bit_frames = np.zeros(max(self.n_channels, 0), np.int32)
+            self.bit_frames = None
+        else:
+            if candidates is not None or max_score is not None:
+                raise ValueError('candidates= and max_score= need bit_frames="auto"')
+            rates = _per_channel(bit_frames, self.n_channels, "bit_frames")
+            if rates is None:
+                batch.validate_bit_frames(int(bit_frames))
+                rates = [int(bit_frames)] * max(self.n_channels, 1)
+            elif any(int(b) != b for b in rates):
+                raise ValueError("bit_frames must hold integers")
+            batch.validate_bit_frames(np.asarray(rates, np.int64))
+            self.channel_bit_frames = np.asarray(rates, np.int32)[: max(self.n_channels, 0)]
+            self.bit_frames = None if len(set(rates)) > 1 else int(rates[0]) if rates else None
         self.channel_amp_start = _channel_thresholds(amp_start_threshold, self.n_channels, "amp_start_threshold",
                                                      batch.threshold_gt)
         self.channel_amp_end = _channel_thresholds(amp_end_threshold, self.n_channels, "amp_end_threshold",
@@ -704,7 +760,13 @@ class LiveReceiver(batch._NativePlan):
         nbytes = C.c_int64()
         with torch.cuda.device(self.device):
             # (one rate / one threshold pair in every entry: the C entries build the one-rate / one-pair receiver)
-            if self.progressive:
+            if self.auto:
+                cands = np.asarray(self.candidates, np.int32)
+                _native.check(_native.lib().afsk_live_create_stream_auto(
+                    self.n_channels, _i32_ptr(cands), int(cands.size), -1 if self.max_score is None else self.max_score,
+                    _i32_ptr(self.channel_amp_start), _i32_ptr(self.channel_amp_end), self.max_payload_len,
+                    self.max_chunk_len, int(self.progressive), C.byref(self._h)))
+            elif self.progressive:
                 _native.check(_native.lib().afsk_live_create_stream_tap(
                     self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_amp_start),
                     _i32_ptr(self.channel_amp_end), self.max_payload_len, self.max_chunk_len, C.byref(self._h)))
@@ -744,7 +806,7 @@ class LiveReceiver(batch._NativePlan):
         """Output buffers for ``push(out=...)`` (double-buffered pushes, graph capture).  ``diagnostics``: also the
         demodulator's ``corrected`` / ``margins`` (``margin_stride`` symbols per slot, default: the longest burst);
         a streaming receiver has ``corrected`` only (``margins`` None).  A progressive receiver's result also holds the
-        tap tensors (``LiveResult.tap``)."""
+        tap tensors (``LiveResult.tap``), an auto receiver's ``bit_frames`` and ``rate_score``."""
         torch = batch._torch()
         n, s, dev = self.n_channels, self.slots, self.device
         demod = batch.alloc_result(n * s, self.out_stride, dev)
@@ -759,8 +821,9 @@ class LiveReceiver(batch._NativePlan):
         if self.progressive:
             tap = LiveTap(z(torch.uint8, n, self.tap_cap), z(torch.int32, n), z(torch.int32, n, s),
                           torch.full((n,), -1, dtype=torch.int64, device=dev), z(torch.int32, n))
+        rate = (z(torch.int32, n, s), torch.full((n, s), -1, dtype=torch.int32, device=dev)) if self.auto else (None, None)
         return LiveResult(z(torch.int32, n), z(torch.int64, n, s), z(torch.int32, n, s), z(torch.int32, n, s), demod,
-                          tap)
+                          tap, *rate)
 
     def _alloc_packed(self, kind, max_records: int, max_bytes: int):
         """A ``kind`` (``LiveEvents`` / ``LiveSegments``) over one zeroed uint8 device allocation of its layout."""
@@ -919,6 +982,10 @@ class LiveReceiver(batch._NativePlan):
             raise ValueError("out= was not allocated by this receiver's alloc_result")
         if self.progressive and (out.tap is None or tuple(out.tap.bytes.shape) != (self.n_channels, self.tap_cap)):
             raise ValueError("out= was not allocated by this progressive receiver's alloc_result")
+        if self.auto and any(t is None or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()
+                             or tuple(t.shape) != (self.n_channels, self.slots)
+                             for t in (out.bit_frames, out.rate_score)):
+            raise ValueError("out= was not allocated by this auto receiver's alloc_result")
         d = out.demod
         soft = (None, None, 0)
         if d.corrected is not None and d.margins is not None:
@@ -941,7 +1008,12 @@ class LiveReceiver(batch._NativePlan):
                 t = out.tap
                 taps = (t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
                         t.open_nbytes.data_ptr())
-            if ragged:
+            if self.auto:
+                _native.check(_native.lib().afsk_live_push_auto(
+                    *head, None if lens is None else lens.data_ptr(), int(bool(flush)),
+                    None if mask is None else mask.data_ptr(), *outs, *taps, out.bit_frames.data_ptr(),
+                    out.rate_score.data_ptr(), batch._stream_ptr(stream, dev)))
+            elif ragged:
                 _native.check(_native.lib().afsk_live_push_ragged(
                     *head, None if lens is None else lens.data_ptr(), int(bool(flush)),
                     None if mask is None else mask.data_ptr(), *outs, *taps, batch._stream_ptr(stream, dev)))

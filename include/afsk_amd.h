@@ -982,6 +982,55 @@ extern int afsk_detect_rate_batch(const int16_t *samples, const int64_t *stream_
                                   void *hip_stream);
 
 /*
+ * The auto-rate streaming live receiver (an addition: ABI version unchanged): a streaming receiver
+ * (afsk_live_create_stream_thresholds) whose channels have no rate of their own.  The rate is decided per BURST, on the
+ * device, inside the push that records the burst's second block: over the burst's first 4096 samples every candidate's
+ * (ci, score) is computed exactly as defined for afsk_detect_rate_batch above, the smallest score wins and the earliest
+ * list position wins a tie.  From then on the burst is what a fixed-rate streaming receiver of the winner's rate makes of
+ * it: clock index = the winner's ci, the per-symbol squelch from the channel's amp_end and that rate, the same terminator
+ * search, squelch stop, Hamming decode, payload row, truncation at max_payload_len and tap.  A channel's successive
+ * bursts may have any rates in any order.  The open burst's rate is part of the channel's state: it survives across
+ * pushes and is cleared where the open burst is dropped (afsk_live_reset, masked or not).
+ *
+ *  afsk_live_create_stream_auto  cand_bit_frames_host: [n_cand] HOST array, 1 <= n_cand <= AFSK_DETECT_MAX_CANDIDATES,
+ *                        each a bit_frames afsk_demod_batch_uniform accepts (else AFSK_E_INVALID_BAUD); duplicates are
+ *                        legal; candidates with bf >= 1200 are accepted and unreliable, as for the detector.  max_score
+ *                        >= 0: a burst whose best score exceeds it is not demodulated (below); < 0: none.  amp_start_host
+ *                        / amp_end_host: [n_channels] each, as afsk_live_create_stream_thresholds (one pair for all
+ *                        channels: the shared-pair receiver).  tap = 1: with the payload tap of
+ *                        afsk_live_create_stream_tap, its tap_cap = AFSK_LIVE_TAP_CAP(max_chunk_len, the smallest
+ *                        candidate); tap = 0: without.  State, slots and limits: afsk_live_stream_layout's.
+ *  afsk_live_push_auto   afsk_live_push_ragged's arguments, checks and outputs, and in front of hip_stream two more
+ *                        DEVICE arrays, int32 [n_channels * slots], written by every push:
+ *                          out_bit_frames   the burst's detected bit_frames; 0 for an unused slot, for a burst reported
+ *                                           with fewer than 4096 samples (status AFSK_ST_TOO_SHORT, as on every
+ *                                           receiver) and for a burst refused by max_score
+ *                          out_rate_score   the winner's score; -1 for an unused slot and for such a short burst
+ *                        A burst refused by max_score reports status AFSK_ST_INVALID_BAUD, nbytes = nbits = 0,
+ *                        clock_idx = term_frame = -1, out_bit_frames 0 and its score, and hands out no tap bytes.
+ *                        NULL lengths and a NULL mask launch the plain cells.  The five tap outputs are all NULL or all
+ *                        given; given needs tap = 1.  ONE launch on hip_stream, no allocation, no synchronisation:
+ *                        capturable into a graph.  With ONE candidate r every output equals, bit for bit, that of the
+ *                        fixed-rate streaming receiver at r.
+ * afsk_live_push, afsk_live_push_tap and afsk_live_push_ragged refuse an auto-rate receiver and afsk_live_push_auto
+ * refuses every other one (AFSK_E_INVALID_ARG; afsk_last_error names the right entry).  afsk_live_info, afsk_live_reset,
+ * afsk_live_destroy, afsk_live_pack and afsk_live_pack_tap serve it unchanged.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_AUTO_SIGNATURES.)
+ */
+extern int afsk_live_create_stream_auto(int32_t n_channels, const int32_t *cand_bit_frames_host, int32_t n_cand,
+                                        int32_t max_score /* < 0: none */, const int32_t *amp_start_host,
+                                        const int32_t *amp_end_host, int32_t max_payload_len, int32_t max_chunk_len,
+                                        int32_t tap /* 0 / 1 */, afsk_live **out);
+extern int afsk_live_push_auto(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                               const int32_t *d_chunk_lens_or_null, int32_t flush, const uint8_t *d_flush_mask_or_null,
+                               int32_t *out_n_closed, int64_t *out_burst_start, int32_t *out_burst_len,
+                               int32_t *out_flags, uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes,
+                               int32_t *out_nbits, int32_t *out_clock_idx, int32_t *out_term_frame, int32_t *out_status,
+                               int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride, uint8_t *tap_bytes,
+                               int32_t *tap_n, int32_t *tap_len, int64_t *open_start, int32_t *open_nbytes,
+                               int32_t *out_bit_frames, int32_t *out_rate_score, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
