@@ -226,6 +226,14 @@ LIVE_AUTO_SIGNATURES = {
                             + [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The relay submit of the live transmitter (afsk_live_relay_check_map, afsk_live_tx_submit_events), likewise.
+LIVE_RELAY_SIGNATURES = {
+    "afsk_live_relay_check_map": (C.c_int, [_i32p, C.c_int32, C.c_int32]),
+    "afsk_live_tx_submit_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+LIVE_TX_SKIPPED, LIVE_TX_NONE = 5, -1        # AFSK_LIVE_TX_* statuses of afsk_live_tx_submit_events alone
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -242,7 +250,7 @@ def lib() -> C.CDLL:
                                   *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
-                                  *LIVE_AUTO_SIGNATURES.items()):
+                                  *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -296,3 +296,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The live transmitter (afsk_live_tx_*: per-channel message queues pulled chunk by chunk) is compiled as part of this
 // translation unit: build.sh compiles a fixed list of files, and it renders with this file's tone_words scheme.
 #include "afsk_live_tx.hip"
+
+// The relay submit of the live transmitter (afsk_live_relay_check_map, afsk_live_tx_submit_events) comes behind it for
+// the same reason: it queues on the transmitter's state, whose layout afsk_live_tx.hip defines.
+#include "afsk_live_relay.hip"

@@ -18,7 +18,9 @@ Any sequence of pushes followed by a flush reports what ``gate_batch`` +
 
 Transmit: a ``LiveTransmitter`` keeps a queue of messages per channel on the device; each ``pull`` writes the next T
 samples of every channel (``afsk_live_tx_pull``), the queued messages back to back, each exactly what
-``Transmitter.save`` writes for it.  Nothing here opens an audio device.
+``Transmitter.save`` writes for it.  Nothing here opens an audio device.  ``LiveTransmitter.submit_events`` queues the
+bursts a receiver's push closed straight from its packed event list (``afsk_live_tx_submit_events``): a relay whose tick
+-- push, pack, submit, pull -- never leaves the device.
 
 Both take one rate for all channels or one per channel (a sequence of n_channels), interleaved in any order, so a
 ``[channels, time]`` buffer of mixed rates is pushed or pulled as it is (``afsk_live_create_mixed``,
@@ -1086,8 +1088,10 @@ def tx_state_bytes_mixed(n_channels: int, queue_depth: int, max_payload_len: int
 
 @dataclass
 class SubmitResult:
-    """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order."""
-    status: "object"         # int32 [n] LIVE_TX_QUEUED / _QUEUE_FULL / _TOO_LONG / _BAD_CHANNEL
+    """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order, or of one
+    ``submit_events``, entry i for record i of the events buffer."""
+    status: "object"         # int32 [n] LIVE_TX_QUEUED / _QUEUE_FULL / _TOO_LONG / _BAD_CHANNEL (submit_events: also
+                             # _UNSORTED, _SKIPPED and, from the push's record count on, _NONE)
     start: "object"          # int64 [n] stream index of the first sample (-1: rejected)
     n_samples: "object"      # int32 [n] samples of the message (0: rejected)
 
@@ -1227,6 +1231,113 @@ class LiveTransmitter(batch._NativePlan):
                 self.handle, n, base + 8 * n, base, base + 12 * n, base + head, None if ordered else base + 16 * n,
                 out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(), batch._stream_ptr(s, dev)))
         out._keepalive = d  # type: ignore[attr-defined]
+        return out
+
+    def alloc_submit_result(self, max_events: int) -> SubmitResult:
+        """Output tensors for ``submit_events(out=...)``: one entry per record place of an events buffer of
+        ``max_events`` records (fixed addresses for a captured graph)."""
+        torch = batch._torch()
+        dev, n = self.device, int(max_events)
+        return SubmitResult(torch.full((n,), _native.LIVE_TX_NONE, dtype=torch.int32, device=dev),
+                            torch.full((n,), -1, dtype=torch.int64, device=dev),
+                            torch.zeros(n, dtype=torch.int32, device=dev))
+
+    def _relay_map(self, channel_map, n_rx: int):
+        """``channel_map`` of ``submit_events`` as ``(int32 [n_rx] tensor on the device or None, uploaded by this
+        call)``: a CUDA tensor is used in place; a host sequence is checked with ``afsk_live_relay_check_map`` and
+        uploaded, and the upload is kept for as long as the same contents are passed."""
+        torch = batch._torch()
+        dev = self.device
+        if channel_map is None:
+            return None, False
+        if isinstance(channel_map, torch.Tensor) and channel_map.is_cuda:
+            if channel_map.dtype != torch.int32:
+                raise TypeError("channel_map must hold int32 transmitter channels")
+            if channel_map.device != dev:
+                raise ValueError(f"channel_map is on {channel_map.device}, the transmitter on {dev}")
+            if channel_map.dim() != 1 or int(channel_map.numel()) != n_rx or not channel_map.is_contiguous():
+                raise ValueError(f"channel_map must be a contiguous [n_rx_channels={n_rx}], got "
+                                 f"{list(channel_map.shape)}")
+            return channel_map, False
+        v = np.asarray(channel_map.cpu() if isinstance(channel_map, torch.Tensor) else channel_map)
+        if v.dtype.kind not in "iu":
+            raise TypeError("channel_map must hold integer transmitter channels")
+        if v.ndim != 1 or v.size != n_rx:
+            raise ValueError(f"channel_map must be [n_rx_channels={n_rx}], got {list(v.shape)}")
+        # (beyond int32: not a channel of any transmitter either way)
+        v = np.ascontiguousarray(np.clip(v.astype(np.int64), -1, 2 ** 31 - 1).astype(np.int32))
+        key = v.tobytes()
+        cached = getattr(self, "_relay_map_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1], False
+        _native.check(_native.lib().afsk_live_relay_check_map(_i32_ptr(v), n_rx, self.n_channels))
+        t = torch.from_numpy(v).to(dev)
+        self._relay_map_cache = (key, t)
+        return t, True
+
+    def submit_events(self, events: "LiveEvents", channel_map=None, skip_flags: int = _native.LIVE_OPEN_END,
+                      out: SubmitResult | None = None, stream=None) -> SubmitResult:
+        """Relay: queue the bursts a receiver's push closed, straight from its packed event list on the device
+        (``afsk_live_tx_submit_events``) -- no copy to the host and no synchronisation, so ``push(events=)``,
+        ``submit_events(out=)`` and ``pull`` of fixed buffers can be captured into ONE graph.
+
+        ``events``: the ``LiveEvents`` of a ``push(events=...)`` / ``pack`` over a CUDA buffer on the transmitter's
+        device; its referenced result supplies the receiver's channel count and payload row width.  A burst is relayed
+        when it decoded (status ``ST_OK``), holds at least one byte, was not cut short (``LIVE_OVERFLOW``, a truncated
+        streaming row, a payload that did not fit the events buffer) and carries none of ``skip_flags``; the default
+        skips a burst a flush reported while it was still recording (``LIVE_OPEN_END``: its payload may be cut short),
+        ``skip_flags=0`` relays it.  Everything else gets ``LIVE_TX_SKIPPED``.
+
+        ``channel_map``: None -- receiver channel c goes to transmitter channel c -- or one transmitter channel per
+        receiver channel: a negative entry drops the channel (``LIVE_TX_SKIPPED``), an entry past the transmitter's
+        channels answers ``LIVE_TX_BAD_CHANNEL``, and no two receiver channels may name one transmitter channel.  A
+        host sequence is checked (``afsk_live_relay_check_map``) and uploaded once, the upload is reused while the same
+        contents are passed (pass it once before capturing a graph); an int32 CUDA tensor is used in place, unchecked.
+
+        The result holds ``[max_events]`` tensors, entry i for record i: the statuses, starts and sample counts of
+        ``submit``, ``LIVE_TX_SKIPPED``, and ``LIVE_TX_NONE`` from the push's record count on.  ``out``
+        (``alloc_submit_result``) reuses them.  Asynchronous on ``stream`` (default: torch's current stream), behind
+        the pack when that ran on the same stream."""
+        _native.require_device()
+        torch = batch._torch()
+        if not isinstance(events, LiveEvents):
+            raise TypeError("events must be the LiveEvents of a push(events=...) or pack")
+        dev = self.device
+        buf, res = events.buffer, events.result
+        if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise ValueError("events must lie in a contiguous uint8 CUDA buffer (LiveReceiver.alloc_events)")
+        if buf.device != dev:
+            raise ValueError(f"events is on {buf.device}, the transmitter on {dev}")
+        if res is None:
+            raise ValueError("events references no LiveResult: pack a push into it first (push(events=...))")
+        n_rx, stride = int(res.n_closed.shape[0]), int(res.demod.bytes.shape[1])
+        me, mb = events.max_events, events.max_bytes
+        ro, po, total = events_layout(n_rx, res.slots, me, mb)
+        if (events.records_offset, events.payload_offset) != (ro, po) or int(buf.numel()) < total:
+            raise ValueError("events was not allocated by a receiver's alloc_events for this push")
+        skip = int(skip_flags)
+        if skip & ~(_native.LIVE_OPEN_END | _native.LIVE_OVERFLOW):
+            raise ValueError("skip_flags may hold LIVE_OPEN_END and LIVE_OVERFLOW alone")
+        cmap, uploaded = self._relay_map(channel_map, n_rx)
+        fresh = out is None
+        if fresh:
+            out = SubmitResult(torch.empty(me, dtype=torch.int32, device=dev),
+                               torch.empty(me, dtype=torch.int64, device=dev),
+                               torch.empty(me, dtype=torch.int32, device=dev))
+        elif any(not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or tuple(t.shape) != (me,)
+                 or not t.is_contiguous()
+                 for t, dt in ((out.status, torch.int32), (out.start, torch.int64), (out.n_samples, torch.int32))):
+            raise ValueError(f"out= was not allocated by alloc_submit_result({me})")
+        with torch.cuda.device(dev):
+            if fresh or uploaded:
+                batch._order_after_current(stream, dev)
+            if uploaded and stream is not None:
+                cmap.record_stream(stream)
+            _native.check(_native.lib().afsk_live_tx_submit_events(
+                self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
+                out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(),
+                batch._stream_ptr(stream, dev)))
+        out._keepalive = (buf, cmap)  # type: ignore[attr-defined]
         return out
 
     def pull(self, T: int, out=None, stream=None, lengths=None):

@@ -1031,6 +1031,62 @@ extern int afsk_live_push_auto(afsk_live *live, const int16_t *chunk, int64_t ch
                                int32_t *out_bit_frames, int32_t *out_rate_score, void *hip_stream);
 
 /*
+ * The relay submit of the live transmitter (added after ABI version 2; the version is unchanged): a station that
+ * answers what it hears -- a digipeater, a cross-rate gateway, a many-channel repeater -- queues the bursts a push closed
+ * on a live transmitter straight from the packed event list afsk_live_pack left on the device.  Nothing goes through the
+ * host, so push + pack + submit + pull is one capturable chain of launches.
+ *
+ *  afsk_live_relay_check_map   host-only (no device needed).  map_host: HOST int32 [n_rx_channels]; entry c is the
+ *                              transmitter channel the bursts of receiver channel c go to.  A negative entry: channel c
+ *                              is not relayed.  An entry >= n_tx_channels is allowed (its records are answered with
+ *                              AFSK_LIVE_TX_BAD_CHANNEL).  Two receiver channels that name the same transmitter channel
+ *                              in 0 ... n_tx_channels - 1: AFSK_E_INVALID_ARG, afsk_last_error names both (the submit
+ *                              gives every destination channel to ONE wave; an ordering rule across receiver channels
+ *                              does not exist).  A NULL map is the identity: AFSK_OK.  n_rx_channels < 1 or
+ *                              n_tx_channels < 1: AFSK_E_INVALID_ARG.
+ *  afsk_live_tx_submit_events  events: a DEVICE events buffer as afsk_live_pack wrote it, with the offsets of
+ *                              afsk_live_events_layout for these max_events / max_bytes; out_stride: that push's;
+ *                              n_rx_channels: the receiver's channels; d_channel_map_or_null: DEVICE int32
+ *                              [n_rx_channels] (a map afsk_live_relay_check_map accepts) or NULL, the identity.  The
+ *                              three outputs are DEVICE arrays of max_events entries, all written by every call.
+ *                              `stored` is read on the device and clamped to 0 ... max_events.  Record i, in this order:
+ *                                1. i >= stored: AFSK_LIVE_TX_NONE, start -1, n_samples 0
+ *                                2. at or after the first stored record whose channel is below its predecessor's:
+ *                                   AFSK_LIVE_TX_UNSORTED (afsk_live_tx_submit's guard; a real pack never trips it)
+ *                                3. not relayable: AFSK_LIVE_TX_SKIPPED -- flags & (AFSK_LIVE_OVERFLOW | skip_flags),
+ *                                   status != AFSK_ST_OK, nbytes < 1, nbytes > out_stride (a truncated streaming row),
+ *                                   payload_offset < 0 or payload_offset + nbytes > max_bytes
+ *                                4. the destination: the record's channel without a map.  With a map a record channel
+ *                                   outside 0 ... n_rx_channels - 1 gets AFSK_LIVE_TX_BAD_CHANNEL (the map is not read
+ *                                   for it), else dst = map[channel]: negative AFSK_LIVE_TX_SKIPPED, >= the
+ *                                   transmitter's channels AFSK_LIVE_TX_BAD_CHANNEL
+ *                                5. afsk_live_tx_submit's rules and outputs on channel dst with the record's nbytes
+ *                                   payload bytes: _TOO_LONG, _QUEUE_FULL, or _QUEUED with start = max(pos, end) and
+ *                                   n_samples from dst's geometry (uniform and mixed transmitters alike)
+ *                              A destination channel's records are queued in record order; the state afterwards is what
+ *                              afsk_live_tx_submit leaves when given the relayable records' destinations and payloads
+ *                              in that order.  skip_flags: AFSK_LIVE_OPEN_END skips a burst a flush reported while it
+ *                              was still recording (its payload may be cut short), 0 relays it.  Reads the header, the
+ *                              first `stored` records, the payload bytes of queued records and the map; writes nothing
+ *                              of the events buffer; whatever the header and the records hold, no access leaves the
+ *                              buffers given (a payload range outside [0, max_bytes) is skipped, not read).  At most
+ *                              two launches in order on hip_stream, no allocation, no synchronisation, no host read of
+ *                              a device value: capturable behind push and pack.  AFSK_E_INVALID_ARG, nothing launched:
+ *                              a NULL tx, events or output; max_events, max_bytes or out_stride < 0; n_rx_channels < 1;
+ *                              skip_flags with bits other than AFSK_LIVE_OPEN_END | AFSK_LIVE_OVERFLOW; an events
+ *                              pointer that is not 16-byte aligned.  max_events == 0: AFSK_OK, no launch.
+ * Submits of both kinds, pulls and resets of one transmitter must run in order.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_RELAY_SIGNATURES.)
+ */
+#define AFSK_LIVE_TX_SKIPPED 5 /* afsk_live_tx_submit_events: the record is not relayable or its channel is not mapped */
+#define AFSK_LIVE_TX_NONE (-1) /* afsk_live_tx_submit_events: the entry is at or past `stored`: no record            */
+extern int afsk_live_relay_check_map(const int32_t *map_host, int32_t n_rx_channels, int32_t n_tx_channels);
+extern int afsk_live_tx_submit_events(afsk_live_tx *tx, const void *events, int32_t max_events, int32_t max_bytes,
+                                      int32_t out_stride, int32_t n_rx_channels, const int32_t *d_channel_map_or_null,
+                                      int32_t skip_flags, int32_t *out_status, int64_t *out_start,
+                                      int32_t *out_n_samples, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
