@@ -5,11 +5,11 @@ group plan.  afsk_capi.hip is compiled AS IS and linked, for this test only, aga
 (tests/helpers/hip_stub_runtime.cpp: device memory = host memory, every stream an in-order worker thread, so
 copies are really asynchronous) and stub kernel launchers -- so "device" buffers are numpy arrays whose
 contents can be checked byte for byte against the stdlib `wave` reader the reference calls (afskmodem.py:214).
+The library is that of tests/helpers/build_stub_lib.sh, built through tests/stub_lib.py.
 tools/capi_asan.sh runs this file again against ThreadSanitizer and AddressSanitizer builds (AFSK_STUB_LIB).
 Nothing here is a product path: the product library fails loudly without a device (tests/test_host_api.py)."""
 import ctypes as C
 import os
-import subprocess
 import threading
 import wave
 
@@ -17,18 +17,15 @@ import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests import stub_lib
 from tests.golden_inputs import build_riff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATTERN = 0x5A5A
 
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    path = os.environ.get("AFSK_STUB_LIB")
-    if not path:
-        path = str(tmp_path_factory.mktemp("stub") / "libafsk_stub.so")
-        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "helpers", "build_stub_lib.sh"), path])
+    path = os.environ.get("AFSK_STUB_LIB") or stub_lib.build(tmp_path_factory, "build_stub_lib.sh")
     os.environ.setdefault("AFSK_INGEST_WINDOW_MB", "4")      # small windows: a 9 MB file spans three of them
     os.environ.setdefault("AFSK_INGEST_SLOTS", "3")          # a short ring: buffers are reused many times
     os.environ.setdefault("AFSK_IO_THREADS", "6")

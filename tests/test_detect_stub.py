@@ -1,18 +1,18 @@
 """The host logic of afsk_detect_rate_batch through the stub HIP runtime (no GPU): the host code of afsk_gate.hip -- the
-detector's entry is part of that translation unit -- built against tests/helpers, where "device" memory is host memory
-and a launch records the kernel's name and a copy of its argument struct instead of running.  The return codes of the
-entry, one launch per call and none for a refused or empty one, the grid, and the candidate list passed BY VALUE: it is
-found in the launch's argument bytes after the caller's own array has been overwritten."""
+detector's entry is part of that translation unit -- built against tests/helpers (build_stub_live_lib.sh, loaded
+through tests/stub_lib.py), where "device" memory is host memory and a launch records the kernel's name and a copy of
+its argument struct instead of running.  The return codes of the entry, one launch per call and none for a refused or
+empty one, the grid, and the candidate list passed BY VALUE: it is found in the launch's argument bytes after the
+caller's own array has been overwritten."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from afskmodem_amd import _native, batch
+from tests import stub_lib
+from tests.stub_lib import last_kernel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = "_ZN4afsk18detect_rate_kernelENS_10DetectArgsE"
 # what the argument struct holds at least: eight pointers, two counts, 36 candidates
 ARG_BYTES = 8 * 8 + 2 * 4 + 4 * 36
@@ -21,23 +21,9 @@ N = 70
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("afsk_stub_detect") / "libafsk_stub_detect.so")
-    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "helpers", "build_stub_detect_lib.sh"), path])
-    lib = C.CDLL(path)
-    for name, (res, args) in _native.DETECT_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    lib.afsk_stub_last_kernel.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint)]
-    lib.afsk_stub_last_arg0.argtypes = [C.c_char_p, C.c_int]
-    lib.afsk_stub_capture_arg0.argtypes = [C.c_int]
+    lib = stub_lib.load(tmp_path_factory, "afsk_stub_detect", [_native.DETECT_SIGNATURES])
     lib.afsk_stub_capture_arg0(ARG_BYTES)
     return lib
-
-
-def last_kernel(lib):
-    buf, grid = C.create_string_buffer(256), C.c_uint()
-    n = lib.afsk_stub_last_kernel(buf, 256, C.byref(grid))
-    return n, buf.value.decode(), grid.value
 
 
 class Call:

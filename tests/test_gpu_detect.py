@@ -12,18 +12,10 @@ import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, batch
 from oracle import afsk_oracle as O
 from tests import detect_model as M
+from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 FIELDS = ("bit_frames", "score", "runner_up", "clock_idx", "scores")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    # fail loudly: GPU tests must exercise the HIP library, never a fallback
-    assert _native.device_count() > 0, "no HIP device: GPU tests need an MI355X"
-    assert torch.cuda.is_available()
-    return torch
 
 
 def place(torch, streams, lens=None):

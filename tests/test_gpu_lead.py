@@ -9,21 +9,14 @@ on 4096+, clock index == lead wherever the training tone survives the .wav write
 import numpy as np
 import pytest
 
-from afskmodem_amd import _native, batch, synth
+from afskmodem_amd import batch, synth
 from oracle import afsk_oracle as O
+from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
 TOTAL = 48000
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert _native.device_count() > 0, "no HIP device: GPU tests need an MI355X"
-    assert torch.cuda.is_available()
-    return torch
 
 
 def lead_batch(torch, n, bauds, seed, max_lead=2048, noise=600, wav_quirk=True):

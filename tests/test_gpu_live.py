@@ -13,45 +13,13 @@ from afskmodem_amd.live import LiveReceiver
 from oracle import afsk_oracle as O
 from tests.golden_inputs import build_capture, listen_cases
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import BLOCK, FIELDS, collect, push_sizes
 
 pytestmark = pytest.mark.gpu
-FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
-BLOCK = 2048
+STEPS = [0, 1, 5, 2047, 2048, 2049, 4000, 9000, 15000]      # what a "ragged" chunking draws its push sizes from
 
 
-def sizes_for(kind, total, rng=None):
-    """Push sizes summing to total."""
-    if kind == "whole":
-        return [total]
-    if kind == "ragged":
-        out, left = [], total
-        while left > 0:
-            t = min(int(rng.choice([0, 1, 5, 2047, 2048, 2049, 4000, 9000, 15000])), left)
-            out.append(t)
-            left -= t
-        return out
-    step = int(kind)
-    return [min(step, total - p) for p in range(0, total, step)] or [0]
-
-
-def collect(res, got):
-    """Append the bursts one push reported to got[c] as dicts (synchronises)."""
-    nc = res.n_closed.cpu().numpy()
-    if not nc.any():
-        return
-    bs, bl, fl = (t.cpu().numpy() for t in (res.burst_start, res.burst_len, res.flags))
-    d = res.demod.cpu()
-    s = res.slots
-    for c in np.nonzero(nc)[0].tolist():
-        for k in range(int(nc[c])):
-            i = c * s + k
-            row = dict(start=int(bs[c, k]), len=int(bl[c, k]), flags=int(fl[c, k]),
-                       bytes=d.bytes[i, : min(int(d.nbytes[i]), d.bytes.shape[1])].tobytes())
-            row.update({f: int(getattr(d, f)[i]) for f in FIELDS})
-            got[c].append(row)
-
-
-def drive(rx, data, sizes, flush=True):
+def drive_flush_last(rx, data, sizes, flush=True):
     """Push the column windows of data ([n, L] device) of the given sizes, flush with the last one."""
     got = [[] for _ in range(data.shape[0])]
     pos = 0
@@ -117,7 +85,7 @@ def test_reference_listen_cases_in_every_chunking(golden, torch_cuda, pair):
         rx = LiveReceiver(len(group), 40, a_start, a_end, max_burst_len=65536, max_chunk_len=total)
         first = None
         for kind in ("whole", "2048", "1", "2047", "2049", "3000", "ragged"):
-            got = drive(rx, dev, sizes_for(kind, total, rng))
+            got = drive_flush_last(rx, dev, push_sizes(kind, total, rng, STEPS))
             for j, i in enumerate(group):
                 c = cases[i]
                 spans = [(g["start"], g["len"], g["flags"]) for g in got[j]]
@@ -149,7 +117,7 @@ def test_random_captures_and_the_slot_bound(torch_cuda):
         rx = LiveReceiver(1, 40, max_burst_len=1 << 17, max_chunk_len=15000)
         d = torch.from_numpy(cap.reshape(1, -1).copy()).to("cuda:0")
         for kind in ("2047", "8192", "ragged"):
-            got = drive(rx, d, sizes_for(kind, len(cap), rng))
+            got = drive_flush_last(rx, d, push_sizes(kind, len(cap), rng, STEPS))
             assert [(g["start"], g["len"], g["flags"]) for g in got[0]] == oracle_bursts(cap, 18000, 14000), (i, kind)
         rx.close()
     # bursts closing every third block: after a burst opened with a 2047-sample carry, one push of max_chunk_len
@@ -201,7 +169,7 @@ def test_real_payloads_in_noise(torch_cuda, baud):
         host[c] = O.add_noise(host[c], 5, c, synth.snr_to_scale_q24(float(snr[c])))
     dev = torch.from_numpy(host).to("cuda:0")
     rx = afskmodem.Receiver(baud).live(n, max_burst_len=4 * 48000, max_chunk_len=4800)
-    got = drive(rx, dev, sizes_for("4800", total))
+    got = drive_flush_last(rx, dev, push_sizes("4800", total))
     for c in range(n):
         spans = [(g["start"], g["len"], g["flags"]) for g in got[c]]
         assert spans == oracle_bursts(host[c], 18000, 14000), c
@@ -224,7 +192,7 @@ def test_overflow_is_flagged_and_not_decoded(torch_cuda):
     dev = torch.from_numpy(host).to("cuda:0")
     rx = LiveReceiver(2, 40, max_burst_len=16384, max_chunk_len=3000)
     for kind in ("3000", "2048"):
-        got = drive(rx, dev, sizes_for(kind, len(cap)))
+        got = drive_flush_last(rx, dev, push_sizes(kind, len(cap)))
         for c in range(2):
             assert [(g["start"], g["len"], g["flags"]) for g in got[c]] == [
                 (s, n, f | (_native.LIVE_OVERFLOW if n > 16384 else 0)) for s, n, f in oracle_bursts(host[c], 18000, 14000)]
@@ -244,8 +212,8 @@ def test_flush_starts_new_streams_and_masked_reset(golden, torch_cuda):
     host, dev = padded(torch, caps)
     rx = LiveReceiver(len(caps), 40, max_burst_len=65536, max_chunk_len=5000)
     half = host.shape[1] // 2 + 1000
-    drive(rx, dev[:, :half], sizes_for("5000", half))             # flushed part-way through the first captures
-    got = drive(rx, dev, sizes_for("5000", host.shape[1]))        # a new stream: the whole captures from sample 0
+    drive_flush_last(rx, dev[:, :half], push_sizes("5000", half))   # flushed part-way through the first captures
+    got = drive_flush_last(rx, dev, push_sizes("5000", host.shape[1]))  # a new stream: the whole captures from sample 0
     g = batch.gate_batch(dev.reshape(-1), torch.arange(len(caps), device="cuda:0", dtype=torch.int64) * host.shape[1],
                          torch.full((len(caps),), host.shape[1], dtype=torch.int32, device="cuda:0"), host.shape[1],
                          18000, 14000, 16)

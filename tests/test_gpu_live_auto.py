@@ -10,35 +10,12 @@ from afskmodem_amd import _native, batch
 from afskmodem_amd.live import LiveReceiver
 from tests import live_auto_model as M
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import BLOCK, collect, drive, push_sizes, same
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BLOCK = 2048
-FIELDS = M.FIELDS
+STEPS = [1, 7, 2047, 2048, 2049, 5000, 8192]                # what a "random" chunking draws its push sizes from
 TAP_FIELDS = ("bytes", "n", "len", "open_start", "open_nbytes")
-
-
-def collect(res, got, corrected=False):
-    """Append one push's bursts to got[c] as dicts (every field, the row up to nbytes, the rate outputs if any)."""
-    nc = res.n_closed.cpu().numpy()
-    if not nc.any():
-        return
-    bs, bl, fl = (t.cpu().numpy() for t in (res.burst_start, res.burst_len, res.flags))
-    d = res.demod.cpu()
-    cor = res.demod.corrected.cpu().numpy() if corrected else None
-    rate = None if res.bit_frames is None else (res.bit_frames.cpu().numpy(), res.rate_score.cpu().numpy())
-    s = res.slots
-    for c in np.nonzero(nc)[0].tolist():
-        for k in range(int(nc[c])):
-            j = c * s + k
-            row = dict(start=int(bs[c, k]), len=int(bl[c, k]), flags=int(fl[c, k]),
-                       bytes=d.bytes[j, : min(int(d.nbytes[j]), d.bytes.shape[1])].tobytes())
-            row.update({f: int(getattr(d, f)[j]) for f in FIELDS})
-            if corrected:
-                row["corrected"] = int(cor[j])
-            if rate:
-                row["bit_frames"], row["rate_score"] = int(rate[0][c, k]), int(rate[1][c, k])
-            got[c].append(row)
 
 
 def unused_slots_are_clear(res):
@@ -46,37 +23,6 @@ def unused_slots_are_clear(res):
     bf, sc = res.bit_frames.cpu().numpy(), res.rate_score.cpu().numpy()
     for c in range(nc.size):
         assert not bf[c, nc[c]:].any() and (sc[c, nc[c]:] == -1).all(), c
-
-
-def sizes_for(T, total, rng):
-    if T == "random":
-        out = []
-        while sum(out) < total:
-            out.append(min(int(rng.choice([1, 7, 2047, 2048, 2049, 5000, 8192])), total - sum(out)))
-        return out
-    return [T] * (total // T) + ([total % T] if total % T else [])
-
-
-def drive(rx, d, sizes, corrected=False, flush=True, each=None):
-    got = [[] for _ in range(rx.n_channels)]
-    out = rx.alloc_result(diagnostics=corrected)
-    p = 0
-    for t in sizes:
-        collect(rx.push(d[:, p: p + t], out=out), got, corrected)
-        if each:
-            each(out)
-        p += t
-    assert p == d.shape[1]
-    if flush:
-        collect(rx.flush(out=out), got, corrected)
-        if each:
-            each(out)
-    return got
-
-
-def same(got, want):
-    """One channel's bursts against expected rows (every field the expected rows have)."""
-    return len(got) == len(want) and all({k: g[k] for k in w} == w for g, w in zip(got, want))
 
 
 def without_rates(rows):
@@ -105,7 +51,7 @@ def test_one_candidate_equals_the_fixed_rate_streaming_receiver(torch_cuda, r, T
     host = M.stack([M.rated_capture(rng, [(r, p) for p in pays[c]] + [("block", 30000)]) for c in range(n)], BLOCK)
     host[:, -BLOCK:] = 30000                                   # one loud block before the flush: a TOO_SHORT burst
     d = torch.from_numpy(host).to(DEV)
-    sizes = sizes_for(T, host.shape[1], rng)
+    sizes = push_sizes(T, host.shape[1], rng, STEPS)
     fixed = LiveReceiver(n, r, max_burst_len=None, device=DEV)
     auto = LiveReceiver(n, "auto", candidates=[r], max_burst_len=None, device=DEV)
     assert auto.auto and auto.bit_frames is None and not auto.channel_bit_frames.any() and auto.candidates == (r,)
@@ -140,7 +86,7 @@ def test_a_rate_per_burst_fast_slow_fast_on_one_channel(torch_cuda, rate_case, T
     assert [bf for bf, _ in sent[0]] == [8, 1000, 20] and [bf for bf, _ in sent[1]] == [1000, 20, 160]
     rx = LiveReceiver(host.shape[0], "auto", max_burst_len=None, device=DEV)
     assert rx.candidates == batch.VALID_BIT_FRAMES
-    got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(T, host.shape[1], np.random.default_rng(3)),
+    got = drive(rx, torch.from_numpy(host).to(DEV), push_sizes(T, host.shape[1], np.random.default_rng(3), STEPS),
                 each=unused_slots_are_clear)
     rx.close()
     check_rate_case(got, sent, want)
@@ -152,7 +98,7 @@ def test_the_reported_rate_score_and_clock_are_the_detectors(torch_cuda, rate_ca
     host, sent, _ = rate_case
     d = torch.from_numpy(host).to(DEV)
     rx = LiveReceiver(host.shape[0], "auto", max_burst_len=None, device=DEV)
-    got = drive(rx, d, sizes_for(8192, host.shape[1], None))
+    got = drive(rx, d, push_sizes(8192, host.shape[1]))
     rx.close()
     rows = [(c, g) for c in range(len(got)) for g in got[c]]
     assert len(rows) == 3 * host.shape[0]
@@ -168,7 +114,7 @@ def test_more_than_one_blocks_worth_of_channels(torch_cuda):
     torch = torch_cuda
     host, sent = M.rate_cases(M.SEED_LARGE, M.LARGE_CHANNELS, 1)
     rx = LiveReceiver(M.LARGE_CHANNELS, "auto", max_burst_len=None, device=DEV)
-    got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(8192, host.shape[1], None))
+    got = drive(rx, torch.from_numpy(host).to(DEV), push_sizes(8192, host.shape[1]))
     rx.close()
     check_rate_case(got, sent, [M.expected(cap) for cap in host])
 
@@ -184,7 +130,7 @@ def test_the_earliest_candidate_wins_a_tie(torch_cuda):
     d = torch.from_numpy(host).to(DEV)
     for cands, winner in (([160, 40], 160), ([40, 160], 40), ([40, 40, 160], 40)):
         rx = LiveReceiver(6, "auto", candidates=cands, max_burst_len=None, device=DEV)
-        got = drive(rx, d, sizes_for(8192, host.shape[1], None))
+        got = drive(rx, d, push_sizes(8192, host.shape[1]))
         rx.close()
         want = M.expected(host[0], cands)
         assert (want[0]["bit_frames"], want[0]["rate_score"], want[0]["clock_idx"]) == (winner, 32767, 0)
@@ -201,7 +147,7 @@ def test_max_score_refuses_noise_bursts_and_decodes_the_message_behind_them(torc
     rx = LiveReceiver(host.shape[0], "auto", max_score=limit, max_burst_len=None, progressive=True, device=DEV)
     assert rx.max_score == limit
     taps = []
-    got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(8192, host.shape[1], None),
+    got = drive(rx, torch.from_numpy(host).to(DEV), push_sizes(8192, host.shape[1]),
                 each=lambda out: taps.append((out.n_closed.cpu().numpy().copy(), out.tap.len.cpu().numpy().copy())))
     rx.close()
     for c in range(host.shape[0]):
@@ -228,8 +174,8 @@ def test_a_short_burst_between_messages_reports_no_rate(torch_cuda):
     first = np.concatenate([first, np.zeros((n, 2 * BLOCK), np.int16), np.full((n, BLOCK), 30000, np.int16)], axis=1)
     second = M.stack([M.rated_capture(rng, sent[c][1:]) for c in range(n)])
     rx = LiveReceiver(n, "auto", max_burst_len=None, device=DEV)
-    got = drive(rx, torch.from_numpy(first).to(DEV), sizes_for(8192, first.shape[1], None))
-    more = drive(rx, torch.from_numpy(second).to(DEV), sizes_for(8192, second.shape[1], None))
+    got = drive(rx, torch.from_numpy(first).to(DEV), push_sizes(8192, first.shape[1]))
+    more = drive(rx, torch.from_numpy(second).to(DEV), push_sizes(8192, second.shape[1]))
     rx.close()
     for c in range(n):
         assert same(got[c], M.expected(first[c])) and same(more[c], M.expected(second[c])), c
@@ -337,7 +283,8 @@ def test_a_threshold_pair_per_channel(torch_cuda):
     pairs = [M.HALF_PAIRS[s != 1.0] for s in M.HALF_SCALE]
     rx = LiveReceiver(6, "auto", [p[0] for p in pairs], [p[1] for p in pairs], max_burst_len=None, device=DEV)
     assert rx.amp_start_threshold is None and list(rx.channel_amp_end) == [p[1] for p in pairs]
-    got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for("random", host.shape[1], np.random.default_rng(9)))
+    got = drive(rx, torch.from_numpy(host).to(DEV),
+                push_sizes("random", host.shape[1], np.random.default_rng(9), STEPS))
     rx.close()
     check_rate_case(got, sent, [M.expected(cap, None, None, *pairs[c]) for c, cap in enumerate(host)])
     # at the full-scale pair the half-scale channels would not even open a burst
@@ -355,7 +302,7 @@ def test_progressive_tap_arrays_equal_the_fixed_progressive_receivers(torch_cuda
     host = M.stack([M.rated_capture(rng, [(r, bytes(rng.integers(0, 256, 16, dtype=np.uint8))) for _ in range(2)])
                     for _ in range(n)])
     d = torch.from_numpy(host).to(DEV)
-    sizes = sizes_for("random", host.shape[1], rng)
+    sizes = push_sizes("random", host.shape[1], rng, STEPS)
     taps = {}
     for kind, bf, kw in (("fixed", r, {}), ("auto", "auto", dict(candidates=[r]))):
         rx = LiveReceiver(n, bf, max_burst_len=None, max_payload_len=0, progressive=True, device=DEV, **kw)
@@ -388,7 +335,7 @@ def test_progressive_assembler_events_and_segments_with_all_candidates(torch_cud
     out = rx.alloc_result()
     d = torch.from_numpy(host).to(DEV)
     whole, whole_s, rated, p = [], [], [], 0
-    for t in sizes_for(8192, host.shape[1], None) + [0]:
+    for t in push_sizes(8192, host.shape[1]) + [0]:
         res = rx.push(d[:, p: p + t], out=out, flush=t == 0, events=ev, segments=sg)
         p += t
         assert res.events.bursts() == res.bursts()

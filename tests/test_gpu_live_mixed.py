@@ -11,15 +11,12 @@ import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, synth
 from afskmodem_amd.live import LiveReceiver, LiveTransmitter
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import FIELDS, push_sizes, random_payload
 from tests.live_tx_model import LiveTxModel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
-
-
-def random_payload(rng, lo, hi):
-    return bytes(rng.integers(0, 256, int(rng.integers(lo, hi + 1)), dtype=np.uint8))
+STEPS = [0, 1, 5, 2047, 2048, 2049, 4000, 8192]              # what a "ragged" chunking draws its push sizes from
 
 
 class MixedTxModel:
@@ -135,18 +132,6 @@ def collect(res, got, rows=None):
             got[c].append(row)
 
 
-def sizes_for(kind, total, rng):
-    if kind == "ragged":
-        out, left = [], total
-        while left > 0:
-            t = min(int(rng.choice([0, 1, 5, 2047, 2048, 2049, 4000, 8192])), left)
-            out.append(t)
-            left -= t
-        return out
-    step = int(kind)
-    return [min(step, total - p) for p in range(0, total, step)]
-
-
 RX_RATES = (160, 80, 40, 20)          # 300 / 600 / 1200 / 2400 baud
 
 
@@ -157,7 +142,7 @@ def test_mixed_receiver_equals_one_rate_receivers(torch_cuda, kind):
     rng = np.random.default_rng(7)
     rates = [RX_RATES[i] for i in rng.permutation(np.arange(n) % 4)]
     data, bursts = interleaved_captures(n, rates, total, seed=21)
-    sizes = sizes_for(kind, total, rng)
+    sizes = push_sizes(kind, total, rng, STEPS)
     rx = LiveReceiver(n, rates, max_chunk_len=T, device=DEV)
     assert rx.bit_frames is None and rx.channel_bit_frames.tolist() == rates
     groups = {bf: [c for c in range(n) if rates[c] == bf] for bf in RX_RATES}

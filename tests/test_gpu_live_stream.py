@@ -10,54 +10,12 @@ from afskmodem_amd import _native
 from afskmodem_amd.live import LiveReceiver, LiveTransmitter
 from oracle import afsk_oracle as O
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import BLOCK, FIELDS, capture_of, collect, drive, noisy, push_sizes, same
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BLOCK = 2048
-FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
+STEPS = [1, 7, 2047, 2048, 2049, 5000, 8192]                # what a "random" chunking draws its push sizes from
 RX_BFS = tuple(bf for bf in range(4, 2048, 4) if 48000 % bf == 0)        # 36 rates: 12000 ... 24 baud
-
-
-def collect(res, got, corrected=False):
-    """Append one push's bursts to got[c] as dicts (every field, the row up to nbytes)."""
-    nc = res.n_closed.cpu().numpy()
-    if not nc.any():
-        return
-    bs, bl, fl = (t.cpu().numpy() for t in (res.burst_start, res.burst_len, res.flags))
-    d = res.demod.cpu()
-    cor = res.demod.corrected.cpu().numpy() if corrected else None
-    s = res.slots
-    for c in np.nonzero(nc)[0].tolist():
-        for k in range(int(nc[c])):
-            j = c * s + k
-            row = dict(start=int(bs[c, k]), len=int(bl[c, k]), flags=int(fl[c, k]),
-                       bytes=d.bytes[j, : min(int(d.nbytes[j]), d.bytes.shape[1])].tobytes())
-            row.update({f: int(getattr(d, f)[j]) for f in FIELDS})
-            if corrected:
-                row["corrected"] = int(cor[j])
-            got[c].append(row)
-
-
-def sizes_for(T, total, rng):
-    if T == "random":
-        out = []
-        while sum(out) < total:
-            out.append(min(int(rng.choice([1, 7, 2047, 2048, 2049, 5000, 8192])), total - sum(out)))
-        return out
-    return [T] * (total // T) + ([total % T] if total % T else [])
-
-
-def drive(rx, d, sizes, corrected=False, flush=True):
-    got = [[] for _ in range(rx.n_channels)]
-    out = rx.alloc_result(diagnostics=corrected)
-    p = 0
-    for t in sizes:
-        collect(rx.push(d[:, p: p + t], out=out), got, corrected)
-        p += t
-    assert p == d.shape[1]
-    if flush:
-        collect(rx.flush(out=out), got, corrected)
-    return got
 
 
 def expected(cap, bf, a_start, a_end, maxp):
@@ -71,30 +29,6 @@ def expected(cap, bf, a_start, a_end, maxp):
         row["bytes"] = r["bytes"][0, : min(row["nbytes"], maxp)].tobytes()
         out.append(row)
     return out
-
-
-def same(got, want):
-    """The streaming receiver's bursts of one channel against the oracle's (every field the oracle has)."""
-    return len(got) == len(want) and all({k: g[k] for k in w} == w for g, w in zip(got, want))
-
-
-def noisy(rng, x, sigma):
-    return np.clip(x + rng.normal(0, sigma, x.size), -32768, 32767).astype(np.int16)
-
-
-def capture_of(rng, bf, payloads, gap=3 * BLOCK, sigma=2000.0, training=0.5):
-    """Messages with quiet gaps, in noise.  A message starts a random number of samples into a block, fewer than
-    the clock search covers (4096 - 2 bf offsets) from 1000 samples per symbol on: the gate cuts bursts at block
-    boundaries, so a slower message starting later in its block is not decodable, by the reference either."""
-    tr = afskmodem.Transmitter(48000 // bf, training)
-    lim = BLOCK if 4096 - 2 * bf >= BLOCK else 4096 - 2 * bf - 8
-    parts, n = [], 0
-    for p in payloads:
-        pad = (-n) % BLOCK + gap + int(rng.integers(0, lim))
-        parts += [np.zeros(pad, np.int16), tr.wav_samples(p)]
-        n += pad + parts[-1].size
-    parts.append(np.zeros(gap + int(rng.integers(0, BLOCK)), np.int16))
-    return noisy(rng, np.concatenate(parts), sigma)
 
 
 @pytest.mark.parametrize("T", [1, 7, 2047, 2048, 2049, 8192, 48000, "random"])
@@ -114,7 +48,7 @@ def test_long_payloads_beyond_the_stored_default(torch_cuda, T):
         for i, c in enumerate(caps):
             host[i, : c.size] = c
         rx = LiveReceiver(2, bf, max_burst_len=None, max_payload_len=256, max_chunk_len=48000, device=DEV)
-        got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(T, total, rng))
+        got = drive(rx, torch.from_numpy(host).to(DEV), push_sizes(T, total, rng, STEPS))
         for i in range(2):
             want = expected(host[i], bf, 18000, 14000, 256)
             assert [g["start"] for g in got[i]] == [w["start"] for w in want], (bf, i)
@@ -152,7 +86,7 @@ def test_every_rate_against_the_stored_receiver_and_the_oracle(torch_cuda, bf):
     host = np.zeros((n, total), np.int16)
     for i, c in enumerate(caps):
         host[i, : c.size] = c
-    got = stored_vs_streaming(torch, host, bf, sizes_for("random", total, rng))
+    got = stored_vs_streaming(torch, host, bf, push_sizes("random", total, rng, STEPS))
     for i in range(n):
         want = expected(host[i], bf, 18000, 14000, 4096)
         assert same(got[i], want), i
@@ -169,7 +103,7 @@ def test_mixed_receiver_all_rates_interleaved(torch_cuda):
     host = np.zeros((len(bfs), total), np.int16)
     for i, c in enumerate(caps):
         host[i, : c.size] = c
-    got = stored_vs_streaming(torch, host, bfs, sizes_for(8192, total, rng))
+    got = stored_vs_streaming(torch, host, bfs, push_sizes(8192, total, rng, STEPS))
     for i, bf in enumerate(bfs):
         want = expected(host[i], bf, 18000, 14000, 4096)
         assert same(got[i], want), (i, bf)
@@ -216,7 +150,7 @@ def test_traps_boundary_short_no_terminator_partial_codewords(torch_cuda):
     rows.append(one)
     bfs.append(40)
     host = np.stack(rows)
-    got = stored_vs_streaming(torch, host, bfs, sizes_for(BLOCK, total, rng))
+    got = stored_vs_streaming(torch, host, bfs, push_sizes(BLOCK, total, rng, STEPS))
     statuses = set()
     for i, bf in enumerate(bfs):
         want = expected(host[i], bf, 18000, 14000, 4096)
@@ -248,11 +182,11 @@ def test_many_bursts_in_one_push_and_one_burst_over_hundreds_of_pushes(torch_cud
     w = afskmodem.Transmitter(1200, 0.5).wav_samples(bytes(rng.integers(0, 256, 256, dtype=np.uint8)))
     host[2, 2 * BLOCK: 2 * BLOCK + w.size] = w
     host[3] = noisy(rng, np.zeros(host.shape[1]), 12000.0)
-    got = stored_vs_streaming(torch, host, 40, sizes_for(T, host.shape[1], rng))
+    got = stored_vs_streaming(torch, host, 40, push_sizes(T, host.shape[1], rng, STEPS))
     for i in range(n):
         want = expected(host[i], 40, 18000, 14000, 4096)
         assert same(got[i], want), i
-    small = stored_vs_streaming(torch, host[:, :300 * BLOCK], 40, sizes_for(511, 300 * BLOCK, rng))
+    small = stored_vs_streaming(torch, host[:, :300 * BLOCK], 40, push_sizes(511, 300 * BLOCK, rng, STEPS))
     assert len(small[2]) == 1 and small[2][0]["len"] > 300 * 511 and small[2][0]["status"] == _native.ST_OK
 
 
@@ -264,7 +198,7 @@ def test_payload_rows_truncate_at_max_payload_len(torch_cuda):
     host = np.stack([cap, cap])
     for maxp in (0, 1, 13, 39, 40):
         rx = LiveReceiver(2, 40, max_burst_len=None, max_payload_len=maxp, device=DEV)
-        got = drive(rx, torch.from_numpy(host).to(DEV), sizes_for(8192, cap.size, rng))
+        got = drive(rx, torch.from_numpy(host).to(DEV), push_sizes(8192, cap.size, rng, STEPS))
         rx.close()
         for g in got:
             assert g[0]["nbytes"] == 40 and g[0]["bytes"] == data[:maxp], maxp

@@ -13,30 +13,13 @@ from afskmodem_amd import _native
 from afskmodem_amd.live import LiveReceiver, LiveTransmitter
 from oracle import afsk_oracle as O
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import BLOCK, capture_of, noisy, push_sizes
 from tests.live_tap_model import TapChannelModel, tap_cap
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BLOCK = 2048
+STEPS = [1, 7, 2047, 2048, 2049, 5000, 8192]                # what a "random" chunking draws its push sizes from
 GUARD = 0xA5
-
-
-def noisy(rng, x, sigma):
-    return np.clip(x + rng.normal(0, sigma, x.size), -32768, 32767).astype(np.int16)
-
-
-def capture_of(rng, bf, payloads, gap=3 * BLOCK, sigma=2000.0, training=0.5):
-    """Messages with quiet gaps, in noise; a message starts a random number of samples into a block (fewer than the
-    clock search covers from 1000 samples per symbol on)."""
-    tr = afskmodem.Transmitter(48000 // bf, training)
-    lim = BLOCK if 4096 - 2 * bf >= BLOCK else 4096 - 2 * bf - 8
-    parts, n = [], 0
-    for p in payloads:
-        pad = (-n) % BLOCK + gap + int(rng.integers(0, lim))
-        parts += [np.zeros(pad, np.int16), tr.wav_samples(p)]
-        n += pad + parts[-1].size
-    parts.append(np.zeros(gap + int(rng.integers(0, BLOCK)), np.int16))
-    return noisy(rng, np.concatenate(parts), sigma)
 
 
 def stack(caps):
@@ -44,15 +27,6 @@ def stack(caps):
     for i, c in enumerate(caps):
         host[i, : c.size] = c
     return host
-
-
-def sizes_for(T, total, rng):
-    if T == "random":
-        out = []
-        while sum(out) < total:
-            out.append(min(int(rng.choice([1, 7, 2047, 2048, 2049, 5000, 8192])), total - sum(out)))
-        return out
-    return [T] * (total // T) + ([total % T] if total % T else [])
 
 
 def expected(cap, bf, a_start=18000, a_end=14000):
@@ -209,7 +183,7 @@ def test_reassembly_and_timeliness(torch_cuda, T, maxp):
     for name in names:
         bf, host, want, lines = case(name)
         rng = np.random.default_rng(11)
-        sizes = sizes_for(T, host.shape[1], rng)
+        sizes = push_sizes(T, host.shape[1], rng, STEPS)
         events, done, maxn = run(torch_cuda, host, bf, sizes, maxp, lines=lines, every_push=T not in (1, 7))
         check_events(events, done, want)
         if name == "6000_long":
@@ -227,7 +201,7 @@ def test_several_bursts_of_one_channel_in_one_push(torch_cuda):
     pays = [[bytes(rng.integers(0, 256, int(rng.integers(1, 9)), dtype=np.uint8)) for _ in range(14)] for _ in range(3)]
     host = stack([capture_of(rng, 20, p, gap=2 * BLOCK, training=0.1) for p in pays])
     want = [expected(host[c], 20) for c in range(3)]
-    events, done, _ = run(torch_cuda, host, 20, sizes_for(48000, host.shape[1], rng), 0,
+    events, done, _ = run(torch_cuda, host, 20, push_sizes(48000, host.shape[1], rng, STEPS), 0,
                           lines=[timeline(host[c], 20) for c in range(3)])
     check_events(events, done, want)
     for c in range(3):
@@ -254,7 +228,7 @@ def test_bursts_that_decode_nothing(torch_cuda):
     want = [expected(host[c], 40) for c in range(4)]
     assert len(want[0]) >= 15 and all(w[3] == b"" for c in (0, 1, 2) for w in want[c]) and want[1] and want[2]
     for T in (8192, 2049):
-        events, done, maxn = run(torch_cuda, host, 40, sizes_for(T, total, rng), 0,
+        events, done, maxn = run(torch_cuda, host, 40, push_sizes(T, total, rng, STEPS), 0,
                                  lines=[timeline(host[c], 40) for c in range(4)])
         check_events(events, done, want)
         assert (maxn[:3] == 0).all()
@@ -272,7 +246,7 @@ def test_mixed_rates_and_a_threshold_pair_per_channel(torch_cuda):
              for _ in range(2)] for bf in bfs]
     caps = [capture_of(rng, bf, p, sigma=1500.0, training=max(0.05, 3.0 * bf / 48000)) for bf, p in zip(bfs, pays)]
     host = stack(caps)
-    sizes = sizes_for(8192, host.shape[1], rng)
+    sizes = push_sizes(8192, host.shape[1], rng, STEPS)
     want = [expected(host[c], bfs[c], starts[c], ends[c]) for c in range(len(bfs))]
     lines = [timeline(host[c], bfs[c], starts[c], ends[c]) for c in range(len(bfs))]
     events, done, _ = run(torch_cuda, host, bfs, sizes, 4, a=(starts, ends), lines=lines)
@@ -292,7 +266,7 @@ def test_reset_with_a_mask_in_mid_burst(torch_cuda):
     host = np.zeros((n, 4 * BLOCK + w.size + 4 * BLOCK), np.int16)
     host[:, 4 * BLOCK: 4 * BLOCK + w.size] = w
     T = 4096
-    sizes = sizes_for(T, host.shape[1], rng)
+    sizes = push_sizes(T, host.shape[1], rng, STEPS)
     at = (4 * BLOCK + w.size // 2) // T                         # a push in mid-payload
     mask = np.array([1, 0, 1, 0, 0, 1], np.uint8)
     events, done, _ = run(torch_cuda, host, 40, sizes, 0, reset_at=(at, mask))

@@ -4,7 +4,6 @@ model (tests/live_tx_model.py) puts them -- the reference's own frame digests, s
 column windows, reset, graph replay, and a loopback through ``LiveReceiver``.  Expected values never come from the
 live path itself."""
 import ctypes as C
-import hashlib
 
 import numpy as np
 import pytest
@@ -12,15 +11,13 @@ import pytest
 import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, batch, synth
 from afskmodem_amd.live import LiveReceiver, LiveTransmitter
+from tests.golden_inputs import sha_i16
 from tests.gpu_common import torch_cuda  # noqa: F401  (fixture)
+from tests.live_drive import random_payload
 from tests.live_tx_model import LiveTxModel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def sha_i16(a) -> str:
-    return hashlib.sha256(np.asarray(a, dtype="<i2").tobytes()).hexdigest()
 
 
 def sizes_for(kind, total, rng):
@@ -99,10 +96,6 @@ def test_reference_digests_in_every_chunking(golden, torch_cuda, kind):
             assert not host[c, :lead].any() and not host[c, lead + n_wav:].any(), (baud, tt, p, kind)
         torch.cuda.synchronize()
         tx.close()
-
-
-def random_payload(rng, lo, hi):
-    return bytes(rng.integers(0, 256, int(rng.integers(lo, hi + 1)), dtype=np.uint8))
 
 
 def test_seeded_queueing_against_the_model(torch_cuda):

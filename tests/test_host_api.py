@@ -13,12 +13,9 @@ import pytest
 import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, batch, synth
 from oracle import afsk_oracle as O
+from tests.golden_inputs import sha_i16
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def sha_i16(a):
-    return hashlib.sha256(np.asarray(a, dtype="<i2").tobytes()).hexdigest()
 
 
 def test_templates_match_reference(golden):

@@ -1,21 +1,19 @@
 """The auto-rate receiver's C entries through the stub HIP runtime (no GPU): the host code of afsk_gate.hip built against
-tests/helpers (build_stub_detect_lib.sh: a launch records the kernel's name and a copy of its first argument instead
-of running).  The return codes of afsk_live_create_stream_auto and afsk_live_push_auto, which push entry serves which
-receiver, one launch per push and which cell of the push table it is, the candidate list passed BY VALUE, and the
-fixed-rate receivers still launching the cells they did."""
+tests/helpers (build_stub_live_lib.sh, loaded through tests/stub_lib.py: a launch records the kernel's name and, when
+asked, a copy of its first argument instead of running).  The return codes of afsk_live_create_stream_auto and
+afsk_live_push_auto, which push entry serves which receiver, one launch per push and which cell of the push table it
+is, the candidate list passed BY VALUE, and the fixed-rate receivers still launching the cells they did."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from afskmodem_amd import _native, batch
+from tests import stub_lib
 from tests.live_push_cells import push_cell
+from tests.stub_lib import i32, last_error, last_kernel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-I32P = C.POINTER(C.c_int32)
 N, T, SLOTS, TAP_CAP = 6, 6144, 2, 800
 # what an auto cell's argument holds at least: the streaming sink's argument (232 bytes; with the tap's 280), then two
 # pointers, max_score, n_cand and 36 candidates
@@ -31,74 +29,14 @@ def auto_cell(mangled):
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("stub_auto") / "libafsk_stub_auto.so")
-    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "helpers", "build_stub_detect_lib.sh"), path])
-    lib = C.CDLL(path)
-    for table in (_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
-                  _native.LIVE_TAP_SIGNATURES, _native.LIVE_AUTO_SIGNATURES,
-                  {"afsk_live_push_ragged": _native.LIVE_RAGGED_SIGNATURES["afsk_live_push_ragged"]}):
-        for name, (res, args) in table.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    lib.afsk_last_error.argtypes = [C.c_char_p, C.c_int]
-    lib.afsk_stub_last_kernel.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint)]
-    lib.afsk_stub_last_arg0.argtypes = [C.c_char_p, C.c_int]
-    lib.afsk_stub_capture_arg0.argtypes = [C.c_int]
-    return lib
+    return stub_lib.load(tmp_path_factory, "afsk_stub_auto",
+                         [_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
+                          _native.LIVE_TAP_SIGNATURES, _native.LIVE_AUTO_SIGNATURES, _native.LIVE_RAGGED_SIGNATURES])
 
 
-def i32(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
-
-
-def last_kernel(lib):
-    buf, grid = C.create_string_buffer(256), C.c_uint()
-    n = lib.afsk_stub_last_kernel(buf, 256, C.byref(grid))
-    return n, buf.value.decode(), grid.value
-
-
-def last_error(lib):
-    buf = C.create_string_buffer(1024)
-    lib.afsk_last_error(buf, 1024)
-    return buf.value.decode()
-
-
-class Buffers:
-    """Host buffers standing in for a push's device arrays."""
-
-    def __init__(self, n=N, width=T, slots=SLOTS):
-        self.width = width
-        self.chunk = np.zeros((n, width), np.int16)
-        self.lens = np.full(n, width // 2, np.int32)
-        self.mask = np.zeros(n, np.uint8)
-        self.n_closed = np.zeros(n, np.int32)
-        self.start = np.zeros((n, slots), np.int64)
-        self.slot = [np.zeros(n * slots, np.int32) for _ in range(8)]    # len, flags, nbytes ... corrected
-        self.tap = (np.zeros((n, TAP_CAP), np.uint8), np.zeros(n, np.int32), np.zeros((n, slots), np.int32),
-                    np.zeros(n, np.int64), np.zeros(n, np.int32))
-        self.rate = (np.zeros(n * slots, np.int32), np.zeros(n * slots, np.int32))
-
-    def outs(self, margins=None):
-        p = lambda a: a.ctypes.data  # noqa: E731
-        ln, flags, nbytes, nbits, ci, term, status, corrected = self.slot
-        return [p(self.n_closed), p(self.start), p(ln), p(flags), None, 0, p(nbytes), p(nbits), p(ci), p(term),
-                p(status), p(corrected), margins, 0]
-
-    def plain(self, h, flush=0):
-        return [h, self.chunk.ctypes.data, self.width, self.width, flush] + self.outs() + [None]
-
-    def taps(self, missing=None):
-        return [None if i == missing else a.ctypes.data for i, a in enumerate(self.tap)]
-
-    def ragged(self, h, chunk_len=None, lens=False, flush=0, mask=False, taps=False, missing=None, margins=None):
-        tap = self.taps(missing) if taps else [None] * 5
-        return [h, self.chunk.ctypes.data, self.width, self.width if chunk_len is None else chunk_len,
-                self.lens.ctypes.data if lens else None, flush, self.mask.ctypes.data if mask else None] \
-            + self.outs(margins) + tap + [None]
-
-    def auto(self, h, rates=(True, True), **kw):
-        return self.ragged(h, **kw)[:-1] + [a.ctypes.data if r else None for a, r in zip(self.rate, rates)] + [None]
+def Buffers():
+    """This module's sizes; a ragged or auto argument list passes neither lens nor mask unless told to."""
+    return stub_lib.Buffers(N, T, SLOTS, TAP_CAP)
 
 
 def create_auto(lib, cands=(40, 160, 8), max_score=-1, per_channel=False, tap=0, maxp=64):

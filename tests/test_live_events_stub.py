@@ -1,66 +1,37 @@
 """The packed event list's C entries through the stub HIP runtime (no GPU): the host code of afsk_gate.hip built
-against tests/helpers, where "device" memory is host memory and a launch records the kernel's name instead of running
-it.  On the library of build_stub_live_lib.sh (it keeps the last launch and the number of launches): every argument
-check of afsk_live_events_layout and afsk_live_pack, and that a refused call launches nothing.  On the library of
-build_stub_ragged_lib.sh (the same host code of afsk_gate.hip, with a log of every launch): that a pack launches exactly
-its three kernels, in order, by mangled name, behind the push entry's own launches, and that the push entry alone launches
-what it launched before."""
+against tests/helpers (build_stub_live_lib.sh, loaded through tests/stub_lib.py), where "device" memory is host memory
+and a launch records the kernel's name instead of running it.  On one copy of the library (``stub``: its last launch
+and its number of launches): every argument check of afsk_live_events_layout and afsk_live_pack, and that a refused
+call launches nothing.  On another copy (``logged``: its log of every launch): that a pack launches exactly its three
+kernels, in order, by mangled name, behind the push entry's own launches, and that the push entry alone launches what
+it launched before."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests import stub_lib
 from tests.live_push_cells import push_cell
+from tests.stub_lib import last_kernel, launches
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, T, SLOTS, STRIDE = 600, 6144, 2, 24
 PACK_KERNELS = ["_ZN4afsk22live_pack_total_kernelINS_14LiveEventsArgsEEEvT_",
                 "_ZN4afsk21live_pack_scan_kernelENS_16LivePackScanArgsE",
                 "_ZN4afsk24live_events_write_kernelENS_14LiveEventsArgsE"]
 BAD = _native.E_INVALID_ARG
-
-
-def build(tmp_path_factory, script, name):
-    path = str(tmp_path_factory.mktemp(name) / f"lib{name}.so")
-    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "helpers", script), path])
-    lib = C.CDLL(path)
-    for table in (_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
-                  _native.LIVE_TAP_SIGNATURES, _native.LIVE_RAGGED_SIGNATURES, _native.LIVE_EVENT_SIGNATURES):
-        for fn_name, (res, args) in table.items():
-            if fn_name == "afsk_live_tx_pull_ragged" and not hasattr(lib, fn_name):
-                continue                                           # (the transmitter is not part of the live library)
-            fn = getattr(lib, fn_name)
-            fn.restype, fn.argtypes = res, args
-    return lib
+TABLES = (_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
+          _native.LIVE_TAP_SIGNATURES, _native.LIVE_RAGGED_SIGNATURES, _native.LIVE_EVENT_SIGNATURES)
 
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    lib = build(tmp_path_factory, "build_stub_live_lib.sh", "afsk_stub_events")
-    lib.afsk_stub_last_kernel.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint)]
-    return lib
+    return stub_lib.load(tmp_path_factory, "afsk_stub_events", TABLES)
 
 
 @pytest.fixture(scope="module")
 def logged(tmp_path_factory):
-    lib = build(tmp_path_factory, "build_stub_ragged_lib.sh", "afsk_stub_events_log")
-    lib.afsk_stub_kernel_log.argtypes = [C.c_char_p, C.c_int, C.c_int]
-    return lib
-
-
-def last_kernel(lib):
-    buf, grid = C.create_string_buffer(256), C.c_uint()
-    n = lib.afsk_stub_last_kernel(buf, 256, C.byref(grid))
-    return n, buf.value.decode(), grid.value
-
-
-def launches(lib):
-    buf = C.create_string_buffer(1 << 14)
-    assert lib.afsk_stub_kernel_log(buf, len(buf), 1) <= len(buf)
-    return buf.value.decode().split()
+    return stub_lib.load(tmp_path_factory, "afsk_stub_events_log", TABLES)
 
 
 class Push:

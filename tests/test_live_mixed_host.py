@@ -10,15 +10,10 @@ import pytest
 
 import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, live
+from tests.stub_lib import arr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIXED_ENTRIES = ("afsk_live_create_mixed", "afsk_live_tx_create_mixed", "afsk_live_tx_state_bytes_mixed")
-I32P = C.POINTER(C.c_int32)
-
-
-def arr(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
 
 
 def test_header_declares_mixed_entries_in_their_own_table():

@@ -1,95 +1,33 @@
 """The ragged push and pull (afsk_live_push_ragged, afsk_live_tx_pull_ragged) through the stub HIP runtime (no GPU):
-the host code of afsk_gate.hip and afsk_synth.hip built against tests/helpers (build_stub_ragged_lib.sh), where
-"device" memory is host memory and a launch records the kernel's name instead of running it.  Every launch of an entry
-is logged in order, so a test sees which kernels a ragged call launches and how many -- for each receiver and
-transmitter kind -- that the plain calls still launch the plain kernels, and every argument check."""
+the host code of afsk_gate.hip and afsk_synth.hip built against tests/helpers (build_stub_live_lib.sh, loaded through
+tests/stub_lib.py), where "device" memory is host memory and a launch records the kernel's name instead of running it.
+Every launch of an entry is logged in order, so a test sees which kernels a ragged call launches and how many -- for
+each receiver and transmitter kind -- that the plain calls still launch the plain kernels, and every argument check."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests import stub_lib
 from tests.live_push_cells import CELLS, push_cell
+from tests.stub_lib import i32
+from tests.stub_lib import launches_decoded as launches
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-I32P = C.POINTER(C.c_int32)
 N, T, SLOTS, TAP_CAP = 6, 6144, 2, 200
 
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("stub_ragged") / "libafsk_stub_ragged.so")
-    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "helpers", "build_stub_ragged_lib.sh"), path])
-    lib = C.CDLL(path)
-    for table in (_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
-                  _native.LIVE_TAP_SIGNATURES, _native.LIVE_MIXED_SIGNATURES, _native.LIVE_TX_SIGNATURES,
-                  _native.LIVE_RAGGED_SIGNATURES):
-        for name, (res, args) in table.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    lib.afsk_stub_kernel_log.argtypes = [C.c_char_p, C.c_int, C.c_int]
-    return lib
+    return stub_lib.load(tmp_path_factory, "afsk_stub_ragged",
+                         [_native.LIVE_SIGNATURES, _native.LIVE_STREAM_SIGNATURES, _native.LIVE_THRESHOLD_SIGNATURES,
+                          _native.LIVE_TAP_SIGNATURES, _native.LIVE_MIXED_SIGNATURES, _native.LIVE_TX_SIGNATURES,
+                          _native.LIVE_RAGGED_SIGNATURES])
 
 
-def launches(lib):
-    """The launches since the last call, in order: the cell (sink, per_channel, ragged) of a live_push_kernel
-    instantiation, any other kernel's plain name (with the bool of a one-parameter template, e.g.
-    live_tx_tile_kernel<0>), or "demod" for a call of a demod launcher."""
-    buf = C.create_string_buffer(1 << 14)
-    assert lib.afsk_stub_kernel_log(buf, len(buf), 1) <= len(buf)
-    out = []
-    for line in buf.value.decode().split():
-        m = re.match(r"_ZN4afsk(\d+)", line)
-        if push_cell(line):
-            out.append(push_cell(line))
-            continue
-        if not m:
-            out.append(line)
-            continue
-        at = m.end()
-        name = line[at: at + int(m.group(1))]
-        t = re.match(r"ILb([01])E", line[at + len(name):])
-        out.append(name + (f"<{t.group(1)}>" if t else ""))
-    return out
-
-
-def i32(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
-
-
-class Buffers:
-    """Host buffers standing in for a push's device arrays."""
-
-    def __init__(self, n=N, width=T, slots=SLOTS):
-        self.width = width
-        self.chunk = np.zeros((n, width), np.int16)
-        self.lens = np.full(n, width // 2, np.int32)
-        self.mask = np.zeros(n, np.uint8)
-        self.n_closed = np.zeros(n, np.int32)
-        self.start = np.zeros((n, slots), np.int64)
-        self.slot = [np.zeros(n * slots, np.int32) for _ in range(8)]    # len, flags, nbytes ... corrected
-        self.tap = (np.zeros((n, TAP_CAP), np.uint8), np.zeros(n, np.int32), np.zeros((n, slots), np.int32),
-                    np.zeros(n, np.int64), np.zeros(n, np.int32))
-
-    def outs(self, margins=None):
-        p = lambda a: a.ctypes.data  # noqa: E731
-        ln, flags, nbytes, nbits, ci, term, status, corrected = self.slot
-        return [p(self.n_closed), p(self.start), p(ln), p(flags), None, 0, p(nbytes), p(nbits), p(ci), p(term),
-                p(status), p(corrected), margins, 0]
-
-    def plain(self, h, flush=0):
-        return [h, self.chunk.ctypes.data, self.width, self.width, flush] + self.outs() + [None]
-
-    def ragged(self, h, chunk_len=None, lens=True, flush=0, mask=True, taps=False, missing=None, margins=None,
-               stride=None):
-        tap = [a.ctypes.data if taps and i != missing else None for i, a in enumerate(self.tap)]
-        return [h, self.chunk.ctypes.data, self.width if stride is None else stride,
-                self.width if chunk_len is None else chunk_len, self.lens.ctypes.data if lens else None, flush,
-                self.mask.ctypes.data if mask else None] + self.outs(margins) + tap + [None]
+def Buffers():
+    """This module's sizes; a ragged argument list passes the lens and the mask unless told otherwise."""
+    return stub_lib.Buffers(N, T, SLOTS, TAP_CAP, given=True)
 
 
 def create(lib, kind):

@@ -1,19 +1,22 @@
 """The packed segment list's C entries through the stub HIP runtime (no GPU): the host code of afsk_gate.hip built
-against tests/helpers, where "device" memory is host memory and a launch records the kernel's name instead of running
-it.  On the library of build_stub_live_lib.sh (it keeps the last launch and the number of launches): every argument
-check of afsk_live_segments_layout and afsk_live_pack_tap, and that a refused call launches nothing.  On the library of
-build_stub_ragged_lib.sh (the same host code, with a log of every launch): that a pack launches exactly its three
-kernels, in order, by mangled name, behind the tapped push's own launches, and that the push alone launches what it
-launched before."""
+against tests/helpers (build_stub_live_lib.sh, loaded through tests/stub_lib.py), where "device" memory is host memory
+and a launch records the kernel's name instead of running it.  On one copy of the library (``stub``: its last launch
+and its number of launches): every argument check of afsk_live_segments_layout and afsk_live_pack_tap, and that a
+refused call launches nothing.  On another copy (``logged``: its log of every launch): that a pack launches exactly its
+three kernels, in order, by mangled name, behind the tapped push's own launches, and that the push alone launches what
+it launched before."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from afskmodem_amd import _native
+from tests import stub_lib
 from tests.live_push_cells import push_cell
+from tests.stub_lib import last_kernel, launches
 from tests.test_live_events_stub import PACK_KERNELS as EVENT_KERNELS
-from tests.test_live_events_stub import Push, build, last_kernel, launches
+from tests.test_live_events_stub import TABLES as EVENT_TABLES
+from tests.test_live_events_stub import Push
 
 N, T, SLOTS, STRIDE, CAP = 600, 6144, 2, 24, 19
 PACK_KERNELS = ["_ZN4afsk22live_pack_total_kernelINS_16LiveSegmentsArgsEEEvT_",
@@ -22,25 +25,17 @@ PACK_KERNELS = ["_ZN4afsk22live_pack_total_kernelINS_16LiveSegmentsArgsEEEvT_",
 BAD = _native.E_INVALID_ARG
 
 
-def bind(lib):
-    for name, (res, args) in _native.LIVE_SEGMENT_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
+TABLES = EVENT_TABLES + (_native.LIVE_SEGMENT_SIGNATURES,)
 
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    lib = bind(build(tmp_path_factory, "build_stub_live_lib.sh", "afsk_stub_segments"))
-    lib.afsk_stub_last_kernel.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint)]
-    return lib
+    return stub_lib.load(tmp_path_factory, "afsk_stub_segments", TABLES)
 
 
 @pytest.fixture(scope="module")
 def logged(tmp_path_factory):
-    lib = bind(build(tmp_path_factory, "build_stub_ragged_lib.sh", "afsk_stub_segments_log"))
-    lib.afsk_stub_kernel_log.argtypes = [C.c_char_p, C.c_int, C.c_int]
-    return lib
+    return stub_lib.load(tmp_path_factory, "afsk_stub_segments_log", TABLES)
 
 
 class TapPush(Push):

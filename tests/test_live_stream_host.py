@@ -12,17 +12,12 @@ import pytest
 from afskmodem_amd import _native, live
 from oracle import afsk_oracle as O
 from tests.live_stream_model import BLOCK, SYNC, StreamDemodModel, demod_streaming
+from tests.stub_lib import arr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STREAM_ENTRIES = ("afsk_live_stream_layout", "afsk_live_create_stream")
 RX_BFS = tuple(bf for bf in range(4, 2048, 4) if 48000 % bf == 0)        # 36 rates: 12000 ... 24 baud
-I32P = C.POINTER(C.c_int32)
 FIELDS = ("nbytes", "nbits", "clock_idx", "term_frame", "status")
-
-
-def arr(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
 
 
 def oracle_demod(burst, bf, amp_end=14000, stride=512):

@@ -12,10 +12,10 @@ import pytest
 from afskmodem_amd import _native, batch, live
 from oracle import afsk_oracle as O
 from tests.live_tap_model import BLOCK, TapChannelModel, TapDemodModel, tap_cap
+from tests.stub_lib import arr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAP_ENTRIES = ("afsk_live_tap_layout", "afsk_live_create_stream_tap", "afsk_live_push_tap")
-I32P = C.POINTER(C.c_int32)
 # 6000, 2400, 1200, 300 and 24 baud, with a payload size that keeps the burst at a few hundred blocks
 RATES = ((8, 3000), (20, 2000), (40, 1500), (160, 300), (2000, 12))
 
@@ -229,11 +229,6 @@ def test_library_exports_tap_entries():
     for name in TAP_ENTRIES:
         assert getattr(lib, name) is not None
     assert _native.lib().afsk_version() == 2
-
-
-def arr(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
 
 
 def test_create_and_push_argument_checks_before_any_device():

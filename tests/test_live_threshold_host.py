@@ -13,17 +13,12 @@ import pytest
 
 import afskmodem_amd as afskmodem
 from afskmodem_amd import _native, batch, live
+from tests.stub_lib import arr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THRESHOLD_ENTRIES = ("afsk_live_create_thresholds", "afsk_live_create_stream_thresholds")
-I32P = C.POINTER(C.c_int32)
 STORED = ("afsk_live_create_thresholds", 96000)
 STREAM = ("afsk_live_create_stream_thresholds", 256)
-
-
-def arr(values):
-    a = np.ascontiguousarray(values, np.int32)
-    return a, a.ctypes.data_as(I32P)
 
 
 def create(kind, bf, start, end, cap=None, chunk=8192, n=None):
