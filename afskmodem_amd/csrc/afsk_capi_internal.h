@@ -1,7 +1,10 @@
 // afsk_capi_internal.h -- host-side pieces the C-ABI translation units share (afsk_capi.hip, afsk_split.hip,
 // afsk_live.hip, afsk_live_tx.hip): the library's last-error slot, the exception barrier of the exported entries, the
 // argument checks and output fields every demod entry has in common, and the owner of a handle's device state.  Host
-// code only; not part of the installed interface.
+// code only; not part of the installed interface.  What only afsk_capi.hip's host entries need lives in four headers
+// that file alone includes: afsk_host_pool.h (NUMA probe, I/O pool, parallel copy), afsk_host_staging.h (scratch cache
+// and lease, layout check, two-window loop, window planner, ring session), afsk_host_riff.h (RIFF/WAVE) and
+// afsk_host_plan.h (rate-grouped dispatch); tests/helpers/capi_host_driver.cpp drives them under the sanitizers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +38,12 @@ int no_throw(F&& body) {
     } catch (...) {
         return fail(AFSK_E_HOST, "host-side failure");
     }
+}
+
+// an entry that is nothing but that barrier around its implementation
+template <class... P, class... A>
+int guarded(int (*impl)(P...), A... args) {
+    return no_throw([&] { return impl(args...); });
 }
 
 // The host side's bit_frames rule (a multiple of 4 with 2*bf < AFSK_SYNC_WINDOW) and its error.

@@ -4,7 +4,8 @@
 // the plain CPU suite.  "Device memory" is host memory; every stream is an in-order worker thread, so
 // hipMemcpyAsync really is asynchronous and a staging buffer handed back to the fillers before its copy has
 // run IS a data race the sanitizer sees.  Linked (with -Bsymbolic) into a test-only build of the library
-// together with stub kernel launchers (tools/capi_asan.sh, tests/test_capi_host_logic.py); it is never part of
+// together with stub kernel launchers (tests/test_capi_host_logic.py, tools/capi_asan.sh), or statically into the
+// stand-alone sanitizer program capi_host_driver.cpp (tests/test_capi_host_sanitizers.py); it is never part of
 // libafsk_amd.so and nothing in afskmodem_amd/ can reach it.
 #include <hip/hip_runtime_api.h>
 

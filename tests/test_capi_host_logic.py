@@ -1,5 +1,7 @@
 """CPU tests of the C-ABI's HOST logic that normally needs a GPU to run at all: the staging ring of
-afsk_wav_ingest (pool threads filling, the caller sending, buffers handed back when a copy completes), the
+afsk_wav_ingest and afsk_wav_egress (pool threads filling or writing, the caller copying, buffers handed back when a
+copy completes or the last file piece is written; tests/test_capi_host_sanitizers.py runs the same ring under the
+sanitizers as a stand-alone program), the
 window packing of afsk_wav_upload / afsk_demod_streams_host, scratch leases under concurrent callers, the
 group plan.  afsk_capi.hip is compiled AS IS and linked, for this test only, against a fake HIP runtime
 (tests/helpers/hip_stub_runtime.cpp: device memory = host memory, every stream an in-order worker thread, so
@@ -368,7 +370,10 @@ def test_group_plan_takes_the_longest_streams_first_when_lengths_are_ragged(stub
 def test_egress_writes_what_the_stdlib_writer_writes(stub, tmp_path):
     """afsk_wav_egress: every file byte for byte what `wave` writes for 1 channel / 16 bit / 48000 Hz
     (SoundOutput.writeToFile, afskmodem.py:256-263) -- streams smaller and larger than a staging window, empty
-    streams, gaps between streams, an existing longer file replaced, an unwritable path reported per file."""
+    streams, gaps between streams, an existing longer file replaced, an unwritable path reported per file.
+    Egress shares the module's staging ring of 3 x 4 MiB with the ingest: the first three windows hold at most
+    1 + 2 + 4 MiB (7.3 MB) of the 11.7 MB written here, so the data span at least four windows for three buffers and
+    every call reuses a buffer that pool threads were still writing files from."""
     rng = np.random.default_rng(21)
     lens = np.array([0, 1, 48000, 48000, 5, 2_300_001, 70000, 4_194_304 // 2, 48000, 0, 1_200_000, 333, 48000], np.int32)
     n = lens.size
