@@ -234,6 +234,22 @@ LIVE_RELAY_SIGNATURES = {
 }
 LIVE_TX_SKIPPED, LIVE_TX_NONE = 5, -1        # AFSK_LIVE_TX_* statuses of afsk_live_tx_submit_events alone
 
+# The rated live transmitter (a rate per queued message: afsk_live_tx_state_bytes_rated, afsk_live_tx_create_rated,
+# afsk_live_tx_submit_rated, afsk_live_tx_submit_events_rated), likewise.
+LIVE_TX_RATED_SIGNATURES = {
+    "afsk_live_tx_state_bytes_rated": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i64p]),
+    "afsk_live_tx_create_rated": (C.c_int, [C.c_int32, C.c_int32, _i32p, _i32p, C.c_int32, C.c_int32,
+                                            C.POINTER(C.c_void_p)]),
+    # afsk_live_tx_submit's arguments, the DEVICE rate_index behind channel
+    "afsk_live_tx_submit_rated": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # afsk_live_tx_submit_events' arguments, the DEVICE rate array and its row width behind skip_flags
+    "afsk_live_tx_submit_events_rated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+LIVE_TX_BAD_RATE = 6                         # AFSK_LIVE_TX_BAD_RATE
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -250,7 +266,8 @@ def lib() -> C.CDLL:
                                   *LIVE_CLASS_SIGNATURES.items(), *LIVE_TAP_SIGNATURES.items(),
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
-                                  *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items()):
+                                  *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
+                                  *LIVE_TX_RATED_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

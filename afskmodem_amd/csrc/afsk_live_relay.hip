@@ -187,6 +187,95 @@ __global__ __launch_bounds__(kRelayThreads) void live_relay_kernel(RelayArgs a, 
     }
 }
 
+// What the rated relay adds (a rated transmitter, afsk_live_tx_submit_events_rated): the table, the geometry ring it
+// writes next to the descriptors, and the rates the auto receiver's push left -- int32 [n_rx, rx_slots], entry
+// (channel, slot) of a record its burst's bit_frames.  A null rx_bf: every record plays at table entry 0.
+struct RelayRated {
+    const TxGeom* rates;
+    TxGeom* msg_geom;
+    const int32_t* rx_bf;
+    int32_t n_rates;
+    int32_t rx_slots;
+};
+
+// live_relay_kernel for a rated transmitter (kept a kernel of its own: the one above is the code it was): the record's
+// rate is looked up in the table (the first entry with its bit_frames; none: AFSK_LIVE_TX_BAD_RATE, behind _TOO_LONG
+// and in front of _QUEUE_FULL), a record whose (channel, slot) lies outside the rate array is AFSK_LIVE_TX_SKIPPED
+// before the array is read, and a queued message's geometry goes to msg_geom next to its descriptor.
+__global__ __launch_bounds__(kRelayThreads) void live_relay_rated_kernel(RelayArgs a, RelayRated rated,
+                                                                         const int32_t* __restrict__ scratch,
+                                                                         const afsk_live_event* __restrict__ records,
+                                                                         const uint8_t* __restrict__ payload,
+                                                                         const int32_t* __restrict__ map) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t base = ((int64_t)blockIdx.x * (kRelayThreads / 64) + wave) * kRelayPerWave;
+    if (base >= a.max_events) return;
+    const int32_t first_bad = scratch[0];
+    const int32_t stored = scratch[1];
+    auto put = [&](int32_t j, int32_t status, int64_t start, int32_t ns) {
+        if (lane == 0) {
+            a.out_status[j] = status;
+            a.out_start[j] = start;
+            a.out_n_samples[j] = ns;
+        }
+    };
+    for (int k = 0; k < kRelayPerWave; k++) {
+        const int32_t i = (int32_t)base + k;
+        if (i >= a.max_events) break;
+        if (i >= stored) { put(i, AFSK_LIVE_TX_NONE, -1, 0); continue; }
+        if (i >= first_bad) { put(i, AFSK_LIVE_TX_UNSORTED, -1, 0); continue; }
+        const int32_t ch = records[i].channel;
+        if (i > 0 && records[i - 1].channel == ch) continue;      // not the first of its run
+        // the run's destination channel; the map is read for a channel of the receiver alone
+        int32_t dst = ch;
+        bool dropped = false;
+        if (map) {
+            const bool in_rx = ch >= 0 && ch < a.n_rx;
+            dst = in_rx ? map[ch] : -1;
+            dropped = in_rx && dst < 0;
+        }
+        const bool ok = dst >= 0 && dst < a.n;
+        TxChan st = ok ? a.chan[dst] : TxChan{};
+        for (int32_t j = i; j < first_bad && records[j].channel == ch; j++) {
+            const afsk_live_event r = records[j];
+            const int64_t off = r.payload_offset;
+            // (the last line: no place in the rate array -- decided before the array is read)
+            if ((r.flags & a.skip_flags) != 0 || r.status != AFSK_ST_OK || r.nbytes < 1 || r.nbytes > a.out_stride ||
+                off < 0 || off + r.nbytes > a.max_bytes || dropped ||
+                (rated.rx_bf && (ch < 0 || ch >= a.n_rx || r.slot < 0 || r.slot >= rated.rx_slots))) {
+                put(j, AFSK_LIVE_TX_SKIPPED, -1, 0);
+                continue;
+            }
+            const int32_t plen = r.nbytes;
+            if (!ok) { put(j, AFSK_LIVE_TX_BAD_CHANNEL, -1, 0); continue; }
+            if (plen > a.max_payload) { put(j, AFSK_LIVE_TX_TOO_LONG, -1, 0); continue; }
+            int32_t idx = 0;                                      // the first table entry at the rate heard
+            if (rated.rx_bf) {
+                const int32_t heard = rated.rx_bf[(int64_t)ch * rated.rx_slots + r.slot];
+                while (idx < rated.n_rates && rated.rates[idx].bf != heard) idx++;
+            }
+            if (idx >= rated.n_rates) { put(j, AFSK_LIVE_TX_BAD_RATE, -1, 0); continue; }
+            const TxGeom g = rated.rates[idx];
+            if (st.count >= a.depth) { put(j, AFSK_LIVE_TX_QUEUE_FULL, -1, 0); continue; }
+            const int64_t start = st.pos > st.end ? st.pos : st.end;
+            const int32_t ns = g.bf * (g.n_train_sym + 4 + 14 * plen) + AFSK_TAIL_SILENCE;   // <= AFSK_MAX_STREAM_LEN
+            int32_t slot = st.head + st.count;
+            if (slot >= a.depth) slot -= a.depth;
+            const int64_t e = (int64_t)dst * a.depth + slot;
+            if (lane == 0) {
+                a.desc[e] = TxDesc{start, ns, plen};
+                rated.msg_geom[e] = g;
+            }
+            relay_copy(a.slots + e * a.max_payload, payload + off, plen, lane);
+            st.end = start + ns;
+            st.count++;
+            put(j, AFSK_LIVE_TX_QUEUED, start, ns);
+        }
+        if (ok && lane == 0) a.chan[dst] = st;
+    }
+}
+
 }  // namespace afsk
 
 extern "C" {
@@ -213,10 +302,15 @@ int afsk_live_relay_check_map(const int32_t* map_host, int32_t n_rx_channels, in
     });
 }
 
-int afsk_live_tx_submit_events(afsk_live_tx* tx, const void* events, int32_t max_events, int32_t max_bytes,
-                               int32_t out_stride, int32_t n_rx_channels, const int32_t* d_channel_map_or_null,
-                               int32_t skip_flags, int32_t* out_status, int64_t* out_start, int32_t* out_n_samples,
-                               void* hip_stream) {
+namespace {
+
+// Both relay entries.  `rated_entry`: the call came through afsk_live_tx_submit_events_rated (a rated transmitter
+// only), rx_bf / rx_slots its rate array; a rated transmitter served through afsk_live_tx_submit_events plays every
+// record at table entry 0 (rx_bf null).
+int relay_submit(afsk_live_tx* tx, bool rated_entry, const void* events, int32_t max_events, int32_t max_bytes,
+                 int32_t out_stride, int32_t n_rx_channels, const int32_t* d_channel_map_or_null, int32_t skip_flags,
+                 const int32_t* rx_bf, int32_t rx_slots, int32_t* out_status, int64_t* out_start,
+                 int32_t* out_n_samples, void* hip_stream) {
     if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
     if (max_events < 0 || max_bytes < 0 || out_stride < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_rx_channels < 1) return afsk::fail(AFSK_E_INVALID_ARG, "n_rx_channels must be at least 1");
@@ -225,6 +319,12 @@ int afsk_live_tx_submit_events(afsk_live_tx* tx, const void* events, int32_t max
         return afsk::fail(AFSK_E_INVALID_ARG, "skip_flags may hold AFSK_LIVE_OPEN_END and AFSK_LIVE_OVERFLOW alone");
     if (!events || !out_status || !out_start || !out_n_samples)
         return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (rated_entry && (!rx_bf || rx_slots < 1))
+        return afsk::fail(AFSK_E_INVALID_ARG, "d_rx_bit_frames must not be NULL and rx_slots must be at least 1");
+    if (rated_entry && tx->n_rates == 0)
+        return afsk::fail(AFSK_E_INVALID_ARG,
+                          "afsk_live_tx_submit_events_rated needs a transmitter of afsk_live_tx_create_rated "
+                          "(this one takes afsk_live_tx_submit_events)");
     if ((uintptr_t)events & 15) return afsk::fail(AFSK_E_INVALID_ARG, "the events buffer must be 16-byte aligned");
     if (max_events == 0) return AFSK_OK;
     if (int rc = tx->state.check_current()) return rc;
@@ -262,10 +362,40 @@ int afsk_live_tx_submit_events(afsk_live_tx* tx, const void* events, int32_t max
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return afsk::hip_fail(e, "launch live_relay_order_kernel");
     const uint32_t blocks = (uint32_t)(((int64_t)max_events + afsk::kRelayPerBlock - 1) / afsk::kRelayPerBlock);
-    hipLaunchKernelGGL(afsk::live_relay_kernel, dim3(blocks), dim3(afsk::kRelayThreads), 0, st, a, in.scratch,
-                       in.records, in.payload, in.map, in.geom);
+    if (tx->n_rates) {
+        afsk::RelayRated rated{};
+        rated.rates = reinterpret_cast<const afsk::TxGeom*>(d + tx->R.o_rates);
+        rated.msg_geom = reinterpret_cast<afsk::TxGeom*>(d + tx->R.o_msg_geom);
+        rated.rx_bf = rx_bf;
+        rated.n_rates = tx->n_rates;
+        rated.rx_slots = rx_slots;
+        hipLaunchKernelGGL(afsk::live_relay_rated_kernel, dim3(blocks), dim3(afsk::kRelayThreads), 0, st, a, rated,
+                           in.scratch, in.records, in.payload, in.map);
+    } else {
+        hipLaunchKernelGGL(afsk::live_relay_kernel, dim3(blocks), dim3(afsk::kRelayThreads), 0, st, a, in.scratch,
+                           in.records, in.payload, in.map, in.geom);
+    }
     e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_relay_kernel");
+}
+
+}  // namespace
+
+int afsk_live_tx_submit_events(afsk_live_tx* tx, const void* events, int32_t max_events, int32_t max_bytes,
+                               int32_t out_stride, int32_t n_rx_channels, const int32_t* d_channel_map_or_null,
+                               int32_t skip_flags, int32_t* out_status, int64_t* out_start, int32_t* out_n_samples,
+                               void* hip_stream) {
+    return relay_submit(tx, false, events, max_events, max_bytes, out_stride, n_rx_channels, d_channel_map_or_null,
+                        skip_flags, nullptr, 0, out_status, out_start, out_n_samples, hip_stream);
+}
+
+int afsk_live_tx_submit_events_rated(afsk_live_tx* tx, const void* events, int32_t max_events, int32_t max_bytes,
+                                     int32_t out_stride, int32_t n_rx_channels, const int32_t* d_channel_map_or_null,
+                                     int32_t skip_flags, const int32_t* d_rx_bit_frames, int32_t rx_slots,
+                                     int32_t* out_status, int64_t* out_start, int32_t* out_n_samples,
+                                     void* hip_stream) {
+    return relay_submit(tx, true, events, max_events, max_bytes, out_stride, n_rx_channels, d_channel_map_or_null,
+                        skip_flags, d_rx_bit_frames, rx_slots, out_status, out_start, out_n_samples, hip_stream);
 }
 
 }  // extern "C"

@@ -23,6 +23,12 @@
 // array past the uniform layout; submit and live_tx_tile_kernel_mixed read them per channel, and the tile kernel picks
 // the small- or large-q tone code per wave (a wave renders tiles of one channel, so the branch is wave-uniform).
 //
+// A rated transmitter (afsk_live_tx_create_rated) keeps a table of up to AFSK_DETECT_MAX_CANDIDATES geometries and one
+// TxGeom per RING ENTRY past the uniform layout: a submit (afsk_live_tx_submit_rated, or the relay's
+// afsk_live_tx_submit_events_rated) writes the message's geometry next to its descriptor, and
+// live_tx_tile_kernel_rated loads the channel's geometry ring with its descriptor ring and renders every tile with the
+// geometry of the message the tile meets (the tone code again chosen per wave and tile).
+//
 // Every message is at least 4 symbols + the 4800-sample silent tail long, so the tones of two messages of a channel
 // are at least 4800 samples apart and a tile of at most 4096 samples meets the tones of one message at most.
 //
@@ -53,7 +59,7 @@ struct TxDesc {             // 16 bytes per ring entry
 };
 static_assert(sizeof(TxDesc) == 16, "TxDesc layout");
 
-struct TxGeom {             // 8 bytes per channel of a mixed transmitter
+struct TxGeom {             // 8 bytes per channel of a mixed transmitter, per table and ring entry of a rated one
     int32_t bf;             // bit_frames: a multiple of 4 in 4 ... 48000
     int32_t n_train_sym;    // 2 * ts_cycles (ts_cycles >= 0)
 };
@@ -98,6 +104,19 @@ inline int live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_p
 
 // A mixed transmitter's allocation: the uniform layout, then TxGeom [n] (256-byte aligned: L.bytes is).
 inline int64_t live_tx_mixed_bytes(const TxLayout& L) { return L.bytes + tx_align256(8 * L.n); }
+
+// A rated transmitter's allocation: the uniform layout, then the table TxGeom [n_rates], then TxGeom [n, depth] (one
+// geometry per ring entry, written by the submit that writes the entry); each part 256-byte aligned.
+struct TxRatedLayout {
+    int64_t o_rates = 0, o_msg_geom = 0, bytes = 0;
+};
+inline TxRatedLayout live_tx_rated_layout(const TxLayout& L, int32_t n_rates) {
+    TxRatedLayout R;
+    R.o_rates = L.bytes;
+    R.o_msg_geom = R.o_rates + tx_align256(8 * (int64_t)n_rates);
+    R.bytes = R.o_msg_geom + tx_align256(8 * L.n * L.depth);
+    return R;
+}
 
 // ------------------------------------------------------------------------------------------------------- submit
 
@@ -165,6 +184,53 @@ __global__ __launch_bounds__(256) void live_tx_submit_kernel(TxSubmitArgs a) {
         if (slot >= a.depth) slot -= a.depth;
         const int64_t e = (int64_t)ch * a.depth + slot;
         a.desc[e] = TxDesc{start, ns, plen};
+        uint8_t* dst = a.slots + e * a.max_payload;
+        const uint8_t* src = a.payload + a.payload_offset[j];
+        for (int32_t b = 0; b < plen; b++) dst[b] = src[b];
+        st.end = start + ns;
+        st.count++;
+        put(j, AFSK_LIVE_TX_QUEUED, start, ns);
+    }
+    if (ok) a.chan[ch] = st;
+}
+
+// live_tx_submit_kernel for a rated transmitter (kept a kernel of its own: the one above is the code it was): message
+// j plays at rates[rate_index[j]] (a null rate_index: rates[0]), an index outside 0 ... n_rates - 1 is
+// AFSK_LIVE_TX_BAD_RATE -- behind _TOO_LONG, in front of _QUEUE_FULL -- and the geometry of a queued message goes to
+// msg_geom next to its descriptor.
+__global__ __launch_bounds__(256) void live_tx_submit_rated_kernel(TxSubmitArgs a, const int32_t* rate_index,
+                                                                   const TxGeom* rates, int32_t n_rates,
+                                                                   TxGeom* msg_geom) {
+    const int32_t i = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= a.n_msgs) return;
+    auto put = [&](int32_t j, int32_t status, int64_t start, int32_t ns) {
+        const int32_t k = a.out_index ? a.out_index[j] : j;
+        if ((uint32_t)k >= (uint32_t)a.n_msgs) return;          // (not a permutation: nothing written for it)
+        a.out_status[k] = status;
+        a.out_start[k] = start;
+        a.out_n_samples[k] = ns;
+    };
+    const int32_t first_bad = *a.first_bad;
+    if (i >= first_bad) { put(i, AFSK_LIVE_TX_UNSORTED, -1, 0); return; }
+    const int32_t ch = a.channel[i];
+    if (i > 0 && a.channel[i - 1] == ch) return;                // not the first of its run
+    const bool ok = ch >= 0 && ch < a.n;
+    TxChan st = ok ? a.chan[ch] : TxChan{};
+    for (int32_t j = i; j < first_bad && a.channel[j] == ch; j++) {
+        const int32_t plen = a.payload_len[j];
+        if (!ok) { put(j, AFSK_LIVE_TX_BAD_CHANNEL, -1, 0); continue; }
+        if (plen < 0 || plen > a.max_payload) { put(j, AFSK_LIVE_TX_TOO_LONG, -1, 0); continue; }
+        const int32_t r = rate_index ? rate_index[j] : 0;
+        if (r < 0 || r >= n_rates) { put(j, AFSK_LIVE_TX_BAD_RATE, -1, 0); continue; }
+        const TxGeom g = rates[r];
+        if (st.count >= a.depth) { put(j, AFSK_LIVE_TX_QUEUE_FULL, -1, 0); continue; }
+        const int64_t start = st.pos > st.end ? st.pos : st.end;
+        const int32_t ns = g.bf * (g.n_train_sym + 4 + 14 * plen) + AFSK_TAIL_SILENCE;   // <= AFSK_MAX_STREAM_LEN
+        int32_t slot = st.head + st.count;
+        if (slot >= a.depth) slot -= a.depth;
+        const int64_t e = (int64_t)ch * a.depth + slot;
+        a.desc[e] = TxDesc{start, ns, plen};
+        msg_geom[e] = g;
         uint8_t* dst = a.slots + e * a.max_payload;
         const uint8_t* src = a.payload + a.payload_offset[j];
         for (int32_t b = 0; b < plen; b++) dst[b] = src[b];
@@ -252,8 +318,21 @@ __device__ __forceinline__ void tx_render(int16_t* dst0, uint32_t len, int32_t x
     }
 }
 
+// The geometry ring of a rated transmitter's channel in LDS (KIND 3 alone: the other kinds have no such array).
+template <int KIND>
+__device__ __forceinline__ TxGeom* tx_geom_ring() {
+    if constexpr (KIND == 3) {
+        __shared__ TxGeom gring[kTxLdsRing];
+        return gring;
+    } else {
+        return nullptr;
+    }
+}
+
 // KIND 0 / 1: a uniform transmitter whose q = bf / 4 is >= 8 / < 8 (a.bf, a.n_train_sym); KIND 2: a mixed one, the
-// channel's geometry from geom[c] and the tone code chosen per wave.  RAGGED: the channel's samples end at
+// channel's geometry from geom[c] and the tone code chosen per wave; KIND 3: a rated one, geom the per-entry
+// geometries TxGeom [n, depth]: the geometry and the tone code are those of the message each tile meets, so nothing
+// derived from them lives outside the tile loop.  RAGGED: the channel's samples end at
 // clamp(lens[c], 0, a.T) instead of a.T (a null lens: a.T); the instantiations without the flag are the code they were.
 template <int KIND, bool RAGGED = false>
 __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, const int32_t* lens = nullptr) {
@@ -285,7 +364,13 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, c
     const TxDesc* gring = a.desc + (int64_t)c * a.depth;
     const uint8_t* gpay = a.slots + (int64_t)c * a.depth * a.max_payload;
     const bool lds_ring = a.depth <= kTxLdsRing;
-    if (lds_ring && (int)threadIdx.x < a.depth) ring[threadIdx.x] = gring[threadIdx.x];
+    TxGeom* const lgeom = tx_geom_ring<KIND>();
+    const TxGeom* ggeom = nullptr;                                     // KIND 3: the channel's geometry ring
+    if constexpr (KIND == 3) ggeom = geom + (int64_t)c * a.depth;
+    if (lds_ring && (int)threadIdx.x < a.depth) {
+        ring[threadIdx.x] = gring[threadIdx.x];
+        if constexpr (KIND == 3) lgeom[threadIdx.x] = ggeom[threadIdx.x];
+    }
     __syncthreads();
 
     for (int k = 0; k < a.tiles_per_block; k++) {
@@ -314,6 +399,11 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, c
                 lim = tones;
                 plen = (uint32_t)d.payload_len;
                 slot = e;
+                if constexpr (KIND == 3) {                             // the message's own geometry (wave-uniform)
+                    const TxGeom g = lds_ring ? lgeom[e] : ggeom[e];
+                    bf = (uint32_t)__builtin_amdgcn_readfirstlane(g.bf);
+                    n_train_sym = (uint32_t)__builtin_amdgcn_readfirstlane(g.n_train_sym);
+                }
                 break;
             }
         }
@@ -373,7 +463,7 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, c
         const uint32_t mq = (65536u + q - 1u) / q;
         const int32_t xb = (int32_t)(Sb * bf);
         const bool odd = (x0 & 1) != 0;
-        if (KIND == 2) {                                               // block- (= wave-) uniform
+        if (KIND >= 2) {                                               // block- (= wave-) uniform
             if (q < 8u) tx_render<true>(dst0, len, x0, lim, xb, q, rcp_q, mq, qbits, odd);
             else tx_render<false>(dst0, len, x0, lim, xb, q, rcp_q, mq, qbits, odd);
         } else {
@@ -390,6 +480,12 @@ __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8
 __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel_mixed(
     TxPullArgs a, const TxGeom* geom) {
     live_tx_tile<2>(a, geom);
+}
+
+// A rated transmitter's tile kernel: msg_geom = TxGeom [n, depth], the geometry of every ring entry.
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_kernel_rated(
+    TxPullArgs a, const TxGeom* msg_geom) {
+    live_tx_tile<3>(a, msg_geom);
 }
 
 // channel c advances by T samples: the messages that have ended are retired, pending is what is left
@@ -426,6 +522,11 @@ __global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     live_tx_tile<2, true>(a, geom, lens);
 }
 
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_ragged_kernel_rated(
+    TxPullArgs a, const TxGeom* msg_geom, const int32_t* lens) {
+    live_tx_tile<3, true>(a, msg_geom, lens);
+}
+
 __global__ __launch_bounds__(256) void live_tx_commit_ragged_kernel(TxChan* chan, const TxDesc* desc, int32_t n,
                                                                     int32_t depth, int32_t T, const int32_t* lens,
                                                                     int32_t* pending) {
@@ -450,10 +551,12 @@ __global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const 
 }  // namespace afsk
 
 struct afsk_live_tx {
-    afsk::DeviceState state;                    // the layout's L.bytes, or live_tx_mixed_bytes(L)
+    afsk::DeviceState state;                    // the layout's L.bytes, live_tx_mixed_bytes(L), or R.bytes (rated)
     afsk::TxLayout L;
     int32_t bit_frames = 0, n_train_sym = 0;   // (a mixed transmitter: 0, see o_geom)
     int64_t o_geom = 0;                         // mixed: offset of TxGeom [n] in the state (0: uniform)
+    int32_t n_rates = 0;                        // rated: entries of the table (0: not rated; then o_geom is 0 too)
+    afsk::TxRatedLayout R;                      // rated: offsets of the table and of TxGeom [n, depth] in the state
 };
 
 namespace {
@@ -505,9 +608,109 @@ int tx_create(int32_t n_channels, const int32_t* bit_frames, const int32_t* ts_c
     });
 }
 
+int tx_check_n_rates(int32_t n_rates) {
+    if (n_rates < 1 || n_rates > AFSK_DETECT_MAX_CANDIDATES)
+        return afsk::fail(AFSK_E_INVALID_ARG, "n_rates must lie in 1 ... 36 (AFSK_DETECT_MAX_CANDIDATES)");
+    return AFSK_OK;
+}
+
+// Both submit entries.  `rated_entry`: the call came through afsk_live_tx_submit_rated (a rated transmitter only); a
+// rated transmitter's messages get rates[rate_index[i]], every one entry 0 with a null rate_index.
+int tx_submit(afsk_live_tx* tx, bool rated_entry, int32_t n_msgs, const int32_t* channel, const int32_t* rate_index,
+              const int64_t* payload_offset, const int32_t* payload_len, const uint8_t* payload,
+              const int32_t* out_index, int32_t* out_status, int64_t* out_start, int32_t* out_n_samples,
+              void* hip_stream) {
+    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (n_msgs < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
+    if (n_msgs == 0) return AFSK_OK;
+    if (!channel || !payload_offset || !payload_len || !payload || !out_status || !out_start || !out_n_samples)
+        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (rated_entry && tx->n_rates == 0)
+        return afsk::fail(AFSK_E_INVALID_ARG,
+                          "afsk_live_tx_submit_rated needs a transmitter of afsk_live_tx_create_rated "
+                          "(this one takes afsk_live_tx_submit)");
+    if (int rc = tx->state.check_current()) return rc;
+    const afsk::TxLayout& L = tx->L;
+    uint8_t* d = tx->state.ptr();
+    int32_t* first_bad = reinterpret_cast<int32_t*>(d + L.o_scratch);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(afsk::live_tx_order_kernel, dim3(1), dim3(256), 0, st, channel, n_msgs, first_bad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_order_kernel");
+    afsk::TxSubmitArgs a{};
+    a.chan = reinterpret_cast<afsk::TxChan*>(d);
+    a.desc = reinterpret_cast<afsk::TxDesc*>(d + L.o_desc);
+    a.slots = d + L.o_slots;
+    a.first_bad = first_bad;
+    a.channel = channel;
+    a.payload_offset = payload_offset;
+    a.payload_len = payload_len;
+    a.payload = payload;
+    a.out_index = out_index;
+    a.out_status = out_status;
+    a.out_start = out_start;
+    a.out_n_samples = out_n_samples;
+    a.n_msgs = n_msgs;
+    a.n = (int32_t)L.n;
+    a.depth = (int32_t)L.depth;
+    a.max_payload = (int32_t)L.max_payload;
+    a.bf = tx->bit_frames;
+    a.n_train_sym = tx->n_train_sym;
+    a.geom = tx->o_geom ? reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom) : nullptr;
+    const dim3 grid((uint32_t)((n_msgs + 255) / 256));
+    if (tx->n_rates)
+        hipLaunchKernelGGL(afsk::live_tx_submit_rated_kernel, grid, dim3(256), 0, st, a, rate_index,
+                           reinterpret_cast<const afsk::TxGeom*>(d + tx->R.o_rates), tx->n_rates,
+                           reinterpret_cast<afsk::TxGeom*>(d + tx->R.o_msg_geom));
+    else
+        hipLaunchKernelGGL(afsk::live_tx_submit_kernel, grid, dim3(256), 0, st, a);
+    e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_submit_kernel");
+}
+
 }  // namespace
 
 extern "C" {
+
+int afsk_live_tx_state_bytes_rated(int32_t n_channels, int32_t n_rates, int32_t queue_depth, int32_t max_payload_len,
+                                   int64_t* out_state_bytes) {
+    afsk::TxLayout L;
+    if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, L)) return rc;
+    if (int rc = tx_check_n_rates(n_rates)) return rc;
+    if (out_state_bytes) *out_state_bytes = afsk::live_tx_rated_layout(L, n_rates).bytes;
+    return AFSK_OK;
+}
+
+int afsk_live_tx_create_rated(int32_t n_channels, int32_t n_rates, const int32_t* bit_frames_host,
+                              const int32_t* ts_cycles_host, int32_t queue_depth, int32_t max_payload_len,
+                              afsk_live_tx** out) {
+    if (!out) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    *out = nullptr;
+    if (int rc = tx_check_n_rates(n_rates)) return rc;
+    if (!bit_frames_host || !ts_cycles_host) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    for (int32_t r = 0; r < n_rates; r++)
+        if (!tx_bf_valid(bit_frames_host[r])) return tx_fail_bit_frames();
+    return afsk::no_throw([&] {
+        std::unique_ptr<afsk_live_tx> tx(new afsk_live_tx());
+        const afsk::TxLayout& L = tx->L;
+        if (int rc = afsk::live_tx_layout(n_channels, queue_depth, max_payload_len, tx->L)) return rc;
+        std::vector<afsk::TxGeom> table((size_t)n_rates);
+        for (int32_t r = 0; r < n_rates; r++) {
+            const int64_t nts = tx_train_sym(ts_cycles_host[r]);
+            if (int rc = tx_check_longest(bit_frames_host[r], nts, max_payload_len)) return rc;
+            table[r] = afsk::TxGeom{bit_frames_host[r], (int32_t)nts};
+        }
+        tx->n_rates = n_rates;
+        tx->R = afsk::live_tx_rated_layout(L, n_rates);
+        // the channel states and the table need a value: a ring entry and its geometry are written by the submit that
+        // queues the message, and a pull reads only entries in [head, head + count)
+        if (int rc = tx->state.create("afsk_live_tx_create_rated", tx->R.bytes, L.o_desc, table.data(), tx->R.o_rates,
+                                      8 * (int64_t)n_rates))
+            return rc;
+        *out = tx.release();
+        return AFSK_OK;
+    });
+}
 
 int afsk_live_tx_layout(int32_t n_channels, int32_t queue_depth, int32_t max_payload_len, int64_t* out_state_bytes) {
     return tx_state_bytes(n_channels, queue_depth, max_payload_len, false, out_state_bytes);
@@ -554,42 +757,16 @@ int afsk_live_tx_info(const afsk_live_tx* tx, int32_t* out_n_channels, int32_t* 
 int afsk_live_tx_submit(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel, const int64_t* payload_offset,
                         const int32_t* payload_len, const uint8_t* payload, const int32_t* out_index,
                         int32_t* out_status, int64_t* out_start, int32_t* out_n_samples, void* hip_stream) {
-    if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
-    if (n_msgs < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
-    if (n_msgs == 0) return AFSK_OK;
-    if (!channel || !payload_offset || !payload_len || !payload || !out_status || !out_start || !out_n_samples)
-        return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
-    if (int rc = tx->state.check_current()) return rc;
-    const afsk::TxLayout& L = tx->L;
-    uint8_t* d = tx->state.ptr();
-    int32_t* first_bad = reinterpret_cast<int32_t*>(d + L.o_scratch);
-    const hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(afsk::live_tx_order_kernel, dim3(1), dim3(256), 0, st, channel, n_msgs, first_bad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_order_kernel");
-    afsk::TxSubmitArgs a{};
-    a.chan = reinterpret_cast<afsk::TxChan*>(d);
-    a.desc = reinterpret_cast<afsk::TxDesc*>(d + L.o_desc);
-    a.slots = d + L.o_slots;
-    a.first_bad = first_bad;
-    a.channel = channel;
-    a.payload_offset = payload_offset;
-    a.payload_len = payload_len;
-    a.payload = payload;
-    a.out_index = out_index;
-    a.out_status = out_status;
-    a.out_start = out_start;
-    a.out_n_samples = out_n_samples;
-    a.n_msgs = n_msgs;
-    a.n = (int32_t)L.n;
-    a.depth = (int32_t)L.depth;
-    a.max_payload = (int32_t)L.max_payload;
-    a.bf = tx->bit_frames;
-    a.n_train_sym = tx->n_train_sym;
-    a.geom = tx->o_geom ? reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom) : nullptr;
-    hipLaunchKernelGGL(afsk::live_tx_submit_kernel, dim3((uint32_t)((n_msgs + 255) / 256)), dim3(256), 0, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_tx_submit_kernel");
+    return tx_submit(tx, false, n_msgs, channel, nullptr, payload_offset, payload_len, payload, out_index, out_status,
+                     out_start, out_n_samples, hip_stream);
+}
+
+int afsk_live_tx_submit_rated(afsk_live_tx* tx, int32_t n_msgs, const int32_t* channel, const int32_t* rate_index,
+                              const int64_t* payload_offset, const int32_t* payload_len, const uint8_t* payload,
+                              const int32_t* out_index, int32_t* out_status, int64_t* out_start,
+                              int32_t* out_n_samples, void* hip_stream) {
+    return tx_submit(tx, true, n_msgs, channel, rate_index, payload_offset, payload_len, payload, out_index, out_status,
+                     out_start, out_n_samples, hip_stream);
 }
 
 namespace {
@@ -631,7 +808,13 @@ int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_sa
         a.bf = (uint32_t)tx->bit_frames;
         a.n_train_sym = (uint32_t)tx->n_train_sym;
         const dim3 grid((uint32_t)(a.blocks_per_row * L.n));
-        if (ragged && tx->o_geom)
+        const afsk::TxGeom* msg_geom = reinterpret_cast<const afsk::TxGeom*>(d + tx->R.o_msg_geom);   // (rated)
+        if (ragged && tx->n_rates)
+            hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel_rated, grid, dim3(afsk::kTxThreads), 0, st, a, msg_geom,
+                               lens);
+        else if (tx->n_rates)
+            hipLaunchKernelGGL(afsk::live_tx_tile_kernel_rated, grid, dim3(afsk::kTxThreads), 0, st, a, msg_geom);
+        else if (ragged && tx->o_geom)
             hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel_mixed, grid, dim3(afsk::kTxThreads), 0, st, a,
                                reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom), lens);
         else if (ragged && tx->bit_frames / 4 >= 8)

@@ -1086,12 +1086,22 @@ def tx_state_bytes_mixed(n_channels: int, queue_depth: int, max_payload_len: int
     return int(nbytes.value)
 
 
+def tx_state_bytes_rated(n_channels: int, n_rates: int, queue_depth: int, max_payload_len: int) -> int:
+    """Device state bytes of a rated live transmitter -- a rate per queued message out of a table of ``n_rates``
+    (``afsk_live_tx_state_bytes_rated``: host-only)."""
+    nbytes = C.c_int64()
+    _native.check(_native.lib().afsk_live_tx_state_bytes_rated(int(n_channels), int(n_rates), int(queue_depth),
+                                                               int(max_payload_len), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
 @dataclass
 class SubmitResult:
     """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order, or of one
     ``submit_events``, entry i for record i of the events buffer."""
     status: "object"         # int32 [n] LIVE_TX_QUEUED / _QUEUE_FULL / _TOO_LONG / _BAD_CHANNEL (submit_events: also
-                             # _UNSORTED, _SKIPPED and, from the push's record count on, _NONE)
+                             # _UNSORTED, _SKIPPED, with rate="heard" _BAD_RATE and, from the push's record count on,
+                             # _NONE)
     start: "object"          # int64 [n] stream index of the first sample (-1: rejected)
     n_samples: "object"      # int32 [n] samples of the message (0: rejected)
 
@@ -1116,19 +1126,52 @@ class LiveTransmitter(batch._NativePlan):
     follows the previous one with no gap, one queued on an idle channel starts at the next sample pulled.  Submits and
     pulls never synchronise with the host; a pull of a fixed T into a fixed buffer can be captured into a graph.  The
     transmitter belongs to the device that was current (or ``device``); ``close()`` only after its launches have
-    completed."""
+    completed.
+
+    ``rates=[...]`` builds the RATED transmitter (``afsk_live_tx_create_rated``): a rate per queued MESSAGE out of a
+    table of up to 36.  An entry is a baud rate, played with ``training_time`` (one value, or one per entry), or a
+    ``Transmitter``, which gives both its rate and its training time.  ``submit(..., baud_rate=)`` names the rate of
+    every message, ``submit_events(..., rate="heard")`` relays every burst at the rate an auto receiver heard it at.
+    ``rated`` is True, ``rates`` the tuple of bauds, ``rate_bit_frames`` and ``rate_ts_cycles`` int32 [n_rates];
+    ``baud_rate``, ``bit_frames`` and ``ts_cycles`` are None and ``channel_bit_frames`` is all 0, as on the auto
+    receiver.  Everything else -- queues, back-to-back starts, ``pending``, ``reset``, plain and ragged pulls, graph
+    capture -- is the live transmitter's own."""
     _destroy = "afsk_live_tx_destroy"
+    rated = False                                # (True, with the three below set, on a rated transmitter)
+    rates = rate_bit_frames = rate_ts_cycles = None
 
     def __init__(self, n_channels: int, baud_rate: int = 1200, training_time: float = 0.5,
-                 queue_depth: int = DEFAULT_QUEUE_DEPTH, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, device=None):
+                 queue_depth: int = DEFAULT_QUEUE_DEPTH, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, device=None,
+                 rates=None):
         torch = batch._torch()
         from .modem import Transmitter
         if int(n_channels) < 1:
             raise ValueError("n_channels must be at least 1")
         self.n_channels = int(n_channels)
-        bauds = _per_channel(baud_rate, self.n_channels, "baud_rate")
-        times = _per_channel(training_time, self.n_channels, "training_time")
-        if bauds is None and times is None:
+        self.rated = rates is not None
+        self.rates = self.rate_bit_frames = self.rate_ts_cycles = None
+        if self.rated:
+            if np.ndim(baud_rate) != 0:
+                raise ValueError("rates= gives a rate per message: a per-channel baud_rate sequence does not go with it")
+            table = list(rates)
+            if not 1 <= len(table) <= _native.DETECT_MAX_CANDIDATES:
+                raise ValueError(f"rates must hold 1 ... {_native.DETECT_MAX_CANDIDATES} entries, got {len(table)}")
+            times = _per_channel(training_time, len(table), "training_time")
+            times = times if times is not None else [training_time] * len(table)
+            # (a Transmitter entry brings its own training time)
+            pairs = [(r.baud_rate, r.training_time) if isinstance(r, Transmitter) else (r, t)
+                     for r, t in zip(table, times)]
+            self.rate_bit_frames = np.asarray([tx_bit_frames(b) for b, _ in pairs], np.int32)
+            self.rates = tuple(int(b) for b, _ in pairs)
+            self.rate_ts_cycles = np.asarray([Transmitter(int(b), t).ts_cycles for b, t in pairs], np.int32)  # ref:438
+            self.bit_frames = self.baud_rate = self.ts_cycles = None
+            self.channel_bit_frames = np.zeros(self.n_channels, np.int32)
+            self.channel_ts_cycles = np.zeros(self.n_channels, np.int32)
+        bauds = None if self.rated else _per_channel(baud_rate, self.n_channels, "baud_rate")
+        times = None if self.rated else _per_channel(training_time, self.n_channels, "training_time")
+        if self.rated:
+            pass
+        elif bauds is None and times is None:
             self.bit_frames = tx_bit_frames(baud_rate)
             self.baud_rate = int(baud_rate)
             self.ts_cycles = Transmitter(self.baud_rate, training_time).ts_cycles  # ref:438 (negative: no cycles)
@@ -1152,10 +1195,15 @@ class LiveTransmitter(batch._NativePlan):
         super().__init__(device)
         nbytes = C.c_int64()
         with torch.cuda.device(self.device):
-            # (one geometry in every entry: the C entry builds the one-geometry transmitter)
-            _native.check(_native.lib().afsk_live_tx_create_mixed(
-                self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_ts_cycles),
-                self.queue_depth, self.max_payload_len, C.byref(self._h)))
+            if self.rated:
+                _native.check(_native.lib().afsk_live_tx_create_rated(
+                    self.n_channels, len(self.rates), _i32_ptr(self.rate_bit_frames), _i32_ptr(self.rate_ts_cycles),
+                    self.queue_depth, self.max_payload_len, C.byref(self._h)))
+            else:
+                # (one geometry in every entry: the C entry builds the one-geometry transmitter)
+                _native.check(_native.lib().afsk_live_tx_create_mixed(
+                    self.n_channels, _i32_ptr(self.channel_bit_frames), _i32_ptr(self.channel_ts_cycles),
+                    self.queue_depth, self.max_payload_len, C.byref(self._h)))
             _native.check(_native.lib().afsk_live_tx_info(self.handle, None, None, None, C.byref(nbytes)))
         self.state_bytes = int(nbytes.value)
         # messages queued or on air per channel after the last pull (0 for channels reset since)
@@ -1171,10 +1219,34 @@ class LiveTransmitter(batch._NativePlan):
         return cls(len(transmitters), [t.baud_rate for t in transmitters], [t.training_time for t in transmitters],
                    **capacities)
 
-    def message_len(self, payload_len, channels=None) -> "int | np.ndarray":
+    def _rate_index(self, baud_rate, shape=()) -> np.ndarray:
+        """The table entries (int32, broadcast to ``shape``) of ``baud_rate`` -- one rate or an array of them, the
+        first entry at that rate; None: entry 0 -- on a rated transmitter; ValueError for a rate the table lacks."""
+        if not self.rated:
+            raise ValueError("baud_rate= needs a rated transmitter (LiveTransmitter(n, rates=[...]))")
+        if baud_rate is None:
+            return np.zeros(shape, np.int32)
+        want = np.asarray(baud_rate)
+        table = np.asarray(self.rates, np.int64)
+        hit = want[..., None] == table
+        if not hit.any(axis=-1).all():
+            missing = sorted(set(np.asarray(want)[~hit.any(axis=-1)].reshape(-1).tolist()))
+            raise ValueError(f"baud rate(s) {missing} are not in the transmitter's table {list(self.rates)}")
+        return np.broadcast_to(hit.argmax(axis=-1).astype(np.int32), np.broadcast_shapes(want.shape, shape))
+
+    def message_len(self, payload_len, channels=None, baud_rate=None) -> "int | np.ndarray":
         """Samples of a message of ``payload_len`` bytes: tones + the 4800-sample silent tail (ref:452-469), at the
         geometry of ``channels`` (an int or an array, broadcast against ``payload_len``; None: the one geometry of a
-        one-geometry transmitter, every channel's -- an [n_channels] array, broadcast -- of a mixed one)."""
+        one-geometry transmitter, every channel's -- an [n_channels] array, broadcast -- of a mixed one).  A rated
+        transmitter: at the table entry of ``baud_rate`` (one rate or an array; None: entry 0), whatever the channel."""
+        if self.rated:
+            idx = self._rate_index(baud_rate)
+            bf = self.rate_bit_frames.astype(np.int64)[idx]
+            ts = np.maximum(self.rate_ts_cycles.astype(np.int64)[idx], 0)
+            out = bf * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
+            return int(out) if np.ndim(out) == 0 else out
+        if baud_rate is not None:
+            raise ValueError("baud_rate= needs a rated transmitter (LiveTransmitter(n, rates=[...]))")
         if channels is None and self.bit_frames is not None:
             ts = max(self.ts_cycles, 0)
             return self.bit_frames * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
@@ -1186,14 +1258,24 @@ class LiveTransmitter(batch._NativePlan):
         out = bf * (2 * ts + 4 + 14 * np.asarray(payload_len, np.int64)) + 4800
         return int(out) if np.ndim(out) == 0 else out
 
-    def submit(self, channels, payloads, stream=None) -> SubmitResult:
+    def submit(self, channels, payloads, stream=None, baud_rate=None) -> SubmitResult:
         """Queue ``payloads[i]`` (str -- UTF-8 -- or bytes) on channel ``channels[i]`` (a sequence, or one int for
         all).  A channel's messages are queued in list order.  Everything goes up in one copy; the outputs are device
         tensors in list order, and nothing synchronises.  Asynchronous on ``stream`` (default: torch's current
-        stream)."""
+        stream).
+
+        A rated transmitter: ``baud_rate`` is the rate of every message, or one per message (None: the table's first
+        entry); a rate the table lacks raises ValueError.  ``baud_rate=`` on any other transmitter raises."""
         torch = batch._torch()
         data = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in payloads]
         n = len(data)
+        if baud_rate is not None and not self.rated:
+            raise ValueError("baud_rate= needs a rated transmitter (LiveTransmitter(n, rates=[...]))")
+        rate_idx = None
+        if self.rated and baud_rate is not None:
+            if np.ndim(baud_rate) != 0 and np.shape(baud_rate) != (n,):
+                raise ValueError(f"{np.size(baud_rate)} baud rates for {n} payloads")
+            rate_idx = self._rate_index(baud_rate, (n,))
         ch = np.broadcast_to(np.asarray(channels, np.int64), (n,)) if np.ndim(channels) == 0 else \
             np.asarray(channels, np.int64)
         if ch.shape != (n,):
@@ -1209,8 +1291,12 @@ class LiveTransmitter(batch._NativePlan):
         lens = np.array([len(d) for d in data], np.int64)[perm]
         offs = np.zeros(n, np.int64)
         np.cumsum(lens[:-1], out=offs[1:])
-        # one host buffer, one copy: offsets int64 | channels int32 | lengths int32 | out_index int32 | payload bytes
+        # one host buffer, one copy: offsets int64 | channels int32 | lengths int32 | out_index int32 | rate index
+        # int32 (a rated submit with rates given) | payload bytes
         head = 8 * n + 4 * n + 4 * n + (0 if ordered else 4 * n)
+        at_rate = head
+        if rate_idx is not None:
+            head += 4 * n
         host = torch.empty(head + int(lens.sum()), dtype=torch.uint8, pin_memory=True)
         h = host.numpy()
         h[: 8 * n].view(np.int64)[:] = offs
@@ -1218,6 +1304,8 @@ class LiveTransmitter(batch._NativePlan):
         h[12 * n: 16 * n].view(np.int32)[:] = np.minimum(lens, 2 ** 31 - 1)
         if not ordered:
             h[16 * n: 20 * n].view(np.int32)[:] = perm
+        if rate_idx is not None:
+            h[at_rate: at_rate + 4 * n].view(np.int32)[:] = rate_idx[perm]
         h[head:] = np.frombuffer(b"".join(data[i] for i in perm.tolist()), np.uint8)
         with torch.cuda.device(dev):
             s = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -1227,9 +1315,15 @@ class LiveTransmitter(batch._NativePlan):
                 batch._order_after_current(stream, dev)      # (the outputs were allocated on the current stream)
                 d.record_stream(stream)
             base = d.data_ptr()
-            _native.check(_native.lib().afsk_live_tx_submit(
-                self.handle, n, base + 8 * n, base, base + 12 * n, base + head, None if ordered else base + 16 * n,
-                out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(), batch._stream_ptr(s, dev)))
+            if rate_idx is not None:
+                _native.check(_native.lib().afsk_live_tx_submit_rated(
+                    self.handle, n, base + 8 * n, base + at_rate, base, base + 12 * n, base + head,
+                    None if ordered else base + 16 * n, out.status.data_ptr(), out.start.data_ptr(),
+                    out.n_samples.data_ptr(), batch._stream_ptr(s, dev)))
+            else:
+                _native.check(_native.lib().afsk_live_tx_submit(
+                    self.handle, n, base + 8 * n, base, base + 12 * n, base + head, None if ordered else base + 16 * n,
+                    out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(), batch._stream_ptr(s, dev)))
         out._keepalive = d  # type: ignore[attr-defined]
         return out
 
@@ -1276,7 +1370,7 @@ class LiveTransmitter(batch._NativePlan):
         return t, True
 
     def submit_events(self, events: "LiveEvents", channel_map=None, skip_flags: int = _native.LIVE_OPEN_END,
-                      out: SubmitResult | None = None, stream=None) -> SubmitResult:
+                      out: SubmitResult | None = None, stream=None, rate=None) -> SubmitResult:
         """Relay: queue the bursts a receiver's push closed, straight from its packed event list on the device
         (``afsk_live_tx_submit_events``) -- no copy to the host and no synchronisation, so ``push(events=)``,
         ``submit_events(out=)`` and ``pull`` of fixed buffers can be captured into ONE graph.
@@ -1297,7 +1391,20 @@ class LiveTransmitter(batch._NativePlan):
         The result holds ``[max_events]`` tensors, entry i for record i: the statuses, starts and sample counts of
         ``submit``, ``LIVE_TX_SKIPPED``, and ``LIVE_TX_NONE`` from the push's record count on.  ``out``
         (``alloc_submit_result``) reuses them.  Asynchronous on ``stream`` (default: torch's current stream), behind
-        the pack when that ran on the same stream."""
+        the pack when that ran on the same stream.
+
+        ``rate="heard"`` (a rated transmitter and the events of an auto receiver's push, ValueError otherwise): every
+        burst is queued at the rate the receiver detected for it (``afsk_live_tx_submit_events_rated`` reads
+        ``events.result.bit_frames`` on the device); a rate the table lacks -- a burst the receiver did not rate is one
+        -- answers ``LIVE_TX_BAD_RATE``.  ``rate=None``: a rated transmitter plays every burst at its first entry."""
+        if rate is not None:                                     # (what needs no device comes first)
+            if rate != "heard":
+                raise ValueError('rate must be None or "heard"')
+            if not self.rated:
+                raise ValueError('rate="heard" needs a rated transmitter (LiveTransmitter(n, rates=[...]))')
+            if isinstance(events, LiveEvents) and events.result is not None and events.result.bit_frames is None:
+                raise ValueError('rate="heard" needs the events of an auto receiver\'s push '
+                                 '(LiveReceiver(n, "auto", ...)): this result holds no detected rates')
         _native.require_device()
         torch = batch._torch()
         if not isinstance(events, LiveEvents):
@@ -1311,6 +1418,13 @@ class LiveTransmitter(batch._NativePlan):
         if res is None:
             raise ValueError("events references no LiveResult: pack a push into it first (push(events=...))")
         n_rx, stride = int(res.n_closed.shape[0]), int(res.demod.bytes.shape[1])
+        heard = None
+        if rate == "heard":
+            heard = res.bit_frames
+            if not isinstance(heard, torch.Tensor) or heard.dtype != torch.int32 or heard.device != dev \
+                    or tuple(heard.shape) != (n_rx, int(res.slots)) or not heard.is_contiguous():
+                raise ValueError(f"the result's bit_frames must be a contiguous int32 [{n_rx}, {int(res.slots)}] "
+                                 f"tensor on {dev}")
         me, mb = events.max_events, events.max_bytes
         ro, po, total = events_layout(n_rx, res.slots, me, mb)
         if (events.records_offset, events.payload_offset) != (ro, po) or int(buf.numel()) < total:
@@ -1333,11 +1447,17 @@ class LiveTransmitter(batch._NativePlan):
                 batch._order_after_current(stream, dev)
             if uploaded and stream is not None:
                 cmap.record_stream(stream)
-            _native.check(_native.lib().afsk_live_tx_submit_events(
-                self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
-                out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(),
-                batch._stream_ptr(stream, dev)))
-        out._keepalive = (buf, cmap)  # type: ignore[attr-defined]
+            if heard is not None:
+                _native.check(_native.lib().afsk_live_tx_submit_events_rated(
+                    self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
+                    heard.data_ptr(), int(res.slots), out.status.data_ptr(), out.start.data_ptr(),
+                    out.n_samples.data_ptr(), batch._stream_ptr(stream, dev)))
+            else:
+                _native.check(_native.lib().afsk_live_tx_submit_events(
+                    self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
+                    out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(),
+                    batch._stream_ptr(stream, dev)))
+        out._keepalive = (buf, cmap, heard)  # type: ignore[attr-defined]
         return out
 
     def pull(self, T: int, out=None, stream=None, lengths=None):

@@ -1087,6 +1087,61 @@ extern int afsk_live_tx_submit_events(afsk_live_tx *tx, const void *events, int3
                                       int32_t *out_n_samples, void *hip_stream);
 
 /*
+ * The rated live transmitter (added after ABI version 2; the version is unchanged): a rate per queued MESSAGE, where
+ * afsk_live_tx_create has one for the transmitter's life and afsk_live_tx_create_mixed one per channel -- a digipeater
+ * on a shared calling channel repeats every burst at the rate it heard.  The transmitter holds a table of up to
+ * AFSK_DETECT_MAX_CANDIDATES geometries and every queued message names one entry; queues, back-to-back starts, pulls
+ * (plain and ragged), pending, reset, info and destroy are afsk_live_tx's own.
+ *
+ *  afsk_live_tx_state_bytes_rated  host-only (no device needed): the state bytes of such a transmitter --
+ *                              afsk_live_tx_layout's, then the table int32 [n_rates, 2] (bit_frames, training symbols),
+ *                              then int32 [n_channels, queue_depth, 2], the geometry of every ring entry; each part
+ *                              256-byte aligned.  afsk_live_tx_info reports the same total.
+ *  afsk_live_tx_create_rated   Transmitter.__init__ (ref:436-450) once per table entry: bit_frames_host, ts_cycles_host
+ *                              HOST arrays [n_rates], n_rates in 1 ... 36 (AFSK_E_INVALID_ARG), each bit_frames a
+ *                              multiple of 4 in 4 ... 48000 (AFSK_E_INVALID_BAUD), each ts_cycles as afsk_live_tx_create
+ *                              (negative: no training cycles, ref:457), and every entry's longest message at most
+ *                              AFSK_MAX_STREAM_LEN samples.  Equal bit_frames in two entries are fine (two training
+ *                              lengths at one rate).  The arrays are the caller's again on return.
+ *  afsk_live_tx_submit_rated   afsk_live_tx_submit (Transmitter.transmit's samples, ref:452-469 and 472-478, queued)
+ *                              with rate_index: DEVICE int32 [n_msgs], the table entry message i plays at, or NULL:
+ *                              entry 0 for all.  n_samples = bit_frames * (2 * ts_cycles + 4 + 14 * payload_len) + 4800
+ *                              of that entry.  An index outside 0 ... n_rates - 1: AFSK_LIVE_TX_BAD_RATE, nothing
+ *                              queued.  The checks of a message run in this order: _UNSORTED, _BAD_CHANNEL, _TOO_LONG,
+ *                              _BAD_RATE, _QUEUE_FULL.  Two launches, as afsk_live_tx_submit.
+ *  afsk_live_tx_submit_events_rated  afsk_live_tx_submit_events (ref:472-478 for every burst heard) with the rate of
+ *                              record r read on the device from d_rx_bit_frames[r.channel * rx_slots + r.slot]: the
+ *                              DEVICE int32 [n_rx_channels, rx_slots] array afsk_live_push_auto wrote as
+ *                              out_bit_frames in the push the events were packed from.  The first table entry with that
+ *                              bit_frames is the message's; none (a burst the receiver did not rate holds 0):
+ *                              AFSK_LIVE_TX_BAD_RATE.  A record whose channel lies outside 0 ... n_rx_channels - 1 or
+ *                              whose slot lies outside 0 ... rx_slots - 1 is AFSK_LIVE_TX_SKIPPED and the array is not
+ *                              read for it.  Order: afsk_live_tx_submit_events' steps 1 - 3 with that condition among
+ *                              the _SKIPPED ones (so a record that is not relayable never reads the array), then
+ *                              _BAD_CHANNEL, _TOO_LONG, _BAD_RATE, _QUEUE_FULL.  Two launches, no atomics, no host read.
+ *                              AFSK_E_INVALID_ARG besides afsk_live_tx_submit_events': a NULL d_rx_bit_frames,
+ *                              rx_slots < 1.
+ * On a rated transmitter afsk_live_tx_submit and afsk_live_tx_submit_events queue every message at table entry 0.  The
+ * two _rated submit entries on a transmitter that is not rated: AFSK_E_INVALID_ARG, nothing launched.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_TX_RATED_SIGNATURES.)
+ */
+#define AFSK_LIVE_TX_BAD_RATE 6 /* rate_index outside the table / the rate heard is not in the table: nothing queued */
+extern int afsk_live_tx_state_bytes_rated(int32_t n_channels, int32_t n_rates, int32_t queue_depth,
+                                          int32_t max_payload_len, int64_t *out_state_bytes);
+extern int afsk_live_tx_create_rated(int32_t n_channels, int32_t n_rates, const int32_t *bit_frames_host,
+                                     const int32_t *ts_cycles_host, int32_t queue_depth, int32_t max_payload_len,
+                                     afsk_live_tx **out);
+extern int afsk_live_tx_submit_rated(afsk_live_tx *tx, int32_t n_msgs, const int32_t *channel,
+                                     const int32_t *rate_index, const int64_t *payload_offset,
+                                     const int32_t *payload_len, const uint8_t *payload, const int32_t *out_index,
+                                     int32_t *out_status, int64_t *out_start, int32_t *out_n_samples, void *hip_stream);
+extern int afsk_live_tx_submit_events_rated(afsk_live_tx *tx, const void *events, int32_t max_events,
+                                            int32_t max_bytes, int32_t out_stride, int32_t n_rx_channels,
+                                            const int32_t *d_channel_map_or_null, int32_t skip_flags,
+                                            const int32_t *d_rx_bit_frames, int32_t rx_slots, int32_t *out_status,
+                                            int64_t *out_start, int32_t *out_n_samples, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
