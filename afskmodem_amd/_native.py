@@ -250,6 +250,14 @@ LIVE_TX_RATED_SIGNATURES = {
 }
 LIVE_TX_BAD_RATE = 6                         # AFSK_LIVE_TX_BAD_RATE
 
+# Carrier sense (afsk_live_busy, afsk_live_tx_pull_hold), likewise.
+LIVE_TX_HOLD_SIGNATURES = {
+    "afsk_live_busy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # afsk_live_tx_pull_ragged's arguments, the DEVICE hold and the holdoff behind lens, out_deferred behind out_pending
+    "afsk_live_tx_pull_hold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -267,7 +275,7 @@ def lib() -> C.CDLL:
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
-                                  *LIVE_TX_RATED_SIGNATURES.items()):
+                                  *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -342,6 +342,13 @@ __global__ __launch_bounds__(256) void live_reset_kernel(LiveChan* chan, const u
     if (c < n && (!mask || mask[c])) chan[c] = LiveChan{};
 }
 
+// afsk_live_busy: busy[c] = 1 while channel c's gate is recording a burst (every receiver kind keeps LiveChan [n] at
+// the front of its state)
+__global__ __launch_bounds__(256) void live_busy_kernel(const LiveChan* chan, int32_t* busy, int32_t n) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < n) busy[c] = chan[c].mode == 2 ? 1 : 0;
+}
+
 }  // namespace afsk
 
 namespace afsk {
@@ -661,6 +668,17 @@ int afsk_live_reset(afsk_live* live, const uint8_t* d_mask_or_null, void* hip_st
                        (int32_t)live->L.n);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_reset_kernel");
+}
+
+int afsk_live_busy(afsk_live* live, int32_t* d_out_busy, void* hip_stream) {
+    if (!live) return afsk::fail(AFSK_E_INVALID_ARG, "null live receiver");
+    if (!d_out_busy) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (int rc = live->state.check_current()) return rc;
+    hipLaunchKernelGGL(afsk::live_busy_kernel, dim3((uint32_t)((live->L.n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)hip_stream, static_cast<const afsk::LiveChan*>(live->state.d), d_out_busy,
+                       (int32_t)live->L.n);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? AFSK_OK : afsk::hip_fail(e, "launch live_busy_kernel");
 }
 
 int afsk_live_destroy(afsk_live* live) {

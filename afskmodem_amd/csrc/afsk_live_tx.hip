@@ -19,6 +19,12 @@
 // one channel, so len_c is one block-uniform scalar load; tiles at or past len_c do nothing, the tile that straddles
 // it is cut there (tx_store's partial store), and columns [len_c, T) of the row are not written.
 //
+// A hold pull (afsk_live_tx_pull_hold) is the ragged pull with carrier sense, again two launches: a channel whose
+// hold[c] is set starts no message in this pull, and after a hold none starts for `holdoff` further samples (the wait
+// counter w in TxChan::pad[0]).  live_tx_tile_hold_kernel renders the messages that have not begun `delta` samples
+// later (tx_hold_delta) without writing state; live_tx_commit_hold_kernel derives the same delta, writes the shifted
+// starts into the ring, the channel's end, w and deferred[c], and then commits as the other pulls do.
+//
 // A mixed transmitter (afsk_live_tx_create_mixed) keeps each channel's bit_frames and training symbols in a TxGeom
 // array past the uniform layout; submit and live_tx_tile_kernel_mixed read them per channel, and the tile kernel picks
 // the small- or large-q tone code per wave (a wave renders tiles of one channel, so the branch is wave-uniform).
@@ -48,7 +54,8 @@ struct TxChan {             // 32 bytes per channel
     int64_t end;            // end (stream index) of the last message queued; <= pos once the queue has drained
     int32_t head;           // ring entry of the oldest message not yet fully emitted
     int32_t count;          // messages queued or on air
-    int32_t pad[2];
+    int32_t pad[2];         // pad[0]: the hold pull's wait counter w (afsk_live_tx_pull_hold; 0 after create and reset,
+                            // neither read nor written by the plain and ragged pulls); pad[1]: spare
 };
 static_assert(sizeof(TxChan) == 32, "TxChan layout");
 
@@ -318,6 +325,17 @@ __device__ __forceinline__ void tx_render(int16_t* dst0, uint32_t len, int32_t x
     }
 }
 
+// The hold rule (afsk_live_tx_pull_hold, include/afsk_amd.h), shared by the tile kernels' hold form and the hold
+// commit.  A channel that advances L samples in this pull lets no message begin before `earliest`: the end of the pull
+// when it is held, else pos + w (w: the wait counter a hold left, TxChan::pad[0]).  u, the oldest message with
+// start >= pos, and every message behind it move by delta = max(0, earliest - u.start).
+__device__ __forceinline__ int64_t tx_hold_earliest(const TxChan& ch, int32_t L, bool held) {
+    return ch.pos + (held ? L : ch.pad[0]);
+}
+__device__ __forceinline__ int64_t tx_hold_delta(int64_t earliest, int64_t u_start) {
+    return earliest > u_start ? earliest - u_start : 0;
+}
+
 // The geometry ring of a rated transmitter's channel in LDS (KIND 3 alone: the other kinds have no such array).
 template <int KIND>
 __device__ __forceinline__ TxGeom* tx_geom_ring() {
@@ -334,8 +352,14 @@ __device__ __forceinline__ TxGeom* tx_geom_ring() {
 // geometries TxGeom [n, depth]: the geometry and the tone code are those of the message each tile meets, so nothing
 // derived from them lives outside the tile loop.  RAGGED: the channel's samples end at
 // clamp(lens[c], 0, a.T) instead of a.T (a null lens: a.T); the instantiations without the flag are the code they were.
-template <int KIND, bool RAGGED = false>
-__device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, const int32_t* lens = nullptr) {
+// HOLD (afsk_live_tx_pull_hold): the channel's messages that have not begun (start >= pos) are rendered `delta` samples
+// later, delta the hold rule's shift (tx_hold_delta) of the oldest of them, found in the tile's own ring walk -- one
+// more block-uniform int32 load (hold[c]; the wait counter comes with the channel state).  The kernel only reads
+// state: live_tx_commit_hold_kernel derives the same delta and writes the shifted starts.  The instantiations without
+// the flag are the code they were.
+template <int KIND, bool RAGGED = false, bool HOLD = false>
+__device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, const int32_t* lens = nullptr,
+                                             const int32_t* hold = nullptr) {
     __shared__ uint8_t win[kWinBytes];
     __shared__ unsigned long long kinds[kTxTile / 4 / 64 + 2];
     __shared__ uint32_t qbits[q_words(kTxTile)];
@@ -356,6 +380,9 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, c
     // the channel state (and geometry) and its whole descriptor ring, loaded at once (no address depends on another
     // of these loads)
     const TxChan ch = a.chan[c];
+    int64_t earliest = 0;                                              // HOLD: no message begins before this sample
+    int64_t delta = -1;                                                // HOLD: the shift, < 0 until the walk meets u
+    if constexpr (HOLD) earliest = tx_hold_earliest(ch, (int32_t)T, hold && hold[c] != 0);
     if (KIND == 2) {
         const TxGeom g = geom[c];
         bf = (uint32_t)g.bf;
@@ -392,10 +419,17 @@ __device__ __forceinline__ void live_tx_tile(TxPullArgs a, const TxGeom* geom, c
         int32_t slot = 0;
         for (int32_t i = 0, e = ch.head; i < ch.count; i++, e = (e + 1 == a.depth ? 0 : e + 1)) {
             const TxDesc d = lds_ring ? ring[e] : gring[e];
-            if (d.start >= p0 + len) break;
+            int64_t start = d.start;
+            if constexpr (HOLD) {
+                if (start >= ch.pos) {                                 // not begun: u (the first such) and all behind
+                    if (delta < 0) delta = tx_hold_delta(earliest, start);
+                    start += delta;
+                }
+            }
+            if (start >= p0 + len) break;
             const int32_t tones = d.n_samples - AFSK_TAIL_SILENCE;
-            if (d.start + tones > p0) {
-                m0 = p0 - d.start;
+            if (start + tones > p0) {
+                m0 = p0 - start;
                 lim = tones;
                 plen = (uint32_t)d.payload_len;
                 slot = e;
@@ -536,6 +570,60 @@ __global__ __launch_bounds__(256) void live_tx_commit_ragged_kernel(TxChan* chan
         const int32_t l = lens[c];
         T = l < 0 ? 0 : (l < T ? l : T);
     }
+    live_tx_commit(chan, desc, c, depth, T, pending);
+}
+
+// The hold pull's kernels (afsk_live_tx_pull_hold): the ragged forms with the hold rule (lens and hold DEVICE arrays or
+// NULL).
+template <bool SMALLQ>
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_hold_kernel(
+    TxPullArgs a, const int32_t* lens, const int32_t* hold) {
+    live_tx_tile<SMALLQ ? 1 : 0, true, true>(a, nullptr, lens, hold);
+}
+
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_hold_kernel_mixed(
+    TxPullArgs a, const TxGeom* geom, const int32_t* lens, const int32_t* hold) {
+    live_tx_tile<2, true, true>(a, geom, lens, hold);
+}
+
+__global__ __launch_bounds__(kTxThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void live_tx_tile_hold_kernel_rated(
+    TxPullArgs a, const TxGeom* msg_geom, const int32_t* lens, const int32_t* hold) {
+    live_tx_tile<3, true, true>(a, msg_geom, lens, hold);
+}
+
+// One thread per channel: the hold rule's writes, then live_tx_commit.  It derives the delta the tile kernel rendered
+// with from the same state, adds it to the start of u and of every ring entry behind u (entries head + i ... head +
+// count - 1, wrapping at depth; read from global memory whatever the depth) and to the channel's end, sets the wait
+// counter (holdoff when held, else what is left of it after L samples) and writes deferred[c].
+__global__ __launch_bounds__(256) void live_tx_commit_hold_kernel(TxChan* chan, TxDesc* desc, int32_t n, int32_t depth,
+                                                                  int32_t T, const int32_t* lens, const int32_t* hold,
+                                                                  int32_t holdoff, int32_t* pending,
+                                                                  int64_t* deferred) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    if (lens) {
+        const int32_t l = lens[c];
+        T = l < 0 ? 0 : (l < T ? l : T);
+    }
+    TxChan st = chan[c];
+    const bool held = hold && hold[c] != 0;
+    const int64_t earliest = tx_hold_earliest(st, T, held);
+    TxDesc* ring = desc + (int64_t)c * depth;
+    int64_t delta = 0;
+    for (int32_t i = 0, e = st.head; i < st.count; i++, e = (e + 1 == depth ? 0 : e + 1)) {
+        if (delta == 0) {
+            const int64_t start = ring[e].start;
+            if (start < st.pos) continue;                              // on air, or in its silent tail
+            delta = tx_hold_delta(earliest, start);                    // e is u
+            if (delta == 0) break;
+        }
+        ring[e].start += delta;
+    }
+    st.end += delta;                                                   // (delta > 0: u is queued, so end >= u's end)
+    const int32_t w = st.pad[0];
+    st.pad[0] = held ? holdoff : (w > T ? w - T : 0);
+    chan[c] = st;
+    deferred[c] = delta;
     live_tx_commit(chan, desc, c, depth, T, pending);
 }
 
@@ -771,10 +859,21 @@ int afsk_live_tx_submit_rated(afsk_live_tx* tx, int32_t n_msgs, const int32_t* c
 
 namespace {
 
-// afsk_live_tx_pull and afsk_live_tx_pull_ragged (`ragged`: the ragged kernels, lens a DEVICE array or NULL)
+// What afsk_live_tx_pull_hold adds to a pull's arguments (a null TxHold: the plain or ragged pull).
+struct TxHold {
+    const int32_t* hold;        // DEVICE int32 [n] or NULL (nobody held)
+    int32_t holdoff;
+    int64_t* deferred;
+};
+
+// afsk_live_tx_pull, afsk_live_tx_pull_ragged (`ragged`: the ragged kernels, lens a DEVICE array or NULL) and
+// afsk_live_tx_pull_hold (`hd`: the hold kernels, which are ragged ones)
 int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, bool ragged, const int32_t* lens,
-            int32_t* out_pending, void* hip_stream) {
+            int32_t* out_pending, void* hip_stream, const TxHold* hd = nullptr) {
     if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
+    if (hd && (hd->holdoff < 0 || hd->holdoff > AFSK_MAX_STREAM_LEN))
+        return afsk::fail(AFSK_E_INVALID_ARG, "holdoff must lie in 0 ... AFSK_MAX_STREAM_LEN");
+    if (hd && !hd->deferred) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument (out_deferred)");
     if (n_samples < 0 || out_row_stride < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_samples > AFSK_MAX_STREAM_LEN) return afsk::fail(AFSK_E_INVALID_ARG, "n_samples exceeds AFSK_MAX_STREAM_LEN");
     const afsk::TxLayout& L = tx->L;
@@ -809,7 +908,19 @@ int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_sa
         a.n_train_sym = (uint32_t)tx->n_train_sym;
         const dim3 grid((uint32_t)(a.blocks_per_row * L.n));
         const afsk::TxGeom* msg_geom = reinterpret_cast<const afsk::TxGeom*>(d + tx->R.o_msg_geom);   // (rated)
-        if (ragged && tx->n_rates)
+        if (hd && tx->n_rates)
+            hipLaunchKernelGGL(afsk::live_tx_tile_hold_kernel_rated, grid, dim3(afsk::kTxThreads), 0, st, a, msg_geom,
+                               lens, hd->hold);
+        else if (hd && tx->o_geom)
+            hipLaunchKernelGGL(afsk::live_tx_tile_hold_kernel_mixed, grid, dim3(afsk::kTxThreads), 0, st, a,
+                               reinterpret_cast<const afsk::TxGeom*>(d + tx->o_geom), lens, hd->hold);
+        else if (hd && tx->bit_frames / 4 >= 8)
+            hipLaunchKernelGGL(afsk::live_tx_tile_hold_kernel<false>, grid, dim3(afsk::kTxThreads), 0, st, a, lens,
+                               hd->hold);
+        else if (hd)
+            hipLaunchKernelGGL(afsk::live_tx_tile_hold_kernel<true>, grid, dim3(afsk::kTxThreads), 0, st, a, lens,
+                               hd->hold);
+        else if (ragged && tx->n_rates)
             hipLaunchKernelGGL(afsk::live_tx_tile_ragged_kernel_rated, grid, dim3(afsk::kTxThreads), 0, st, a, msg_geom,
                                lens);
         else if (tx->n_rates)
@@ -829,7 +940,11 @@ int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_sa
         e = hipGetLastError();
         if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_tile_kernel");
     }
-    if (ragged)
+    if (hd)
+        hipLaunchKernelGGL(afsk::live_tx_commit_hold_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st,
+                           chan, reinterpret_cast<afsk::TxDesc*>(d + L.o_desc), (int32_t)L.n, (int32_t)L.depth,
+                           n_samples, lens, hd->hold, hd->holdoff, out_pending, hd->deferred);
+    else if (ragged)
         hipLaunchKernelGGL(afsk::live_tx_commit_ragged_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st,
                            chan, desc, (int32_t)L.n, (int32_t)L.depth, n_samples, lens, out_pending);
     else
@@ -849,6 +964,13 @@ int afsk_live_tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, in
 int afsk_live_tx_pull_ragged(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples,
                              const int32_t* d_lens_or_null, int32_t* out_pending, void* hip_stream) {
     return tx_pull(tx, out, out_row_stride, n_samples, true, d_lens_or_null, out_pending, hip_stream);
+}
+
+int afsk_live_tx_pull_hold(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples,
+                           const int32_t* d_lens_or_null, const int32_t* d_hold_or_null, int32_t holdoff,
+                           int32_t* out_pending, int64_t* out_deferred, void* hip_stream) {
+    const TxHold hd{d_hold_or_null, holdoff, out_deferred};
+    return tx_pull(tx, out, out_row_stride, n_samples, true, d_lens_or_null, out_pending, hip_stream, &hd);
 }
 
 int afsk_live_tx_reset(afsk_live_tx* tx, const uint8_t* d_mask_or_null, int32_t* out_pending_or_null,

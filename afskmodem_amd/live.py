@@ -124,6 +124,30 @@ def _device_lengths(lengths, n_channels: int, dev, owner: str):
     return torch.from_numpy(np.ascontiguousarray(v)).to(dev), True
 
 
+def _device_hold(hold, n_channels: int, dev):
+    """The ``hold`` of a hold pull as ``(int32 [n_channels] tensor on dev or None, uploaded)``: an int32 CUDA tensor on
+    ``dev`` is used in place (no copy, no synchronisation); True / False hold every channel / none (False: no array at
+    all); a host sequence, numpy array or CPU tensor of bools or integers is uploaded with one copy.  Anything else --
+    another dtype, another length -- is a ValueError."""
+    torch = batch._torch()
+    if isinstance(hold, (bool, np.bool_)):
+        return (torch.ones(n_channels, dtype=torch.int32, device=dev), True) if hold else (None, False)
+    if isinstance(hold, torch.Tensor) and hold.is_cuda:
+        if hold.dtype != torch.int32:
+            raise ValueError(f"a CUDA hold must hold int32 entries (e.g. LiveReceiver.busy()), got {hold.dtype}")
+        if hold.device != dev:
+            raise ValueError(f"hold is on {hold.device}, the transmitter on {dev}")
+        if hold.dim() != 1 or int(hold.numel()) != n_channels or not hold.is_contiguous():
+            raise ValueError(f"hold must be a contiguous [n_channels={n_channels}], got {list(hold.shape)}")
+        return hold, False
+    v = hold.numpy() if isinstance(hold, torch.Tensor) else np.asarray(hold)
+    if v.dtype.kind not in "biu":
+        raise ValueError(f"hold must hold bool or integer entries, got {v.dtype}")
+    if v.ndim != 1 or v.size != n_channels:
+        raise ValueError(f"hold must be [n_channels={n_channels}], got {list(v.shape)}")
+    return torch.from_numpy(np.ascontiguousarray((v != 0).astype(np.int32))).to(dev), True
+
+
 def _flush_mask(flush, n_channels: int, dev):
     """A per-channel ``flush`` ([n_channels] bool / uint8, host or device) as ``(uint8 tensor on dev, the caller's own
     tensor)`` through ``_device_mask``; a tensor or array of another dtype is a TypeError."""
@@ -1055,6 +1079,28 @@ class LiveReceiver(batch._NativePlan):
             _native.check(_native.lib().afsk_live_reset(self.handle, None if m is None else m.data_ptr(),
                                                         batch._stream_ptr(stream, dev)))
 
+    def busy(self, out=None, stream=None):
+        """int32 ``[n_channels]`` CUDA tensor: 1 for every channel whose gate is recording a burst after the last
+        push, flush or reset, else 0 (``afsk_live_busy``: one launch, no host read).  ``out=`` (a contiguous int32
+        ``[n_channels]`` tensor on the receiver's device) is filled in place and returned -- a fixed address for
+        graphs, and what ``LiveTransmitter.pull(hold=)`` takes."""
+        torch = batch._torch()
+        dev = self.device
+        fresh = out is None
+        if fresh:
+            out = torch.empty(self.n_channels, dtype=torch.int32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32:
+            raise TypeError("out must be an int32 CUDA tensor")
+        elif not out.is_cuda or out.device != dev:
+            raise ValueError(f"out is on {out.device}, the receiver on {dev}")
+        elif out.dim() != 1 or int(out.numel()) != self.n_channels or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous [n_channels={self.n_channels}], got {list(out.shape)}")
+        with torch.cuda.device(dev):
+            if fresh:
+                batch._order_after_current(stream, dev)
+            _native.check(_native.lib().afsk_live_busy(self.handle, out.data_ptr(), batch._stream_ptr(stream, dev)))
+        return out
+
 
 # ------------------------------------------------------------------------------------------------- live transmit
 
@@ -1123,7 +1169,8 @@ class LiveTransmitter(batch._NativePlan):
 
     Each channel queues up to ``queue_depth`` messages not yet fully emitted, of at most ``max_payload_len`` bytes,
     on the device.  A channel's stream is numbered from 0 at creation or ``reset``; a message queued on a busy channel
-    follows the previous one with no gap, one queued on an idle channel starts at the next sample pulled.  Submits and
+    follows the previous one with no gap, one queued on an idle channel starts at the next sample pulled -- unless the
+    channel is held off the air (``pull(hold=, holdoff=)``: carrier sense, ``deferred``).  Submits and
     pulls never synchronise with the host; a pull of a fixed T into a fixed buffer can be captured into a graph.  The
     transmitter belongs to the device that was current (or ``device``); ``close()`` only after its launches have
     completed.
@@ -1208,6 +1255,8 @@ class LiveTransmitter(batch._NativePlan):
         self.state_bytes = int(nbytes.value)
         # messages queued or on air per channel after the last pull (0 for channels reset since)
         self.pending = torch.zeros(self.n_channels, dtype=torch.int32, device=self.device)
+        # samples the last hold pull (pull(hold=)) moved every channel's waiting messages by
+        self.deferred = torch.zeros(self.n_channels, dtype=torch.int64, device=self.device)
 
     @classmethod
     def from_transmitters(cls, transmitters, **capacities) -> "LiveTransmitter":
@@ -1460,7 +1509,7 @@ class LiveTransmitter(batch._NativePlan):
         out._keepalive = (buf, cmap, heard)  # type: ignore[attr-defined]
         return out
 
-    def pull(self, T: int, out=None, stream=None, lengths=None):
+    def pull(self, T: int, out=None, stream=None, lengths=None, hold=None, holdoff: int = 0):
         """Write samples ``[pos, pos + T)`` of every channel into ``out`` ([n_channels, >= T] int16 CUDA tensor with
         contiguous rows and any row stride -- e.g. a column window of a [channels, time] buffer; None: a new [n, T]
         tensor) and return ``out[:, :T]``.  Nothing of ``out`` outside those T columns is written.  Then every
@@ -1470,17 +1519,35 @@ class LiveTransmitter(batch._NativePlan):
         A ragged pull (``afsk_live_tx_pull_ragged``): with ``lengths`` ([n_channels]: an int32 CUDA tensor on the
         transmitter's device, used in place, or a host sequence, uploaded with one copy) channel c writes only columns
         ``[0, len_c)`` with ``len_c = clamp(lengths[c], 0, T)``, leaves the columns from ``len_c`` on as they were
-        (a new ``out`` is zeroed first) and advances by ``len_c``."""
+        (a new ``out`` is zeroed first) and advances by ``len_c``.
+
+        A hold pull (``afsk_live_tx_pull_hold``, carrier sense): with ``hold`` ([n_channels], indexed by TRANSMITTER
+        channel: an int32 CUDA tensor on the transmitter's device such as ``LiveReceiver.busy()``, used in place and
+        read when the kernels run; or True / False; or a host sequence of bools, uploaded with one copy) a channel whose
+        entry is non-zero starts no message in this pull -- one on air plays on, an idle one writes zeros -- and after
+        its last held pull none starts for ``holdoff`` further samples (0 ... AFSK_MAX_STREAM_LEN).  The messages
+        that have not begun move later as a block, back to back as they were, and ``deferred`` (int64 [n_channels],
+        a fixed address like ``pending``) holds by how many samples this pull moved them.  ``hold=False`` with
+        ``holdoff=0`` on a transmitter that was never held is the plain (or ragged) pull bit for bit.  ``hold=None``
+        is today's plain or ragged pull, which knows nothing of the wait; ``holdoff`` without ``hold`` is a
+        ValueError.  A caller whose receiver channels map to other transmitter channels gathers ``busy`` first
+        (``busy[rx_of_tx]``)."""
         torch = batch._torch()
         T = int(T)
         if T < 0:
             raise ValueError("T must be >= 0")
         if T > _native.MAX_STREAM_LEN:
             raise ValueError(f"T = {T} exceeds AFSK_MAX_STREAM_LEN")
+        holdoff = int(holdoff)
+        if hold is None and holdoff != 0:
+            raise ValueError("holdoff needs hold= (hold=False: nobody held, the wait still counts down)")
+        if not 0 <= holdoff <= _native.MAX_STREAM_LEN:
+            raise ValueError(f"holdoff = {holdoff} must lie in 0 ... AFSK_MAX_STREAM_LEN")
         dev = self.device
         fresh = out is None
         lens, lens_up = (None, False) if lengths is None else _device_lengths(lengths, self.n_channels, dev,
                                                                              "transmitter")
+        held, held_up = (None, False) if hold is None else _device_hold(hold, self.n_channels, dev)
         if fresh:
             out = (torch.empty if lens is None else torch.zeros)((self.n_channels, T), dtype=torch.int16, device=dev)
         if not isinstance(out, torch.Tensor):
@@ -1489,11 +1556,18 @@ class LiveTransmitter(batch._NativePlan):
         if self.n_channels > 1 and T > 0 and out.stride(0) < T:
             raise ValueError(f"out row stride {out.stride(0)} is below T = {T}: the rows would overlap")
         with torch.cuda.device(dev):
-            if fresh or lens_up:
+            if fresh or lens_up or held_up:
                 batch._order_after_current(stream, dev)
             if lens_up and stream is not None:
                 lens.record_stream(stream)
-            if lens is not None:
+            if held_up and stream is not None:
+                held.record_stream(stream)
+            if hold is not None:
+                _native.check(_native.lib().afsk_live_tx_pull_hold(
+                    self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T,
+                    None if lens is None else lens.data_ptr(), None if held is None else held.data_ptr(), holdoff,
+                    self.pending.data_ptr(), self.deferred.data_ptr(), batch._stream_ptr(stream, dev)))
+            elif lens is not None:
                 _native.check(_native.lib().afsk_live_tx_pull_ragged(
                     self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T, lens.data_ptr(),
                     self.pending.data_ptr(), batch._stream_ptr(stream, dev)))

@@ -1142,6 +1142,53 @@ extern int afsk_live_tx_submit_events_rated(afsk_live_tx *tx, const void *events
                                             int64_t *out_start, int32_t *out_n_samples, void *hip_stream);
 
 /*
+ * Carrier sense (added after ABI version 2; the version is unchanged): a transmitter channel stays off the air while
+ * the receiver of that channel is hearing a burst, and for a slot time after it stops -- what a packet-radio TNC does
+ * with data carrier detect.  Both halves run on the device, so push -> busy -> submit_events -> pull is one captured
+ * graph with no host read in it.  All of it is integer and sample-exact.
+ *
+ *  afsk_live_busy          d_out_busy[c] (DEVICE int32 [n_channels]) = 1 when channel c's gate is recording a burst (it
+ *                          has heard a block above amp_start and none below amp_end since), else 0: the state the
+ *                          last push, flush or reset left, for a receiver of any kind (stored, streaming, tapped, auto;
+ *                          one rate or mixed; one threshold pair or one per channel; plain or ragged pushes).  One
+ *                          launch of one thread per channel on hip_stream, after the pushes it is ordered behind.
+ *  afsk_live_tx_pull_hold  afsk_live_tx_pull_ragged (its arguments, its checks, d_lens_or_null NULL: n_samples for every
+ *                          channel) with d_hold_or_null (DEVICE int32 [n_channels]; a non-zero entry holds the channel;
+ *                          NULL: nobody is held), holdoff (samples, 0 ... AFSK_MAX_STREAM_LEN, else AFSK_E_INVALID_ARG)
+ *                          and out_deferred (DEVICE int64 [n_channels], not NULL).  hold is indexed by TRANSMITTER
+ *                          channel and read when the kernels run, as d_lens_or_null is.  For channel c, with pos its
+ *                          stream position before the pull, L the samples it advances (n_samples or clamp(lens[c], 0,
+ *                          n_samples)), h = hold[c] != 0, and w the channel's wait counter (int32 state, 0 after create
+ *                          and reset):
+ *                            1. earliest = h ? pos + L : pos + w.
+ *                            2. u = the oldest queued message with start >= pos: it has not begun.  A message with
+ *                               start < pos is on air, or in its silent tail, and is never touched.
+ *                            3. If u exists and u.start < earliest: delta = earliest - u.start; u and every message
+ *                               behind it in the queue get start += delta, the channel's end (where the next submit
+ *                               queues) gets += delta, out_deferred[c] = delta.  Otherwise out_deferred[c] = 0.
+ *                            4. The pull renders and commits exactly as afsk_live_tx_pull_ragged would on the adjusted
+ *                               queue: a message on air plays to its end, a held idle channel writes zeros, with w < L and
+ *                               no hold a message begins w samples into the pull, out_pending counts as before.
+ *                            5. w' = h ? holdoff : max(0, w - L).
+ *                          So: messages queued back to back stay back to back; a later submit queues behind the shifted
+ *                          end; every message is still exactly the samples of its payload at its rate, only later, by the
+ *                          sum of the out_deferred values it lived through; a shift only widens the gap between two
+ *                          messages.  With hold all zero (or NULL), holdoff 0 and w 0 the result is
+ *                          afsk_live_tx_pull_ragged's bit for bit and out_deferred all 0.  A channel with L = 0 that is
+ *                          held shifts nothing and sets w = holdoff.  afsk_live_tx_pull and afsk_live_tx_pull_ragged
+ *                          neither read nor write w, and may alternate with hold pulls.  Works for transmitters of every
+ *                          kind (one geometry, mixed, rated).  Two launches in order on hip_stream (one when n_samples
+ *                          is 0), capturable into a graph.
+ * Not part of the rule: p-persistence or random backoff (every released channel starts after exactly its wait), and
+ * muting a receiver channel while its own transmitter is on air.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_TX_HOLD_SIGNATURES.)
+ */
+extern int afsk_live_busy(afsk_live *live, int32_t *d_out_busy, void *hip_stream);
+extern int afsk_live_tx_pull_hold(afsk_live_tx *tx, int16_t *out, int64_t out_row_stride, int32_t n_samples,
+                                  const int32_t *d_lens_or_null, const int32_t *d_hold_or_null, int32_t holdoff,
+                                  int32_t *out_pending, int64_t *out_deferred, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
