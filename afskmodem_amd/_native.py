@@ -258,6 +258,19 @@ LIVE_TX_HOLD_SIGNATURES = {
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# Half-duplex stations (afsk_live_tx_pull_csma, afsk_live_push_muted, afsk_live_push_auto_muted), likewise.
+_ragged_args = LIVE_RAGGED_SIGNATURES["afsk_live_push_ragged"][1]
+LIVE_CSMA_SIGNATURES = {
+    # afsk_live_tx_pull_hold's arguments, persist, slot and seed behind holdoff, out_on_air behind out_deferred
+    "afsk_live_tx_pull_csma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    # afsk_live_push_ragged's / afsk_live_push_auto's arguments, the DEVICE mute ranges behind the flush mask
+    "afsk_live_push_muted": (C.c_int, _ragged_args[:7] + [C.c_void_p] + _ragged_args[7:]),
+    "afsk_live_push_auto_muted": (C.c_int, _ragged_args[:7] + [C.c_void_p]
+                                  + LIVE_AUTO_SIGNATURES["afsk_live_push_auto"][1][7:]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -275,7 +288,8 @@ def lib() -> C.CDLL:
                                   *LIVE_RAGGED_SIGNATURES.items(), *LIVE_EVENT_SIGNATURES.items(),
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
-                                  *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items()):
+                                  *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
+                                  *LIVE_CSMA_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -141,6 +141,30 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
         }
 }
 
+__device__ __forceinline__ void live_zero_block(vec16 (&v)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = vec16{0u, 0u, 0u, 0u};
+}
+
+// The muted walk's select: sample i of the block (register v[i / 512][(i & 511) / 2 - 4 * lane], low half for an even
+// i) is column col0 + i of the chunk; the samples whose column lies in [lo, hi) become 0.  One per-lane value, the
+// lane's first column relative to lo, and the wave-uniform width hi - lo: sample i is muted iff (uint32)(base + i) <
+// width, i a compile-time constant per register half.
+__device__ __forceinline__ void live_mute_block(vec16 (&v)[4], int32_t col0, int32_t lo, int32_t hi, int lane) {
+    const uint32_t base = (uint32_t)(col0 + 8 * lane - lo);
+    const uint32_t width = (uint32_t)(hi - lo);
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t i = 512u * j + 2u * k;
+            uint32_t x = v[j][k];
+            if (base + i < width) x &= 0xffff0000u;
+            if (base + i + 1u < width) x &= 0x0000ffffu;
+            v[j][k] = x;
+        }
+}
+
 // The gate walk both live receivers share: one wave per channel walks the push's whole blocks through the listen state
 // machine with the next block's load in flight, and hands every event to its sink -- the stored receiver's
 // (LiveStoreSink: record rows and demodulator slots) or the streaming one's (afsk_live_stream.hip: demodulation as
@@ -168,13 +192,26 @@ __device__ __forceinline__ void live_load_carry_block(vec16 (&v)[4], const int16
 // len).  A channel with len 0 and no flush walks no block, copies nothing, and stores the state it loaded.  The sinks
 // never see either value, so plain and ragged pushes of one receiver may alternate.  The instantiations without the
 // flag are the code they were.
-template <bool PER_CHANNEL = false, bool RAGGED = false, class Sink>
+// MUTE (afsk_live_push_muted, with RAGGED only): columns [lo', hi') of the channel's row count as 0, lo' = clamp(mute[c][0],
+// 0, len), hi' = clamp(mute[c][1], lo', len) -- two more wave-uniform scalar loads.  A block whose columns meet the range
+// (a wave-uniform test) gets them cleared in its registers before anything uses it (live_mute_block), so the amplitude
+// and the sink's record see the zeros; the carry copy stores 0 for a muted column, so a muted sample is 0 in the next
+// push too.  Block 0 of a push with a carry goes the same way: its carried samples lie at columns below 0, which no
+// range holds, so they are not muted again.  No column at or beyond len is read, as in the ragged form.  Beyond what
+// the rule needs, a block that lies wholly inside the range is not loaded: its registers are set to zero, and neither
+// the select nor the amplitude sum runs for it.  The instantiations without the flag are the code they were.
+template <bool PER_CHANNEL = false, bool RAGGED = false, bool MUTE = false, class Sink>
 __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, const int32_t* thr_start = nullptr,
                                                const int32_t* thr_end = nullptr, const int32_t* chunk_lens = nullptr,
-                                               const uint8_t* flush_mask = nullptr) {
+                                               const uint8_t* flush_mask = nullptr, const int32_t* mute = nullptr) {
+    static_assert(RAGGED || !MUTE, "the muted walk is a ragged one");
     const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= a.n) return;
+    const int c_lane = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c_lane >= a.n) return;
+    // MUTE: the channel number as the wave-uniform value it is, so the addresses derived from it (the state, the carry,
+    // the outputs) have scalar bases instead of pairs of VGPRs held across the walk -- what keeps the stored cell
+    // inside its ragged twin's register allocation.  The other forms keep the per-lane value: the code they were.
+    const int c = MUTE ? __builtin_amdgcn_readfirstlane(c_lane) : c_lane;
     LiveChan st = a.chan[c];
     int32_t amp_start = a.amp_start, amp_end = a.amp_end;
     if constexpr (PER_CHANNEL) {
@@ -192,6 +229,14 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
         }
         rag_flush = a.flush;
         if (flush_mask) rag_flush |= __builtin_amdgcn_readfirstlane((int32_t)flush_mask[cu]);
+    }
+    int32_t mute_lo = 0, mute_hi = 0;                              // MUTE: the channel's muted columns [lo', hi')
+    if constexpr (MUTE) {
+        const int cu = __builtin_amdgcn_readfirstlane(c);
+        const int32_t lo = __builtin_amdgcn_readfirstlane(mute[2 * (int64_t)cu]);
+        const int32_t hi = __builtin_amdgcn_readfirstlane(mute[2 * (int64_t)cu + 1]);
+        mute_lo = lo < 0 ? 0 : (lo > rag_len ? rag_len : lo);
+        mute_hi = hi < mute_lo ? mute_lo : (hi > rag_len ? rag_len : hi);
     }
     // (the plain form reads LiveArgs where it always did)
     auto len = [&]() -> int32_t {
@@ -224,14 +269,34 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
         sk.report(a, slot0 + k, st, ovf, flags, lane);
         k++;
     };
+    // MUTE: block b lies wholly inside the muted range (wave-uniform; never block 0 of a push with a carry, whose first
+    // column is below 0): it is zeros, and its columns are not loaded
+    auto mute_whole = [&](int32_t b) -> bool {
+        if constexpr (MUTE) {
+            const int32_t col0 = b * kListenBlock - cl;
+            return mute_lo <= col0 && col0 + kListenBlock <= mute_hi;
+        } else {
+            return false;
+        }
+    };
     vec16 cur[4], nxt[4];
     if (nblk > 0) {
         if (cl > 0) live_load_carry_block(cur, carry, src, cl, lane);
+        else if (mute_whole(0)) live_zero_block(cur);
         else live_load_chunk_block(cur, src, lane);
     }
     for (int32_t b = 0; b < nblk; b++) {
-        if (b + 1 < nblk) live_load_chunk_block(nxt, src + (int64_t)(b + 1) * kListenBlock - cl, lane);   // next block in flight
-        const int32_t amp = (int32_t)((uint32_t)__builtin_amdgcn_readlane(block_abs_sum(cur), 63) >> 11);
+        if (b + 1 < nblk) {                                         // next block in flight
+            if (mute_whole(b + 1)) live_zero_block(nxt);
+            else live_load_chunk_block(nxt, src + (int64_t)(b + 1) * kListenBlock - cl, lane);
+        }
+        const bool whole = mute_whole(b);                           // (zeros already: no select, and no sum to take)
+        if constexpr (MUTE) {
+            const int32_t col0 = b * kListenBlock - cl;             // the block's first column (< 0: carried samples)
+            if (!whole && mute_lo < mute_hi && mute_lo < col0 + kListenBlock && mute_hi > col0)      // wave-uniform
+                live_mute_block(cur, col0, mute_lo, mute_hi, lane);
+        }
+        const int32_t amp = whole ? 0 : (int32_t)((uint32_t)__builtin_amdgcn_readlane(block_abs_sum(cur), 63) >> 11);
         int ev = 0;                                                 // 1 = record the block, 2 = record it and close
         if (st.mode == 0) {
             st.mode = 1;                                            // ref:303
@@ -266,7 +331,14 @@ __device__ __forceinline__ void live_gate_walk(const LiveArgs& a, Sink& sk, cons
         // whole block in this push only [cl, tail) is new
         const int32_t tail = (int32_t)(((int64_t)cl + len()) & (kListenBlock - 1));
         const int64_t base = (int64_t)nblk * kListenBlock - cl;
-        for (int i = (nblk == 0 ? cl : 0) + lane; i < tail; i += 64) carry[i] = src[base + i];
+        for (int i = (nblk == 0 ? cl : 0) + lane; i < tail; i += 64) {
+            if constexpr (MUTE) {
+                const int64_t col = base + i;
+                carry[i] = col >= mute_lo && col < mute_hi ? (int16_t)0 : src[col];
+            } else {
+                carry[i] = src[base + i];
+            }
+        }
         st.pos += len();
         st.head = sk.head(st);
     }

@@ -1,12 +1,16 @@
 // afsk_live_push.hip -- every live receiver's push (afsk_live_push, afsk_live_push_tap, afsk_live_push_ragged,
-// afsk_live_push_auto, include/afsk_amd.h): one kernel template, one table of its instantiations, one host path.
+// afsk_live_push_auto, afsk_live_push_muted, afsk_live_push_auto_muted, include/afsk_amd.h): one kernel template (and its
+// muted twin), one table of their instantiations, one host path.
 //
 // live_push_kernel<Sink, PER_CHANNEL, RAGGED> builds the sink from its argument struct and runs live_gate_walk
 // (afsk_live.hip) with it.  The three sinks -- LiveStoreSink (afsk_live.hip), LiveStreamSinkT<false> and
 // LiveStreamSinkT<true> (afsk_live_stream.hip; the tapped one: afsk_live_tap.hip) -- times the walk's two flags are the
 // twelve cells of kLivePushCells; nothing else calls live_gate_walk.  A further sink or flag is a further index of the
 // table, not a further copy of the path: the auto-rate receiver's two sinks, LiveAutoSinkT<false> and LiveAutoSinkT<true>
-// (afsk_live_auto.hip), are sink kinds 3 and 4 -- eight more cells, launched by afsk_live_push_auto alone.
+// (afsk_live_auto.hip), are sink kinds 3 and 4 -- eight more cells, launched by afsk_live_push_auto alone.  The muted
+// push (afsk_live_push_muted, afsk_live_push_auto_muted) is form 2 of the table's last index: live_push_mute_kernel<Sink,
+// PER_CHANNEL>, the ragged walk with its MUTE flag and the mute array as a third argument -- a kernel of its own name, ten
+// more cells, so live_push_kernel's instantiations and their names stay what they were.
 //
 // afsk::live_push does what the three C entries have in common, once: the argument checks, the receiver's device, the
 // kernel arguments, the choice of the cell from the receiver's kind and the call's form, the launch and, for a stored
@@ -33,33 +37,53 @@ __global__ __launch_bounds__(256) void live_push_kernel(typename Sink::Args a, L
     live_gate_walk<PER_CHANNEL, RAGGED>(Sink::gate(a), sk, x.thr_start, x.thr_end, x.chunk_lens, x.flush_mask);
 }
 
+// the muted push: the ragged walk that takes columns [lo', hi') of channel c's row as 0, mute = DEVICE int32 [n, 2]
+template <class Sink, bool PER_CHANNEL>
+__global__ __launch_bounds__(256) void live_push_mute_kernel(typename Sink::Args a, LivePushPtrs x, const int32_t* mute) {
+    Sink sk(a);
+    live_gate_walk<PER_CHANNEL, true, true>(Sink::gate(a), sk, x.thr_start, x.thr_end, x.chunk_lens, x.flush_mask, mute);
+}
+
 struct LivePushCell {
-    void (*kernel)();               // live_push_kernel<...>, called as void (*)(Sink::Args, LivePushPtrs)
+    void (*kernel)();               // live_push_kernel<...>, called as void (*)(Sink::Args, LivePushPtrs); a muted cell:
+                                    // live_push_mute_kernel<...>, void (*)(Sink::Args, LivePushPtrs, const int32_t*)
     const char* what;               // for hip_fail
 };
 template <class Sink, bool PER_CHANNEL, bool RAGGED>
 LivePushCell live_push_cell(const char* what) {
     return {reinterpret_cast<void (*)()>(&live_push_kernel<Sink, PER_CHANNEL, RAGGED>), what};
 }
+template <class Sink, bool PER_CHANNEL>
+LivePushCell live_push_mute_cell(const char* what) {
+    return {reinterpret_cast<void (*)()>(&live_push_mute_kernel<Sink, PER_CHANNEL>), what};
+}
 #define AFSK_LIVE_PUSH_CELLS(Sink, name)                                                                \
     {{live_push_cell<Sink, false, false>("launch live_push_kernel<" name ">"),                          \
-      live_push_cell<Sink, false, true>("launch live_push_kernel<" name ", ragged>")},                  \
+      live_push_cell<Sink, false, true>("launch live_push_kernel<" name ", ragged>"),                   \
+      live_push_mute_cell<Sink, false>("launch live_push_mute_kernel<" name ">")},                      \
      {live_push_cell<Sink, true, false>("launch live_push_kernel<" name ", per channel>"),              \
-      live_push_cell<Sink, true, true>("launch live_push_kernel<" name ", per channel, ragged>")}}
+      live_push_cell<Sink, true, true>("launch live_push_kernel<" name ", per channel, ragged>"),       \
+      live_push_mute_cell<Sink, true>("launch live_push_mute_kernel<" name ", per channel>")}}
 enum LiveSinkKind { kLiveStored, kLiveStream, kLiveTapped, kLiveAuto, kLiveAutoTapped };
-// [sink kind][a threshold pair per channel][ragged]
-static const LivePushCell kLivePushCells[5][2][2] = {AFSK_LIVE_PUSH_CELLS(LiveStoreSink, "stored"),
+enum LivePushForm { kLivePlain, kLiveRagged, kLiveMuted };
+// [sink kind][a threshold pair per channel][form: plain, ragged, muted]
+static const LivePushCell kLivePushCells[5][2][3] = {AFSK_LIVE_PUSH_CELLS(LiveStoreSink, "stored"),
                                                      AFSK_LIVE_PUSH_CELLS(LiveStreamSinkT<false>, "streaming"),
                                                      AFSK_LIVE_PUSH_CELLS(LiveStreamSinkT<true>, "tapped"),
                                                      AFSK_LIVE_PUSH_CELLS(LiveAutoSinkT<false>, "auto"),
                                                      AFSK_LIVE_PUSH_CELLS(LiveAutoSinkT<true>, "auto, tapped")};
 #undef AFSK_LIVE_PUSH_CELLS
 
+// mute: the muted cells' third argument (null: a plain or ragged cell)
 template <class Args>
 hipError_t live_push_launch(const LivePushCell& cell, int64_t n, hipStream_t stream, const Args& a,
-                            const LivePushPtrs& x) {
-    hipLaunchKernelGGL(reinterpret_cast<void (*)(Args, LivePushPtrs)>(cell.kernel), dim3((uint32_t)((n + 3) / 4)),
-                       dim3(256), 0, stream, a, x);
+                            const LivePushPtrs& x, const int32_t* mute) {
+    if (mute)
+        hipLaunchKernelGGL(reinterpret_cast<void (*)(Args, LivePushPtrs, const int32_t*)>(cell.kernel),
+                           dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, stream, a, x, mute);
+    else
+        hipLaunchKernelGGL(reinterpret_cast<void (*)(Args, LivePushPtrs)>(cell.kernel), dim3((uint32_t)((n + 3) / 4)),
+                           dim3(256), 0, stream, a, x);
     return hipGetLastError();
 }
 
@@ -84,7 +108,8 @@ struct LiveTapOutputs {
 
 // What a push entry asks for.  `ragged`: the ragged cells, with chunk_lens and flush_mask (device arrays, either may be
 // null).  `tap_required`: the entry is the tapped push (else the tap outputs may be all null: an untapped push).
-// `auto_rate`: the entry is afsk_live_push_auto, with the two per-slot rate outputs.
+// `auto_rate`: the entry is afsk_live_push_auto, with the two per-slot rate outputs.  `muted`: the entry is
+// afsk_live_push_muted or afsk_live_push_auto_muted, a ragged push with d_mute (DEVICE int32 [n, 2], not null).
 struct LivePushCall {
     const int16_t* chunk;
     int64_t chunk_row_stride;
@@ -101,6 +126,8 @@ struct LivePushCall {
     bool auto_rate = false;
     int32_t* out_bit_frames = nullptr;
     int32_t* out_rate_score = nullptr;
+    bool muted = false;
+    const int32_t* mute = nullptr;
 };
 
 // the gate's arguments every receiver has; o_carry: the carry's place in its state
@@ -168,13 +195,22 @@ int live_push(afsk_live* live, const LivePushCall& c) {
     if ((c.chunk_len > 0 && !c.chunk) || c.gate.missing() || o.missing() || (c.tap_required && n_tap != 5) ||
         (c.auto_rate && (!c.out_bit_frames || !c.out_rate_score)))
         return fail(AFSK_E_INVALID_ARG, "null pointer argument");
+    if (c.muted && !c.mute)
+        return fail(AFSK_E_INVALID_ARG, c.auto_rate ? "afsk_live_push_auto_muted: null pointer argument (d_mute)"
+                                                    : "afsk_live_push_muted: null pointer argument (d_mute)");
     const bool is_auto = live->auto_n_cand > 0;
     if (is_auto && !c.auto_rate)
-        return fail(AFSK_E_INVALID_ARG, "an auto-rate receiver (afsk_live_create_stream_auto) is pushed with "
-                                        "afsk_live_push_auto");
+        return fail(AFSK_E_INVALID_ARG, c.muted ? "afsk_live_push_muted: an auto-rate receiver "
+                                                  "(afsk_live_create_stream_auto) is pushed with afsk_live_push_auto_muted"
+                                                : "an auto-rate receiver (afsk_live_create_stream_auto) is pushed with "
+                                                  "afsk_live_push_auto");
     if (!is_auto && c.auto_rate)
-        return fail(AFSK_E_INVALID_ARG, "afsk_live_push_auto needs a receiver of afsk_live_create_stream_auto: this one "
-                                        "is pushed with afsk_live_push, afsk_live_push_tap or afsk_live_push_ragged");
+        return fail(AFSK_E_INVALID_ARG, c.muted ? "afsk_live_push_auto_muted needs a receiver of "
+                                                  "afsk_live_create_stream_auto: this one is pushed with "
+                                                  "afsk_live_push_muted"
+                                                : "afsk_live_push_auto needs a receiver of afsk_live_create_stream_auto: "
+                                                  "this one is pushed with afsk_live_push, afsk_live_push_tap or "
+                                                  "afsk_live_push_ragged");
     const bool streaming = live->max_payload_len >= 0;
     if (streaming && o.margins)
         return fail(AFSK_E_INVALID_ARG, "a streaming live receiver has no margins: out_margins must be NULL");
@@ -191,33 +227,35 @@ int live_push(afsk_live* live, const LivePushCall& c) {
 
     const LiveSinkKind kind = is_auto ? (tapped ? kLiveAutoTapped : kLiveAuto)
                                       : tapped ? kLiveTapped : streaming ? kLiveStream : kLiveStored;
-    const LivePushCell& cell = kLivePushCells[kind][live->per_channel][c.ragged];
+    const LivePushCell& cell =
+        kLivePushCells[kind][live->per_channel][c.muted ? kLiveMuted : c.ragged ? kLiveRagged : kLivePlain];
     LivePushPtrs x{};
     if (live->per_channel) {
         x.thr_start = live->thr_start();
         x.thr_end = live->thr_end();
     }
-    if (c.ragged) {
+    if (c.ragged || c.muted) {
         x.chunk_lens = c.chunk_lens;
         x.flush_mask = c.flush_mask;
     }
     const int64_t n = live->L.n;
+    const int32_t* mute = c.muted ? c.mute : nullptr;
     LiveArgs g{};
     hipError_t e;
     if (kind == kLiveStored) {
         g = live_stored_args(live, c);
-        e = live_push_launch(cell, n, c.stream, g, x);
+        e = live_push_launch(cell, n, c.stream, g, x, mute);
     } else {
         const LiveStreamArgs s = live_stream_args(live, c);
         const LiveTapArgs t{c.tap.bytes, live->tap_cap, c.tap.n, c.tap.len, c.tap.open_start, c.tap.open_nbytes};
         if (is_auto) {
             LiveAutoDetect d{c.out_bit_frames, c.out_rate_score, live->auto_max_score, live->auto_n_cand, {}};
             std::copy(live->auto_cand, live->auto_cand + live->auto_n_cand, d.cand);
-            e = tapped ? live_push_launch(cell, n, c.stream, LiveAutoArgsT<true>{{s, t}, d}, x)
-                       : live_push_launch(cell, n, c.stream, LiveAutoArgsT<false>{s, d}, x);
+            e = tapped ? live_push_launch(cell, n, c.stream, LiveAutoArgsT<true>{{s, t}, d}, x, mute)
+                       : live_push_launch(cell, n, c.stream, LiveAutoArgsT<false>{s, d}, x, mute);
         } else {
-            e = tapped ? live_push_launch(cell, n, c.stream, LiveStreamTapArgs{s, t}, x)
-                       : live_push_launch(cell, n, c.stream, s, x);
+            e = tapped ? live_push_launch(cell, n, c.stream, LiveStreamTapArgs{s, t}, x, mute)
+                       : live_push_launch(cell, n, c.stream, s, x, mute);
         }
     }
     if (e != hipSuccess) return hip_fail(e, cell.what);
@@ -286,6 +324,39 @@ int afsk_live_push_auto(afsk_live* live, const int16_t* chunk, int64_t chunk_row
                                    out_status, out_corrected, out_margins, margin_stride},
                                   {tap_bytes, tap_n, tap_len, open_start, open_nbytes}, false,
                                   (hipStream_t)hip_stream, true, out_bit_frames, out_rate_score});
+}
+
+int afsk_live_push_muted(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                         const int32_t* d_chunk_lens_or_null, int32_t flush, const uint8_t* d_flush_mask_or_null,
+                         const int32_t* d_mute, int32_t* out_n_closed, int64_t* out_burst_start, int32_t* out_burst_len,
+                         int32_t* out_flags, uint8_t* out_bytes, int32_t out_stride, int32_t* out_nbytes,
+                         int32_t* out_nbits, int32_t* out_clock_idx, int32_t* out_term_frame, int32_t* out_status,
+                         int32_t* out_corrected, int32_t* out_margins, int32_t margin_stride, uint8_t* tap_bytes,
+                         int32_t* tap_n, int32_t* tap_len, int64_t* open_start, int32_t* open_nbytes, void* hip_stream) {
+    return afsk::live_push(live, {chunk, chunk_row_stride, chunk_len, flush, true, d_chunk_lens_or_null,
+                                  d_flush_mask_or_null,
+                                  {out_n_closed, out_burst_start, out_burst_len, out_flags},
+                                  {out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame,
+                                   out_status, out_corrected, out_margins, margin_stride},
+                                  {tap_bytes, tap_n, tap_len, open_start, open_nbytes}, false,
+                                  (hipStream_t)hip_stream, false, nullptr, nullptr, true, d_mute});
+}
+
+int afsk_live_push_auto_muted(afsk_live* live, const int16_t* chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                              const int32_t* d_chunk_lens_or_null, int32_t flush, const uint8_t* d_flush_mask_or_null,
+                              const int32_t* d_mute, int32_t* out_n_closed, int64_t* out_burst_start,
+                              int32_t* out_burst_len, int32_t* out_flags, uint8_t* out_bytes, int32_t out_stride,
+                              int32_t* out_nbytes, int32_t* out_nbits, int32_t* out_clock_idx, int32_t* out_term_frame,
+                              int32_t* out_status, int32_t* out_corrected, int32_t* out_margins, int32_t margin_stride,
+                              uint8_t* tap_bytes, int32_t* tap_n, int32_t* tap_len, int64_t* open_start,
+                              int32_t* open_nbytes, int32_t* out_bit_frames, int32_t* out_rate_score, void* hip_stream) {
+    return afsk::live_push(live, {chunk, chunk_row_stride, chunk_len, flush, true, d_chunk_lens_or_null,
+                                  d_flush_mask_or_null,
+                                  {out_n_closed, out_burst_start, out_burst_len, out_flags},
+                                  {out_bytes, out_stride, out_nbytes, out_nbits, out_clock_idx, out_term_frame,
+                                   out_status, out_corrected, out_margins, margin_stride},
+                                  {tap_bytes, tap_n, tap_len, open_start, open_nbytes}, false,
+                                  (hipStream_t)hip_stream, true, out_bit_frames, out_rate_score, true, d_mute});
 }
 
 }  // extern "C"

@@ -25,6 +25,11 @@
 // later (tx_hold_delta) without writing state; live_tx_commit_hold_kernel derives the same delta, writes the shifted
 // starts into the ring, the channel's end, w and deferred[c], and then commits as the other pulls do.
 //
+// A csma pull (afsk_live_tx_pull_csma) is the hold pull with p-persistence: the same tile launch (it only reads w), and
+// live_tx_commit_csma_kernel in place of the hold commit -- a held channel's wait becomes holdoff + slot * G with G drawn
+// from a counter hash (the draw counter k in TxChan::pad[1]), and on_air[c] reports the columns of the pull that carry
+// the channel's tones.
+//
 // A mixed transmitter (afsk_live_tx_create_mixed) keeps each channel's bit_frames and training symbols in a TxGeom
 // array past the uniform layout; submit and live_tx_tile_kernel_mixed read them per channel, and the tile kernel picks
 // the small- or large-q tone code per wave (a wave renders tiles of one channel, so the branch is wave-uniform).
@@ -55,7 +60,8 @@ struct TxChan {             // 32 bytes per channel
     int32_t head;           // ring entry of the oldest message not yet fully emitted
     int32_t count;          // messages queued or on air
     int32_t pad[2];         // pad[0]: the hold pull's wait counter w (afsk_live_tx_pull_hold; 0 after create and reset,
-                            // neither read nor written by the plain and ragged pulls); pad[1]: spare
+                            // neither read nor written by the plain and ragged pulls); pad[1]: the csma pull's draw
+                            // counter k (afsk_live_tx_pull_csma; 0 after create and reset, touched by no other pull)
 };
 static_assert(sizeof(TxChan) == 32, "TxChan layout");
 
@@ -627,6 +633,77 @@ __global__ __launch_bounds__(256) void live_tx_commit_hold_kernel(TxChan* chan, 
     live_tx_commit(chan, desc, c, depth, T, pending);
 }
 
+// The csma pull's draw (afsk_live_tx_pull_csma): the slots a released channel waits past its holdoff, G = the first j in
+// 0 ... 254 whose draw (hash32(base ^ j) & 255) is <= persist, 255 when there is none; base is keyed by the seed, the
+// channel and the channel's draw counter k, so every held pull draws afresh and no two channels share a sequence.
+__device__ __forceinline__ int32_t tx_csma_slots(uint32_t seed, int c, uint32_t k, int32_t persist) {
+    const uint32_t base = hash32(hash32(seed ^ hash32((uint32_t)c + 0x9e3779b9U)) ^ k);
+    int32_t g = 0;
+    while (g < 255 && (int32_t)(hash32(base ^ (uint32_t)g) & 255u) > persist) g++;
+    return g;
+}
+
+// live_tx_commit_hold_kernel with p-persistence (afsk_live_tx_pull_csma): a held channel's wait becomes holdoff + slot * G
+// (tx_csma_slots) and its draw counter k (TxChan::pad[1]) goes up by one; a channel that is not held keeps k.  It also
+// writes on_air[c] = (lo, hi), the hull in columns of this pull of the tone samples the tile kernel rendered for the
+// channel: read from the ring after the shift and before live_tx_commit retires anything, so it sees the starts the
+// tile kernel rendered with.  The ring is in stream order, so lo comes from the first message whose tones meet the pull
+// and hi from the last.
+__global__ __launch_bounds__(256) void live_tx_commit_csma_kernel(TxChan* chan, TxDesc* desc, int32_t n, int32_t depth,
+                                                                  int32_t T, const int32_t* lens, const int32_t* hold,
+                                                                  int32_t holdoff, int32_t persist, int32_t slot,
+                                                                  uint32_t seed, int32_t* pending, int64_t* deferred,
+                                                                  int32_t* on_air) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    if (lens) {
+        const int32_t l = lens[c];
+        T = l < 0 ? 0 : (l < T ? l : T);
+    }
+    TxChan st = chan[c];
+    const bool held = hold && hold[c] != 0;
+    const int64_t earliest = tx_hold_earliest(st, T, held);
+    TxDesc* ring = desc + (int64_t)c * depth;
+    int64_t delta = 0;
+    bool shifting = false;                                             // e is u or behind it
+    int32_t lo = 0, hi = 0;
+    for (int32_t i = 0, e = st.head; i < st.count; i++, e = (e + 1 == depth ? 0 : e + 1)) {
+        TxDesc d = ring[e];
+        if (!shifting && d.start >= st.pos) {                          // e is u
+            shifting = true;
+            delta = tx_hold_delta(earliest, d.start);
+        }
+        if (shifting && delta > 0) {
+            d.start += delta;
+            ring[e].start = d.start;
+        }
+        if (d.start >= st.pos + T) {
+            if (delta == 0) break;                                     // nothing behind it moves or meets the pull
+            continue;
+        }
+        const int64_t t1 = d.start + d.n_samples - AFSK_TAIL_SILENCE;  // the end of its tones
+        if (t1 <= st.pos) continue;                                    // in its silent tail
+        const int32_t a0 = (int32_t)(d.start > st.pos ? d.start - st.pos : 0);
+        const int32_t a1 = (int32_t)(t1 < st.pos + T ? t1 - st.pos : T);
+        if (hi == 0) lo = a0;                                          // (a1 > a0 >= 0: hi == 0 means none met yet)
+        hi = a1;
+    }
+    st.end += delta;                                                   // (delta > 0: u is queued, so end >= u's end)
+    const int32_t w = st.pad[0];
+    if (held) {
+        const uint32_t k = (uint32_t)st.pad[1];
+        st.pad[0] = holdoff + slot * tx_csma_slots(seed, c, k, persist);   // < 2^31 by the entry's argument bounds
+        st.pad[1] = (int32_t)(k + 1u);
+    } else {
+        st.pad[0] = w > T ? w - T : 0;
+    }
+    chan[c] = st;
+    deferred[c] = delta;
+    on_air[2 * c] = lo;
+    on_air[2 * c + 1] = hi;
+    live_tx_commit(chan, desc, c, depth, T, pending);
+}
+
 __global__ __launch_bounds__(256) void live_tx_reset_kernel(TxChan* chan, const uint8_t* mask, int32_t* pending,
                                                             int32_t n) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -864,16 +941,28 @@ struct TxHold {
     const int32_t* hold;        // DEVICE int32 [n] or NULL (nobody held)
     int32_t holdoff;
     int64_t* deferred;
+    bool csma = false;          // afsk_live_tx_pull_csma: the four below, and the csma commit
+    int32_t persist = 255, slot = 0;
+    uint32_t seed = 0;
+    int32_t* on_air = nullptr;
 };
 
 // afsk_live_tx_pull, afsk_live_tx_pull_ragged (`ragged`: the ragged kernels, lens a DEVICE array or NULL) and
-// afsk_live_tx_pull_hold (`hd`: the hold kernels, which are ragged ones)
+// afsk_live_tx_pull_hold (`hd`: the hold kernels, which are ragged ones) and afsk_live_tx_pull_csma (`hd->csma`: the hold
+// tile kernels and the csma commit)
 int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples, bool ragged, const int32_t* lens,
             int32_t* out_pending, void* hip_stream, const TxHold* hd = nullptr) {
     if (!tx) return afsk::fail(AFSK_E_INVALID_ARG, "null live transmitter");
     if (hd && (hd->holdoff < 0 || hd->holdoff > AFSK_MAX_STREAM_LEN))
         return afsk::fail(AFSK_E_INVALID_ARG, "holdoff must lie in 0 ... AFSK_MAX_STREAM_LEN");
     if (hd && !hd->deferred) return afsk::fail(AFSK_E_INVALID_ARG, "null pointer argument (out_deferred)");
+    if (hd && hd->csma) {
+        if (hd->persist < 0 || hd->persist > 255)
+            return afsk::fail(AFSK_E_INVALID_ARG, "afsk_live_tx_pull_csma: persist must lie in 0 ... 255");
+        if (hd->slot < 0 || hd->slot > (1 << 20))
+            return afsk::fail(AFSK_E_INVALID_ARG, "afsk_live_tx_pull_csma: slot must lie in 0 ... 2^20");
+        if (!hd->on_air) return afsk::fail(AFSK_E_INVALID_ARG, "afsk_live_tx_pull_csma: null pointer argument (out_on_air)");
+    }
     if (n_samples < 0 || out_row_stride < 0) return afsk::fail(AFSK_E_INVALID_ARG, "negative size");
     if (n_samples > AFSK_MAX_STREAM_LEN) return afsk::fail(AFSK_E_INVALID_ARG, "n_samples exceeds AFSK_MAX_STREAM_LEN");
     const afsk::TxLayout& L = tx->L;
@@ -940,7 +1029,12 @@ int tx_pull(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_sa
         e = hipGetLastError();
         if (e != hipSuccess) return afsk::hip_fail(e, "launch live_tx_tile_kernel");
     }
-    if (hd)
+    if (hd && hd->csma)
+        hipLaunchKernelGGL(afsk::live_tx_commit_csma_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st,
+                           chan, reinterpret_cast<afsk::TxDesc*>(d + L.o_desc), (int32_t)L.n, (int32_t)L.depth,
+                           n_samples, lens, hd->hold, hd->holdoff, hd->persist, hd->slot, hd->seed, out_pending,
+                           hd->deferred, hd->on_air);
+    else if (hd)
         hipLaunchKernelGGL(afsk::live_tx_commit_hold_kernel, dim3((uint32_t)((L.n + 255) / 256)), dim3(256), 0, st,
                            chan, reinterpret_cast<afsk::TxDesc*>(d + L.o_desc), (int32_t)L.n, (int32_t)L.depth,
                            n_samples, lens, hd->hold, hd->holdoff, out_pending, hd->deferred);
@@ -970,6 +1064,14 @@ int afsk_live_tx_pull_hold(afsk_live_tx* tx, int16_t* out, int64_t out_row_strid
                            const int32_t* d_lens_or_null, const int32_t* d_hold_or_null, int32_t holdoff,
                            int32_t* out_pending, int64_t* out_deferred, void* hip_stream) {
     const TxHold hd{d_hold_or_null, holdoff, out_deferred};
+    return tx_pull(tx, out, out_row_stride, n_samples, true, d_lens_or_null, out_pending, hip_stream, &hd);
+}
+
+int afsk_live_tx_pull_csma(afsk_live_tx* tx, int16_t* out, int64_t out_row_stride, int32_t n_samples,
+                           const int32_t* d_lens_or_null, const int32_t* d_hold_or_null, int32_t holdoff,
+                           int32_t persist, int32_t slot, uint32_t seed, int32_t* out_pending, int64_t* out_deferred,
+                           int32_t* out_on_air, void* hip_stream) {
+    const TxHold hd{d_hold_or_null, holdoff, out_deferred, true, persist, slot, seed, out_on_air};
     return tx_pull(tx, out, out_row_stride, n_samples, true, d_lens_or_null, out_pending, hip_stream, &hd);
 }
 

@@ -148,6 +148,40 @@ def _device_hold(hold, n_channels: int, dev):
     return torch.from_numpy(np.ascontiguousarray((v != 0).astype(np.int32))).to(dev), True
 
 
+def _device_mute(mute, n_channels: int, T: int, dev):
+    """The ``mute`` of a muted push as ``(int32 [n_channels, 2] tensor on dev, uploaded)``: an int32 CUDA tensor on ``dev``
+    is used in place (no copy, no synchronisation: e.g. ``LiveTransmitter.on_air``); a host sequence of [n_channels, 2]
+    column ranges is uploaded with one copy; an [n_channels] bool mask mutes the whole push (0, T) where it is true -- on
+    the host (uploaded) or a CUDA bool tensor on ``dev`` (turned into ranges there, no synchronisation; counted as
+    uploaded: a new tensor of this call)."""
+    torch = batch._torch()
+    if isinstance(mute, torch.Tensor) and mute.is_cuda and mute.dtype == torch.bool:
+        if mute.device != dev:
+            raise ValueError(f"mute is on {mute.device}, the receiver on {dev}")
+        if tuple(mute.shape) != (n_channels,):
+            raise ValueError(f"a bool mute mask must be [n_channels={n_channels}], got {list(mute.shape)}")
+        hi = torch.where(mute, T, 0).to(torch.int32)
+        return torch.stack([torch.zeros_like(hi), hi], dim=1).contiguous(), True
+    if isinstance(mute, torch.Tensor) and mute.is_cuda:
+        if mute.dtype != torch.int32:
+            raise ValueError("a CUDA mute must hold int32 column ranges (e.g. LiveTransmitter.on_air) or be a bool "
+                             f"mask, got {mute.dtype}")
+        if mute.device != dev:
+            raise ValueError(f"mute is on {mute.device}, the receiver on {dev}")
+        if tuple(mute.shape) != (n_channels, 2) or not mute.is_contiguous():
+            raise ValueError(f"mute must be a contiguous [n_channels={n_channels}, 2], got {list(mute.shape)}")
+        return mute, False
+    v = mute.numpy() if isinstance(mute, torch.Tensor) else np.asarray(mute)
+    if v.dtype == np.bool_ and v.shape == (n_channels,):
+        v = np.stack([np.zeros(n_channels, np.int64), np.where(v, T, 0)], axis=1)
+    elif v.dtype.kind not in "iu":
+        raise ValueError(f"mute must hold integer column ranges or be an [n_channels] bool mask, got {v.dtype}")
+    if v.shape != (n_channels, 2):
+        raise ValueError(f"mute must be [n_channels={n_channels}, 2] or an [n_channels] bool mask, got {list(v.shape)}")
+    v = np.clip(v.astype(np.int64), -2 ** 31, 2 ** 31 - 1)           # (the kernel clamps to 0 ... len anyway)
+    return torch.from_numpy(np.ascontiguousarray(v, np.int32)).to(dev), True
+
+
 def _flush_mask(flush, n_channels: int, dev):
     """A per-channel ``flush`` ([n_channels] bool / uint8, host or device) as ``(uint8 tensor on dev, the caller's own
     tensor)`` through ``_device_mask``; a tensor or array of another dtype is a TypeError."""
@@ -963,7 +997,7 @@ class LiveReceiver(batch._NativePlan):
         return chunk, False
 
     def push(self, chunk, stream=None, out: LiveResult | None = None, flush=False, lengths=None,
-             events: LiveEvents | None = None, segments: LiveSegments | None = None) -> LiveResult:
+             events: LiveEvents | None = None, segments: LiveSegments | None = None, mute=None) -> LiveResult:
         """Append ``chunk`` ([n_channels, T] int16: a CUDA tensor with contiguous rows and any row stride -- e.g. a
         column window of a [channels, time] buffer, no copy -- or a numpy array, uploaded with one copy; None = T 0)
         to every channel's stream and return the bursts that closed, demodulated.  ``flush``: then end every stream
@@ -983,7 +1017,16 @@ class LiveReceiver(batch._NativePlan):
 
         ``segments`` (``alloc_segments``; a progressive receiver only, ValueError otherwise): also ``pack_tap`` the
         result into it, behind the push (and behind the event pack) on the same stream; the returned result then
-        carries it as ``.segments``.  Without it the call launches and sets nothing more."""
+        carries it as ``.segments``.  Without it the call launches and sets nothing more.
+
+        A muted push (``afsk_live_push_muted`` / ``afsk_live_push_auto_muted``): with ``mute`` ([n_channels, 2] column
+        ranges (lo, hi) of this push -- an int32 CUDA tensor on the receiver's device such as
+        ``LiveTransmitter.on_air``, used in place and read when the kernel runs; or a host sequence, uploaded with one
+        copy; or an [n_channels] bool mask, host or CUDA: the whole push where true) channel c takes columns ``[lo, hi)`` of its
+        row, clamped to its length, as zeros: the push gives what it would give on a chunk with those columns zeroed,
+        bit for bit, and a muted sample that is carried stays muted.  A half-duplex station passes its own
+        transmitter's ``on_air`` here so that it does not hear itself.  Works on every receiver kind and with every
+        other argument; without ``mute`` the push launches what it launched before."""
         torch = batch._torch()
         if segments is not None and not self.progressive:
             raise ValueError("segments= needs a progressive receiver (LiveReceiver(..., progressive=True)): only its "
@@ -1000,6 +1043,10 @@ class LiveReceiver(batch._NativePlan):
             own = own and mine
             flush = False
         ragged = lens is not None or mask is not None
+        ranges = None
+        if mute is not None:
+            ranges, up = _device_mute(mute, self.n_channels, int(chunk.shape[1]), dev)
+            own = own and not up
         fresh = out is None
         if fresh:
             out = self.alloc_result()
@@ -1023,7 +1070,7 @@ class LiveReceiver(batch._NativePlan):
             if fresh or uploaded or not own:
                 batch._order_after_current(stream, dev)
             if stream is not None:                   # what this call uploaded is used on `stream`
-                for t in ([chunk] if uploaded else []) + ([] if own else [x for x in (lens, mask) if x is not None]):
+                for t in ([chunk] if uploaded else []) + ([] if own else [x for x in (lens, mask, ranges) if x is not None]):
                     t.record_stream(stream)
             head = (self.handle, chunk.data_ptr() if T else None, int(chunk.stride(0)) if T else 0, T)
             outs = (out.n_closed.data_ptr(), out.burst_start.data_ptr(), out.burst_len.data_ptr(), out.flags.data_ptr(),
@@ -1034,7 +1081,13 @@ class LiveReceiver(batch._NativePlan):
                 t = out.tap
                 taps = (t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
                         t.open_nbytes.data_ptr())
-            if self.auto:
+            if ranges is not None:
+                rates = (out.bit_frames.data_ptr(), out.rate_score.data_ptr()) if self.auto else ()
+                entry = _native.lib().afsk_live_push_auto_muted if self.auto else _native.lib().afsk_live_push_muted
+                _native.check(entry(*head, None if lens is None else lens.data_ptr(), int(bool(flush)),
+                                    None if mask is None else mask.data_ptr(), ranges.data_ptr(), *outs, *taps, *rates,
+                                    batch._stream_ptr(stream, dev)))
+            elif self.auto:
                 _native.check(_native.lib().afsk_live_push_auto(
                     *head, None if lens is None else lens.data_ptr(), int(bool(flush)),
                     None if mask is None else mask.data_ptr(), *outs, *taps, out.bit_frames.data_ptr(),
@@ -1049,7 +1102,7 @@ class LiveReceiver(batch._NativePlan):
             else:
                 _native.check(_native.lib().afsk_live_push(*head, int(bool(flush)), *outs,
                                                            batch._stream_ptr(stream, dev)))
-        out._chunk_keepalive = (chunk, lens, mask)  # type: ignore[attr-defined]
+        out._chunk_keepalive = (chunk, lens, mask, ranges)  # type: ignore[attr-defined]
         if events is not None:
             out.events = self.pack(out, out=events, stream=stream)  # type: ignore[attr-defined]
         if segments is not None:
@@ -1057,13 +1110,13 @@ class LiveReceiver(batch._NativePlan):
         return out
 
     def flush(self, chunk=None, stream=None, out: LiveResult | None = None, mask=None, lengths=None,
-              events: LiveEvents | None = None, segments: LiveSegments | None = None) -> LiveResult:
+              events: LiveEvents | None = None, segments: LiveSegments | None = None, mute=None) -> LiveResult:
         """``push(chunk, flush=True)``: end every channel's stream.  A burst still recording is reported (whole blocks,
         ``LIVE_OPEN_END``), the partial block is dropped, and the next push starts new streams at sample 0.  ``mask``
-        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths``, ``events`` and
-        ``segments``: as ``push``."""
+        ([n_channels] bool / uint8, host or device): only the channels where it is true; ``lengths``, ``events``,
+        ``segments`` and ``mute``: as ``push``."""
         return self.push(chunk, stream=stream, out=out, flush=True if mask is None else mask, lengths=lengths,
-                         events=events, segments=segments)
+                         events=events, segments=segments, mute=mute)
 
     def reset(self, mask=None, stream=None) -> None:
         """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /
@@ -1257,6 +1310,8 @@ class LiveTransmitter(batch._NativePlan):
         self.pending = torch.zeros(self.n_channels, dtype=torch.int32, device=self.device)
         # samples the last hold pull (pull(hold=)) moved every channel's waiting messages by
         self.deferred = torch.zeros(self.n_channels, dtype=torch.int64, device=self.device)
+        # the columns (lo, hi) of the last csma pull (pull(hold=, persist=, slot=, seed=)) that carry every channel's tones
+        self.on_air = torch.zeros((self.n_channels, 2), dtype=torch.int32, device=self.device)
 
     @classmethod
     def from_transmitters(cls, transmitters, **capacities) -> "LiveTransmitter":
@@ -1509,7 +1564,8 @@ class LiveTransmitter(batch._NativePlan):
         out._keepalive = (buf, cmap, heard)  # type: ignore[attr-defined]
         return out
 
-    def pull(self, T: int, out=None, stream=None, lengths=None, hold=None, holdoff: int = 0):
+    def pull(self, T: int, out=None, stream=None, lengths=None, hold=None, holdoff: int = 0, persist=None,
+             slot=None, seed=None):
         """Write samples ``[pos, pos + T)`` of every channel into ``out`` ([n_channels, >= T] int16 CUDA tensor with
         contiguous rows and any row stride -- e.g. a column window of a [channels, time] buffer; None: a new [n, T]
         tensor) and return ``out[:, :T]``.  Nothing of ``out`` outside those T columns is written.  Then every
@@ -1531,7 +1587,18 @@ class LiveTransmitter(batch._NativePlan):
         ``holdoff=0`` on a transmitter that was never held is the plain (or ragged) pull bit for bit.  ``hold=None``
         is today's plain or ragged pull, which knows nothing of the wait; ``holdoff`` without ``hold`` is a
         ValueError.  A caller whose receiver channels map to other transmitter channels gathers ``busy`` first
-        (``busy[rx_of_tx]``)."""
+        (``busy[rx_of_tx]``).
+
+        A csma pull (``afsk_live_tx_pull_csma``, p-persistence): any of ``persist`` (0 ... 255; None with one of the
+        others: 255), ``slot`` (samples, 0 ... 2^20; None: 0) and ``seed`` (uint32; None: 0) that is given -- whatever
+        its value, ``seed=0`` included -- makes the hold pull draw a backoff for every
+        held channel -- after its last held pull it waits ``holdoff + slot * G`` samples, G geometric with a slot taken
+        with probability ``(persist + 1) / 256`` (the KISS rule), drawn from a hash of ``seed``, the channel and the
+        channel's draw count, so two stations with different seeds that heard the same burst do not key up together.
+        ``persist=255`` is the hold pull bit for bit.  ``on_air`` (int32 [n_channels, 2], a fixed address like
+        ``deferred``) then holds the columns ``[lo, hi)`` of this pull that carry each channel's tones ((0, 0): none):
+        what ``LiveReceiver.push(mute=)`` of the same tick takes so that a station does not hear itself.  They need
+        ``hold=`` as ``holdoff`` does; without them the pull launches what it launched before."""
         torch = batch._torch()
         T = int(T)
         if T < 0:
@@ -1543,6 +1610,17 @@ class LiveTransmitter(batch._NativePlan):
             raise ValueError("holdoff needs hold= (hold=False: nobody held, the wait still counts down)")
         if not 0 <= holdoff <= _native.MAX_STREAM_LEN:
             raise ValueError(f"holdoff = {holdoff} must lie in 0 ... AFSK_MAX_STREAM_LEN")
+        csma = persist is not None or slot is not None or seed is not None
+        persist = 255 if persist is None else int(persist)
+        slot, seed = 0 if slot is None else int(slot), 0 if seed is None else int(seed)
+        if csma and hold is None:
+            raise ValueError("persist / slot / seed need hold= (hold=False: nobody held, nobody draws)")
+        if not 0 <= persist <= 255:
+            raise ValueError(f"persist = {persist} must lie in 0 ... 255")
+        if not 0 <= slot <= 1 << 20:
+            raise ValueError(f"slot = {slot} must lie in 0 ... 2^20")
+        if not 0 <= seed < 1 << 32:
+            raise ValueError(f"seed = {seed} must be a uint32")
         dev = self.device
         fresh = out is None
         lens, lens_up = (None, False) if lengths is None else _device_lengths(lengths, self.n_channels, dev,
@@ -1562,7 +1640,13 @@ class LiveTransmitter(batch._NativePlan):
                 lens.record_stream(stream)
             if held_up and stream is not None:
                 held.record_stream(stream)
-            if hold is not None:
+            if csma:
+                _native.check(_native.lib().afsk_live_tx_pull_csma(
+                    self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T,
+                    None if lens is None else lens.data_ptr(), None if held is None else held.data_ptr(), holdoff,
+                    persist, slot, seed, self.pending.data_ptr(), self.deferred.data_ptr(), self.on_air.data_ptr(),
+                    batch._stream_ptr(stream, dev)))
+            elif hold is not None:
                 _native.check(_native.lib().afsk_live_tx_pull_hold(
                     self.handle, out.data_ptr() if T else None, int(out.stride(0)) if T else 0, T,
                     None if lens is None else lens.data_ptr(), None if held is None else held.data_ptr(), holdoff,

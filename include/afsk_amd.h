@@ -1179,14 +1179,87 @@ extern int afsk_live_tx_submit_events_rated(afsk_live_tx *tx, const void *events
  *                          neither read nor write w, and may alternate with hold pulls.  Works for transmitters of every
  *                          kind (one geometry, mixed, rated).  Two launches in order on hip_stream (one when n_samples
  *                          is 0), capturable into a graph.
- * Not part of the rule: p-persistence or random backoff (every released channel starts after exactly its wait), and
- * muting a receiver channel while its own transmitter is on air.
+ * Not part of this rule: random backoff (every released channel starts after exactly its wait) and muting a receiver
+ * channel while its own transmitter is on air -- afsk_live_tx_pull_csma and afsk_live_push_muted below.
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_TX_HOLD_SIGNATURES.)
  */
 extern int afsk_live_busy(afsk_live *live, int32_t *d_out_busy, void *hip_stream);
 extern int afsk_live_tx_pull_hold(afsk_live_tx *tx, int16_t *out, int64_t out_row_stride, int32_t n_samples,
                                   const int32_t *d_lens_or_null, const int32_t *d_hold_or_null, int32_t holdoff,
                                   int32_t *out_pending, int64_t *out_deferred, void *hip_stream);
+
+/*
+ * Half-duplex stations (added after ABI version 2; the version is unchanged): what carrier sense lacks to put a station
+ * on a shared channel.  Two stations that heard the same burst are released by the same block and would key up on the
+ * same sample, again on every retry: the csma pull spreads them with the KISS persistence rule.  A station whose own
+ * output reaches its input would hold itself and, with afsk_live_tx_submit_events, repeat itself: the muted push does
+ * not hear the columns it is told.  All of it is integer and sample-exact, and
+ *   push_muted(mute = on_air) -> busy -> submit_events -> pull_csma(hold = busy)
+ * stays one captured graph.
+ *
+ *  afsk_live_tx_pull_csma  afsk_live_tx_pull_hold (its arguments, its checks) with persist (0 ... 255, else
+ *                          AFSK_E_INVALID_ARG), slot (samples, 0 ... 2^20, else AFSK_E_INVALID_ARG), seed (any uint32)
+ *                          and out_on_air (DEVICE int32 [n_channels, 2], not NULL).  Steps 1-4 of the hold rule are
+ *                          unchanged; with k the channel's draw counter (int32 state, 0 after create and reset) step 5
+ *                          becomes
+ *                            5. not held: w' = max(0, w - L), k' = k.
+ *                               held:     with hash32(x) on uint32:  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *                                         x *= 0x846ca68b; x ^= x >> 16 (the noise generator's hash),
+ *                                           base = hash32(hash32(seed ^ hash32((uint32)c + 0x9e3779b9)) ^ (uint32)k),
+ *                                           G = the smallest j in 0 ... 254 with (hash32(base ^ j) & 255) <= persist,
+ *                                               255 when there is none,
+ *                                         w' = holdoff + slot * G (below 2^31 by the bounds above), k' = k + 1 (uint32
+ *                                         wrap-around).
+ *                          So a released channel waits its holdoff plus a geometric number of slots, each taken with
+ *                          probability (persist + 1) / 256: KISS p-persistence with the draws made at release; when the
+ *                          carrier comes back, the next held pull draws again.  With persist = 255 G is 0: every sample,
+ *                          out_pending and out_deferred are afsk_live_tx_pull_hold's bit for bit.  afsk_live_tx_pull,
+ *                          _pull_ragged and _pull_hold neither read nor write k, and may alternate with this entry.
+ *                          out_on_air[c] = (lo, hi): the hull, in columns of this pull, of the tone samples the pull
+ *                          rendered for channel c -- over the channel's messages after step 3, each contributing
+ *                          [start, start + n_samples - AFSK_TAIL_SILENCE) intersected with [pos, pos + L), relative to
+ *                          pos; the silent tail is not on air; (0, 0) when there is no tone sample or L = 0.  Works for
+ *                          transmitters of every kind.  Two launches in order on hip_stream (one when n_samples is 0):
+ *                          the hold pull's tile kernel, which only reads w, and a commit kernel of its own.
+ *  afsk_live_push_muted    afsk_live_push_ragged (its arguments, its checks, its outputs) with d_mute (DEVICE int32
+ *                          [n_channels, 2], not NULL, read when the kernel runs) behind d_flush_mask_or_null.  Channel c
+ *                          appends len_c samples as in the ragged push; with lo' = clamp(mute[c][0], 0, len_c) and hi' =
+ *                          clamp(mute[c][1], lo', len_c), columns [lo', hi') of its row count as 0 wherever the push uses
+ *                          them -- a block's amplitude, what is recorded or demodulated, and the partial block carried
+ *                          to the next push (a muted sample that is carried is 0 in the next push too).  No column at
+ *                          or beyond len_c is read.  Every output and the receiver's state equal, bit for bit, those of
+ *                          afsk_live_push_ragged on a chunk whose columns [lo', hi') were zeroed.  For a receiver of any
+ *                          kind but the auto-rate one; one launch (plus the stored receiver's demodulator launches), and
+ *                          may alternate with the other pushes.  out_on_air of a pull of the same length is such an
+ *                          array.
+ *  afsk_live_push_auto_muted  the same for afsk_live_push_auto and a receiver of afsk_live_create_stream_auto (d_mute
+ *                          again behind d_flush_mask_or_null).
+ * Not part of the rule: persist / slot per channel; a draw for a message submitted to a channel that is clear and idle
+ * (it starts at once); muting by anything but one column range per channel and push.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_CSMA_SIGNATURES.)
+ */
+extern int afsk_live_tx_pull_csma(afsk_live_tx *tx, int16_t *out, int64_t out_row_stride, int32_t n_samples,
+                                  const int32_t *d_lens_or_null, const int32_t *d_hold_or_null, int32_t holdoff,
+                                  int32_t persist, int32_t slot, uint32_t seed, int32_t *out_pending,
+                                  int64_t *out_deferred, int32_t *out_on_air, void *hip_stream);
+extern int afsk_live_push_muted(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                                const int32_t *d_chunk_lens_or_null, int32_t flush, const uint8_t *d_flush_mask_or_null,
+                                const int32_t *d_mute, int32_t *out_n_closed, int64_t *out_burst_start,
+                                int32_t *out_burst_len, int32_t *out_flags, uint8_t *out_bytes, int32_t out_stride,
+                                int32_t *out_nbytes, int32_t *out_nbits, int32_t *out_clock_idx, int32_t *out_term_frame,
+                                int32_t *out_status, int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride,
+                                uint8_t *tap_bytes, int32_t *tap_n, int32_t *tap_len, int64_t *open_start,
+                                int32_t *open_nbytes, void *hip_stream);
+extern int afsk_live_push_auto_muted(afsk_live *live, const int16_t *chunk, int64_t chunk_row_stride, int32_t chunk_len,
+                                     const int32_t *d_chunk_lens_or_null, int32_t flush,
+                                     const uint8_t *d_flush_mask_or_null, const int32_t *d_mute, int32_t *out_n_closed,
+                                     int64_t *out_burst_start, int32_t *out_burst_len, int32_t *out_flags,
+                                     uint8_t *out_bytes, int32_t out_stride, int32_t *out_nbytes, int32_t *out_nbits,
+                                     int32_t *out_clock_idx, int32_t *out_term_frame, int32_t *out_status,
+                                     int32_t *out_corrected, int32_t *out_margins, int32_t margin_stride,
+                                     uint8_t *tap_bytes, int32_t *tap_n, int32_t *tap_len, int64_t *open_start,
+                                     int32_t *open_nbytes, int32_t *out_bit_frames, int32_t *out_rate_score,
+                                     void *hip_stream);
 
 /*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
