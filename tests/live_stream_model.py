@@ -15,17 +15,23 @@ SYNC = 4096
 H = ((1, 0, 1, 0, 1, 0, 1), (0, 1, 1, 0, 0, 1, 1), (0, 0, 0, 1, 1, 1, 1))
 
 
-def symbol(x, bf, amp_end):
-    """(decision, loud) of one symbol's bf samples: the quarter sums of split_segment_rt_kernel."""
-    x = np.asarray(x, np.int64)
+def symbols(x, bf, amp_end):
+    """(decisions, loud flags) of the rows of x ([n, bf] samples, one symbol each): the quarter sums of
+    split_segment_rt_kernel."""
+    x = np.asarray(x, np.int64).reshape(-1, bf)
     q = bf // 4
-    h = np.where(x > 512, 0, np.where(x < -512, 65535, 32767))
-    hq = [int(h[i * q:(i + 1) * q].sum()) for i in range(4)]
+    h = np.where(x > 512, 0, np.where(x < -512, 65535, 32767)).reshape(-1, 4, q).sum(axis=2)
     full = 65535 * q
-    md = (2 * full + hq[0] + hq[2] - hq[1] - hq[3]) // bf
-    sd = (2 * full + hq[0] + hq[1] - hq[2] - hq[3]) // bf
+    md = (2 * full + h[:, 0] + h[:, 2] - h[:, 1] - h[:, 3]) // bf
+    sd = (2 * full + h[:, 0] + h[:, 1] - h[:, 2] - h[:, 3]) // bf
     thr = min(max(amp_end, 0), 40000) * bf
-    return int(md < sd), int(np.abs(x).sum()) >= thr
+    return (md < sd).astype(int).tolist(), (np.abs(x).sum(axis=1) >= thr).tolist()
+
+
+def symbol(x, bf, amp_end):
+    """(decision, loud) of one symbol's bf samples."""
+    d, loud = symbols(x, bf, amp_end)
+    return d[0], loud[0]
 
 
 def hamming(cw_bits):
@@ -73,11 +79,13 @@ class StreamDemodModel:
             self.phase, self.k = 1, 0
         bf = self.bf
         k_end = (self.length - self.ci - 1) // bf          # symbols with ci + (k + 1) * bf < len
-        while self.k < k_end and self.phase < 3:
-            p = self.ci + self.k * bf - self.keep_from
-            assert p >= 0, "a symbol's samples were dropped"
-            d, loud = symbol(self.keep[p:p + bf], bf, self.amp_end)
-            self._commit(d, loud)
+        p = self.ci + self.k * bf - self.keep_from
+        assert p >= 0 or self.k >= k_end, "a symbol's samples were dropped"
+        dec, loud = symbols(self.keep[p:p + max(k_end - self.k, 0) * bf], bf, self.amp_end)
+        for d, l in zip(dec, loud):                         # (the block's complete symbols, decided at once)
+            if self.phase == 3:
+                break
+            self._commit(d, l)
             self.k += 1
         # what the next block needs: the uncommitted symbol's samples (at most bf)
         start = self.ci + self.k * bf

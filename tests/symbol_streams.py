@@ -3,7 +3,9 @@
 A stream is written as the list of symbols a receiver will decide on, one oracle tone per symbol, so that a test can
 put the terminator, a quiet symbol or a flipped coded bit at an exact symbol index.  Pure numpy plus the oracle's
 tones.  What a stream decodes to is never taken from here: the sweeps ask the oracle, and check from the oracle's
-outputs that every placement they were built for happened (clock index = the lead-in, terminator where intended)."""
+outputs that every placement they were built for happened (clock index = the lead-in, terminator where intended).
+tests/live_sweep_inputs.py builds the streaming live receiver's sweeps (gate-block edges, near-tie symbols) on it,
+too."""
 import functools
 
 import numpy as np
