@@ -271,6 +271,14 @@ LIVE_CSMA_SIGNATURES = {
                                   + LIVE_AUTO_SIGNATURES["afsk_live_push_auto"][1][7:]),
 }
 
+# The live medium (afsk_live_mix, afsk_live_mix_check), likewise.
+LIVE_MIX_SIGNATURES = {
+    "afsk_live_mix": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                C.c_uint32, C.c_void_p, C.c_void_p]),
+    "afsk_live_mix_check": (C.c_int, [_i32p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -289,7 +297,7 @@ def lib() -> C.CDLL:
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
-                                  *LIVE_CSMA_SIGNATURES.items()):
+                                  *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

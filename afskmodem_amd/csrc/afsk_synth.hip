@@ -238,6 +238,26 @@ __device__ __forceinline__ uint32_t hash32(uint32_t x) {
     return x;
 }
 
+// noise_kernel's generator for the live medium (afsk_live_mix.hip).  noise_kernel below keeps its own text: routed through
+// these two it computes the same samples with another instruction schedule, and the kernels this unit had stay as they
+// were, instruction for instruction (profiles/live_mix_isa.txt).  tests/test_gpu_live_mix.py holds the two against each
+// other sample for sample.  The key of a stream ...
+__device__ __forceinline__ uint32_t noise_key(uint32_t seed, uint32_t stream_idx) {
+    return hash32(seed ^ hash32(stream_idx + 0x9e3779b9U));
+}
+
+// ... and what is added to that stream's sample at sample index t (the caller clips the sum to int16).
+__device__ __forceinline__ int64_t noise_term(uint32_t key, uint32_t t, int64_t scale) {
+    int32_t sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+        const uint32_t hsh = hash32(key ^ (t * 8u + k));
+        sum += (int32_t)(hsh & 0xffffu) + (int32_t)(hsh >> 16);
+    }
+    const int64_t centred = (int64_t)sum - 524280;
+    return (centred * scale + (1 << 23)) >> 24;
+}
+
 __global__ __launch_bounds__(256) void noise_kernel(NoiseArgs a) {
     const int s = blockIdx.x / a.chunks;
     const int chunk = blockIdx.x - s * a.chunks;
@@ -300,3 +320,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The relay submit of the live transmitter (afsk_live_relay_check_map, afsk_live_tx_submit_events) comes behind it for
 // the same reason: it queues on the transmitter's state, whose layout afsk_live_tx.hip defines.
 #include "afsk_live_relay.hip"
+
+// The live medium (afsk_live_mix, afsk_live_mix_check) comes last, for the same reason: it stores with this file's
+// store16 and draws its noise with noise_key / noise_term.
+#include "afsk_live_mix.hip"

@@ -1675,3 +1675,178 @@ class LiveTransmitter(batch._NativePlan):
                     m.record_stream(stream)
             _native.check(_native.lib().afsk_live_tx_reset(self.handle, None if m is None else m.data_ptr(),
                                                            self.pending.data_ptr(), batch._stream_ptr(stream, dev)))
+
+
+# ------------------------------------------------------------------------------------------------- the live medium
+
+MEDIUM_UNITY = 32768                         # a link's unity gain (Q15)
+MEDIUM_MAX_GAIN = 65535                      # |gain_q15| of a link
+MEDIUM_MAX_SAMPLES = 1 << 20                 # columns of one mix
+
+
+def medium_gain_q15(gain) -> int:
+    """A link's gain as the C entry takes it: an int is Q15 already (unity 32768), a float is ``round(gain * 32768)``."""
+    if isinstance(gain, (bool, np.bool_)):
+        raise TypeError("a gain is an int (Q15) or a float")
+    if isinstance(gain, (int, np.integer)):
+        return int(gain)
+    return int(round(float(gain) * MEDIUM_UNITY))
+
+
+def medium_csr(n_out: int, links) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(out, src, gain)`` triples as the CSR arrays of ``afsk_live_mix``: ``(row_ptr [n_out + 1], link_src, link_gain_q15)``,
+    int32, the links of a row in the order they were given.  An ``out`` outside 0 ... n_out - 1 is a ValueError; sources
+    and gains are checked by ``afsk_live_mix_check``."""
+    rows = [[] for _ in range(int(n_out))]
+    for o, s, g in links:
+        o = int(o)
+        if not 0 <= o < n_out:
+            raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
+        rows[o].append((int(s), medium_gain_q15(g)))
+    counts = np.asarray([len(r) for r in rows], np.int64)
+    if int(counts.sum()) > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 links")
+    row_ptr = np.zeros(n_out + 1, np.int32)
+    row_ptr[1:] = np.cumsum(counts)
+    flat = [e for r in rows for e in r]
+    clip = lambda v: np.clip(np.asarray(v, np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)  # noqa: E731
+    return row_ptr, clip([s for s, _ in flat]), clip([g for _, g in flat])
+
+
+def medium_matrix_links(gain, n_channels: int, extra=()) -> tuple[int, int, list]:
+    """``(n_src, n_out, links)`` of a station-level gain matrix ``gain`` [n_listeners, n_stations] expanded over the
+    ``n_channels`` channels every station has: output row ``l * P + c`` hears source row ``s * P + c`` at ``gain[l][s]``;
+    a zero entry makes no link (a listener that station does not reach).  ``extra``: source rows behind the stations'
+    that every listener hears -- an int E for E groups of P rows at unity (group e's row c on channel c), or a sequence
+    of gains, one per group."""
+    g = np.asarray(gain)
+    if g.ndim != 2 or g.size == 0:
+        raise ValueError("gain must be an [n_listeners, n_stations] matrix")
+    P = int(n_channels)
+    if P < 1:
+        raise ValueError("n_channels must be at least 1")
+    extras = [MEDIUM_UNITY] * extra if isinstance(extra, (int, np.integer)) else [medium_gain_q15(x) for x in extra]
+    n_l, n_s = g.shape
+    q = [[medium_gain_q15(g[l, s].item()) for s in range(n_s)] + extras for l in range(n_l)]
+    links = [(l * P + c, s * P + c, q[l][s]) for l in range(n_l) for c in range(P) for s in range(n_s + len(extras))
+             if q[l][s] != 0]
+    return (n_s + len(extras)) * P, n_l * P, links
+
+
+class LiveMedium:
+    """The air between live stations on the device (``afsk_live_mix``): every output row is the clipped
+    sum of the source rows its links name, each scaled by a Q15 gain, plus optional receiver noise that continues from
+    mix to mix.
+
+        medium = LiveMedium.from_matrix([[0, 1.0, 0], [0.5, 0, 0.5], [0, 1.0, 0]], P, device=dev)   # A - B - C
+        for s, tx in enumerate(stations):
+            tx.pull(T, out=src[s * P:(s + 1) * P], hold=busy[s], ...)      # the stations write their rows in place
+        heard = medium.mix(src, out=chunks)                                # [3 * P, T]: what every station hears
+
+    ``links``: ``(out, src, gain)`` triples -- output row ``out`` hears source row ``src``; an int gain is Q15 (unity
+    32768, at most +-65535), a float is ``round(gain * 32768)``.  They are checked once (``afsk_live_mix_check``) and
+    kept as device arrays at fixed addresses, as are the noise scales and the position: a captured graph of
+    ``medium.mix`` replays.  ``noise_scale_q24`` ([n_out] or one int for all; ``synth.snr_to_scale_q24``): output row r
+    gets the noise of ``batch.add_noise_batch`` stream ``noise_idx_base + r`` with ``seed``, sample index ``pos + j``;
+    every mix then advances ``pos`` by T on the device, so two mixes of T equal one of 2 T.  A medium without noise
+    keeps no position (``pos`` is 0) and its mix is one launch.  Like a receiver or a transmitter, the medium must outlive
+    every graph that captured its ``mix``: the graph reads its device arrays."""
+
+    def __init__(self, n_src: int, n_out: int, links, device=None, noise_scale_q24=None, seed: int = 0,
+                 noise_idx_base: int = 0):
+        torch = batch._torch()
+        self.n_src, self.n_out = int(n_src), int(n_out)
+        if self.n_src < 0 or self.n_out < 0:
+            raise ValueError("n_src and n_out must be >= 0")
+        if not 0 <= int(seed) < 1 << 32 or not 0 <= int(noise_idx_base) < 1 << 32:
+            raise ValueError("seed and noise_idx_base must be uint32")
+        self.seed, self.noise_idx_base = int(seed), int(noise_idx_base)
+        self.row_ptr, self.link_src, self.link_gain_q15 = medium_csr(self.n_out, links)
+        self.n_links = int(self.link_src.size)
+        _native.check(_native.lib().afsk_live_mix_check(
+            _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
+            _i32_ptr(self.link_gain_q15) if self.n_links else None, self.n_out, self.n_src, self.n_links))
+        scale = None
+        if noise_scale_q24 is not None:
+            scale = np.asarray(noise_scale_q24)
+            if scale.dtype.kind not in "iu":
+                raise TypeError("noise_scale_q24 must hold integers (synth.snr_to_scale_q24)")
+            scale = np.broadcast_to(scale, (self.n_out,)) if scale.ndim == 0 else scale
+            if scale.shape != (self.n_out,):
+                raise ValueError(f"noise_scale_q24 must be [n_out={self.n_out}] or one value")
+            if scale.size and (scale.min() < -2 ** 31 or scale.max() > 2 ** 31 - 1):
+                raise ValueError("noise_scale_q24 must fit int32")
+            scale = np.ascontiguousarray(scale, np.int32)
+        _native.require_device()
+        self.device = batch._default_device(device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+        self.d_row_ptr, self.d_link_src, self.d_link_gain_q15 = up(self.row_ptr), up(self.link_src), up(self.link_gain_q15)
+        self.d_noise_scale_q24 = None if scale is None else up(scale)
+        self.d_pos = None if scale is None else torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    @classmethod
+    def from_matrix(cls, gain, n_channels: int, extra=(), **kw) -> "LiveMedium":
+        """The medium of ``medium_matrix_links(gain, n_channels, extra)``: ``gain`` [n_listeners, n_stations] per station,
+        expanded over the stations' ``n_channels`` channels; keywords as the constructor's."""
+        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra)
+        return cls(n_src, n_out, links, **kw)
+
+    @property
+    def pos(self) -> int:
+        """The medium sample the next mix begins at (a host read of the device counter: it synchronises)."""
+        return 0 if self.d_pos is None else int(self.d_pos.item())
+
+    def reset(self, pos: int = 0, stream=None) -> None:
+        """Set the position (the noise's sample index) to ``pos``, 0 ... 2^63 - 1; asynchronous on ``stream``."""
+        pos = int(pos)
+        if not 0 <= pos < 1 << 63:
+            raise ValueError("pos must lie in 0 ... 2^63 - 1")
+        if self.d_pos is None:
+            if pos:
+                raise ValueError("a medium without noise keeps no position")
+            return
+        torch = batch._torch()
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            self.d_pos.fill_(pos)
+
+    def mix(self, src, T: int | None = None, out=None, lengths=None, stream=None):
+        """Mix columns ``[0, T)`` of ``src`` ([n_src, >= T] int16 CUDA tensor, contiguous rows, any row stride; ``T`` None:
+        its width) into ``out`` ([n_out, >= T], likewise; None: a new [n_out, T] tensor) and return ``out[:, :T]``.
+        Nothing of ``out`` beyond those T columns is written.  ``lengths`` ([n_src]: an int32 CUDA tensor used in place,
+        e.g. a ragged pull's, or a host sequence, uploaded): source row s counts for ``clamp(lengths[s], 0, T)`` columns
+        and is silent, and not read, beyond.  ``out`` must not overlap ``src``.  Asynchronous on ``stream``."""
+        torch = batch._torch()
+        dev = self.device
+        if not isinstance(src, torch.Tensor):
+            raise TypeError("src must be an int16 CUDA tensor")
+        T = int(src.shape[1]) if T is None and src.dim() == 2 else int(T if T is not None else -1)
+        if not 0 <= T <= MEDIUM_MAX_SAMPLES:
+            raise ValueError(f"T = {T} must lie in 0 ... 2^20")
+        _check_rows(src, "src", "medium", self.n_src, dev, T)
+        fresh = out is None
+        if fresh:
+            out = torch.empty((self.n_out, T), dtype=torch.int16, device=dev)
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be an int16 CUDA tensor")
+        _check_rows(out, "out", "medium", self.n_out, dev, T)
+        for t, name, n in ((src, "src", self.n_src), (out, "out", self.n_out)):
+            if n > 1 and T > 0 and t.stride(0) < T:
+                raise ValueError(f"{name} row stride {t.stride(0)} is below T = {T}: the rows would overlap")
+        lens, lens_up = (None, False) if lengths is None else _device_lengths(lengths, self.n_src, dev, "medium")
+        if T == 0 or self.n_out == 0:                           # nothing to write (the C entry launches nothing either)
+            return out[:, :T]
+        with torch.cuda.device(dev):
+            if fresh or lens_up:
+                batch._order_after_current(stream, dev)
+            if lens_up and stream is not None:
+                lens.record_stream(stream)
+            _native.check(_native.lib().afsk_live_mix(
+                src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,
+                None if lens is None else lens.data_ptr(), self.d_row_ptr.data_ptr(),
+                self.d_link_src.data_ptr() if self.n_links else None,
+                self.d_link_gain_q15.data_ptr() if self.n_links else None, self.n_links,
+                out.data_ptr(), int(out.stride(0)), self.n_out, T,
+                None if self.d_noise_scale_q24 is None else self.d_noise_scale_q24.data_ptr(), self.seed,
+                self.noise_idx_base, None if self.d_pos is None else self.d_pos.data_ptr(),
+                batch._stream_ptr(stream, dev)))
+        return out[:, :T]

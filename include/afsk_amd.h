@@ -1262,6 +1262,61 @@ extern int afsk_live_push_auto_muted(afsk_live *live, const int16_t *chunk, int6
                                      void *hip_stream);
 
 /*
+ * The live medium (added after ABI version 2; the version is unchanged): the air between live stations.  Every output
+ * row is the clipped sum of the source rows its links name, each scaled by a gain -- many stations per channel, hidden
+ * terminals (a gain of 0 is no link), near / far levels, and receiver noise that continues from call to call.  The
+ * reference has no counterpart (it opens one sound device).  All of it is integer and sample-exact.
+ *
+ *  afsk_live_mix        Sources are the rows of ONE int16 matrix src [n_src, >= n_samples] with src_row_stride samples
+ *                       between rows -- a station's pull writes its rows in place, a capture or a background is more
+ *                       rows.  Links are a CSR list per output row, all DEVICE int32 and read when the kernel runs:
+ *                       d_row_ptr [n_out + 1], d_link_src [n_links], d_link_gain_q15 [n_links]; unity gain is 32768.
+ *                       With T = n_samples, for output row r and column j in [0, T):
+ *                         lo = clamp(row_ptr[r], 0, n_links)
+ *                         hi = clamp(row_ptr[r + 1], lo, min(n_links, lo + 32768))
+ *                         acc(r, j)  = sum over links k in [lo, hi) of term_k(j)
+ *                         term_k(j)  = (g_k * x_k(j)) >> 15                  (arithmetic shift: floor)
+ *                         g_k        = clamp(link_gain_q15[k], -65535, 65535)
+ *                         x_k(j)     = src[link_src[k]][j]  if 0 <= link_src[k] < n_src and j < len_k,  else 0
+ *                         len_k      = clamp(src_lens[link_src[k]], 0, T)    (T when d_src_lens_or_null is NULL)
+ *                         out[r][j]  = clamp(acc(r, j), -32768, 32767)
+ *                       Columns of a source at or beyond its length are NOT READ (a raggedly pulled buffer with stale
+ *                       columns is safe), columns of out at or beyond T are not written, a row with no links is zeros.
+ *                       A product fits int32 (65535 * 32768 < 2^31, both factors fit 24 bits) and so does a row's sum
+ *                       (32768 * 65535 < 2^31).  With every gain 32768 the result equals, bit for bit,
+ *                       clamp(sum of the int32 rows) -> int16.  A table that breaks the rules afsk_live_mix_check
+ *                       enforces is clamped or ignored as written above: it cannot make the kernel read out of bounds.
+ *                       Noise, when d_noise_scale_q24_or_null (DEVICE int32 [n_out]) is given: the result equals the
+ *                       noiseless mix followed by afsk_add_noise_batch (its generator, its rounding, its second clip)
+ *                       over the output rows taken as streams whose sample 0 is medium sample pos -- row r is stream
+ *                       noise_idx_base + r (uint32) with seed noise_seed, column j has sample index (uint32)(pos + j),
+ *                       a row whose scale is 0 draws nothing.  pos = *d_pos_or_null (DEVICE int64 [1], read when the
+ *                       kernel runs; 0 when NULL).  When d_pos_or_null is given a second, one-thread launch behind the
+ *                       mix adds n_samples to it, so a captured graph replays with continuing noise and two mixes of T
+ *                       equal one mix of 2 T.
+ *                       AFSK_E_INVALID_ARG: a NULL src / out / d_row_ptr / d_link_src / d_link_gain_q15 unless its
+ *                       count (n_src / n_out / n_out / n_links / n_links) is 0; a negative count; n_samples outside
+ *                       0 ... 2^20; a row stride below n_samples where there is more than one row; out's byte range
+ *                       (first row's first column to last row's column T) overlapping src's; n_out * ceil(T / 2048)
+ *                       above 2^31 - 1.  n_samples == 0 or n_out == 0 launches nothing and leaves pos unchanged.
+ *                       Otherwise one launch, two with d_pos_or_null, in order on hip_stream, no host read: capturable.
+ *  afsk_live_mix_check  host-only (no device needed), HOST arrays: AFSK_E_INVALID_ARG for a row_ptr that does not
+ *                       start at 0, falls, or does not end at n_links; a row with more than 32768 links; a source
+ *                       outside 0 ... n_src - 1; a gain outside -65535 ... 65535; a negative count or a NULL array
+ *                       (the link arrays may be NULL when n_links is 0).
+ * Not part of the rule: a delay per link, filters or fading, more than one source matrix per call, a length per output
+ * row.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_MIX_SIGNATURES.)
+ */
+extern int afsk_live_mix(const int16_t *src, int64_t src_row_stride, int32_t n_src, const int32_t *d_src_lens_or_null,
+                         const int32_t *d_row_ptr, const int32_t *d_link_src, const int32_t *d_link_gain_q15,
+                         int32_t n_links, int16_t *out, int64_t out_row_stride, int32_t n_out, int32_t n_samples,
+                         const int32_t *d_noise_scale_q24_or_null, uint32_t noise_seed, uint32_t noise_idx_base,
+                         int64_t *d_pos_or_null, void *hip_stream);
+extern int afsk_live_mix_check(const int32_t *h_row_ptr, const int32_t *h_link_src, const int32_t *h_link_gain_q15,
+                               int32_t n_out, int32_t n_src, int32_t n_links);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
