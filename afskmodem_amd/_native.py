@@ -279,6 +279,27 @@ LIVE_MIX_SIGNATURES = {
     "afsk_live_mix_check": (C.c_int, [_i32p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
 }
 
+# The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept), likewise.
+LIVE_DEDUP_SIGNATURES = {
+    "afsk_live_dedup_layout": (C.c_int, [C.c_int32, C.c_int32, _i64p]),
+    "afsk_live_dedup_create": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "afsk_live_dedup_destroy": (C.c_int, [C.c_void_p]),
+    "afsk_live_dedup_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afsk_live_dedup_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "afsk_live_dedup_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "afsk_live_dedup_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int64, C.c_void_p, C.c_void_p]),
+    "afsk_live_dedup_note": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    # afsk_live_tx_submit_events_rated's arguments, the DEVICE keep array behind rx_slots
+    "afsk_live_tx_submit_events_kept": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+LIVE_DEDUP_NONE, LIVE_DEDUP_DUP, LIVE_DEDUP_NEW, LIVE_DEDUP_PASS = -1, 0, 1, 2     # AFSK_LIVE_DEDUP_* verdicts
+LIVE_DEDUP_MAX_DEPTH = 64
+LIVE_TX_DUPLICATE = 7                        # AFSK_LIVE_TX_DUPLICATE
+
 
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
@@ -297,7 +318,8 @@ def lib() -> C.CDLL:
                                   *LIVE_SEGMENT_SIGNATURES.items(), *DETECT_SIGNATURES.items(),
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
-                                  *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items()):
+                                  *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items(),
+                                  *LIVE_DEDUP_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

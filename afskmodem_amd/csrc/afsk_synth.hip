@@ -324,3 +324,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The live medium (afsk_live_mix, afsk_live_mix_check) comes last, for the same reason: it stores with this file's
 // store16 and draws its noise with noise_key / noise_term.
 #include "afsk_live_mix.hip"
+
+// The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept) closes the unit, behind afsk_live_relay.hip:
+// it launches that file's order kernel and queues with its RelayArgs and RelayRated.
+#include "afsk_live_dedup.hip"

@@ -20,7 +20,9 @@ Transmit: a ``LiveTransmitter`` keeps a queue of messages per channel on the dev
 samples of every channel (``afsk_live_tx_pull``), the queued messages back to back, each exactly what
 ``Transmitter.save`` writes for it.  Nothing here opens an audio device.  ``LiveTransmitter.submit_events`` queues the
 bursts a receiver's push closed straight from its packed event list (``afsk_live_tx_submit_events``): a relay whose tick
--- push, pack, submit, pull -- never leaves the device.
+-- push, pack, submit, pull -- never leaves the device.  ``LiveDedup`` (``LiveReceiver.deduper``) is such a relay's duplicate
+list, kept on the device: ``filter`` gives every record of the list a verdict and ``submit_events(keep=)`` does not repeat
+what the channel handled within the window, so two relays that hear each other fall silent.
 
 Both take one rate for all channels or one per channel (a sequence of n_channels), interleaved in any order, so a
 ``[channels, time]`` buffer of mixed rates is pushed or pulled as it is (``afsk_live_create_mixed``,
@@ -1154,6 +1156,10 @@ class LiveReceiver(batch._NativePlan):
             _native.check(_native.lib().afsk_live_busy(self.handle, out.data_ptr(), batch._stream_ptr(stream, dev)))
         return out
 
+    def deduper(self, depth: int = 8, window=30.0) -> "LiveDedup":
+        """A duplicate filter (``LiveDedup``) for this receiver's channels, on its device."""
+        return LiveDedup(self.n_channels, depth=depth, window=window, device=self.device)
+
 
 # ------------------------------------------------------------------------------------------------- live transmit
 
@@ -1194,13 +1200,35 @@ def tx_state_bytes_rated(n_channels: int, n_rates: int, queue_depth: int, max_pa
     return int(nbytes.value)
 
 
+def _device_events(events, dev, owner: str):
+    """What ``submit_events`` and ``LiveDedup.filter`` check of the ``LiveEvents`` they read on the device: a contiguous
+    uint8 CUDA buffer on ``dev`` with the layout of the referenced result's push.  Returns ``(buffer, result,
+    receiver channels, payload row width, max_events, max_bytes)``."""
+    torch = batch._torch()
+    if not isinstance(events, LiveEvents):
+        raise TypeError("events must be the LiveEvents of a push(events=...) or pack")
+    buf, res = events.buffer, events.result
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous():
+        raise ValueError("events must lie in a contiguous uint8 CUDA buffer (LiveReceiver.alloc_events)")
+    if buf.device != dev:
+        raise ValueError(f"events is on {buf.device}, the {owner} on {dev}")
+    if res is None:
+        raise ValueError("events references no LiveResult: pack a push into it first (push(events=...))")
+    n_rx, stride = int(res.n_closed.shape[0]), int(res.demod.bytes.shape[1])
+    me, mb = events.max_events, events.max_bytes
+    ro, po, total = events_layout(n_rx, res.slots, me, mb)
+    if (events.records_offset, events.payload_offset) != (ro, po) or int(buf.numel()) < total:
+        raise ValueError("events was not allocated by a receiver's alloc_events for this push")
+    return buf, res, n_rx, stride, me, mb
+
+
 @dataclass
 class SubmitResult:
     """Device-resident outputs of one ``submit`` (torch tensors), in the caller's message order, or of one
     ``submit_events``, entry i for record i of the events buffer."""
     status: "object"         # int32 [n] LIVE_TX_QUEUED / _QUEUE_FULL / _TOO_LONG / _BAD_CHANNEL (submit_events: also
-                             # _UNSORTED, _SKIPPED, with rate="heard" _BAD_RATE and, from the push's record count on,
-                             # _NONE)
+                             # _UNSORTED, _SKIPPED, with rate="heard" _BAD_RATE, with keep= _DUPLICATE and, from the
+                             # push's record count on, _NONE)
     start: "object"          # int64 [n] stream index of the first sample (-1: rejected)
     n_samples: "object"      # int32 [n] samples of the message (0: rejected)
 
@@ -1474,7 +1502,7 @@ class LiveTransmitter(batch._NativePlan):
         return t, True
 
     def submit_events(self, events: "LiveEvents", channel_map=None, skip_flags: int = _native.LIVE_OPEN_END,
-                      out: SubmitResult | None = None, stream=None, rate=None) -> SubmitResult:
+                      out: SubmitResult | None = None, stream=None, rate=None, keep=None) -> SubmitResult:
         """Relay: queue the bursts a receiver's push closed, straight from its packed event list on the device
         (``afsk_live_tx_submit_events``) -- no copy to the host and no synchronisation, so ``push(events=)``,
         ``submit_events(out=)`` and ``pull`` of fixed buffers can be captured into ONE graph.
@@ -1500,7 +1528,13 @@ class LiveTransmitter(batch._NativePlan):
         ``rate="heard"`` (a rated transmitter and the events of an auto receiver's push, ValueError otherwise): every
         burst is queued at the rate the receiver detected for it (``afsk_live_tx_submit_events_rated`` reads
         ``events.result.bit_frames`` on the device); a rate the table lacks -- a burst the receiver did not rate is one
-        -- answers ``LIVE_TX_BAD_RATE``.  ``rate=None``: a rated transmitter plays every burst at its first entry."""
+        -- answers ``LIVE_TX_BAD_RATE``.  ``rate=None``: a rated transmitter plays every burst at its first entry.
+
+        ``keep`` (a contiguous int32 ``[max_events]`` CUDA tensor on the transmitter's device, read when the kernels
+        run: the verdicts of ``LiveDedup.filter`` on the same events): a relayable record whose entry is 0
+        (``LIVE_DEDUP_DUP``) answers ``LIVE_TX_DUPLICATE`` and takes no queue slot; any other value changes nothing
+        (``afsk_live_tx_submit_events_kept``, transmitters of every kind, with and without ``rate="heard"``).
+        ``keep=None`` calls the entries it called before."""
         if rate is not None:                                     # (what needs no device comes first)
             if rate != "heard":
                 raise ValueError('rate must be None or "heard"')
@@ -1511,17 +1545,8 @@ class LiveTransmitter(batch._NativePlan):
                                  '(LiveReceiver(n, "auto", ...)): this result holds no detected rates')
         _native.require_device()
         torch = batch._torch()
-        if not isinstance(events, LiveEvents):
-            raise TypeError("events must be the LiveEvents of a push(events=...) or pack")
         dev = self.device
-        buf, res = events.buffer, events.result
-        if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous():
-            raise ValueError("events must lie in a contiguous uint8 CUDA buffer (LiveReceiver.alloc_events)")
-        if buf.device != dev:
-            raise ValueError(f"events is on {buf.device}, the transmitter on {dev}")
-        if res is None:
-            raise ValueError("events references no LiveResult: pack a push into it first (push(events=...))")
-        n_rx, stride = int(res.n_closed.shape[0]), int(res.demod.bytes.shape[1])
+        buf, res, n_rx, stride, me, mb = _device_events(events, dev, "transmitter")
         heard = None
         if rate == "heard":
             heard = res.bit_frames
@@ -1529,13 +1554,16 @@ class LiveTransmitter(batch._NativePlan):
                     or tuple(heard.shape) != (n_rx, int(res.slots)) or not heard.is_contiguous():
                 raise ValueError(f"the result's bit_frames must be a contiguous int32 [{n_rx}, {int(res.slots)}] "
                                  f"tensor on {dev}")
-        me, mb = events.max_events, events.max_bytes
-        ro, po, total = events_layout(n_rx, res.slots, me, mb)
-        if (events.records_offset, events.payload_offset) != (ro, po) or int(buf.numel()) < total:
-            raise ValueError("events was not allocated by a receiver's alloc_events for this push")
         skip = int(skip_flags)
         if skip & ~(_native.LIVE_OPEN_END | _native.LIVE_OVERFLOW):
             raise ValueError("skip_flags may hold LIVE_OPEN_END and LIVE_OVERFLOW alone")
+        if keep is not None:
+            if not isinstance(keep, torch.Tensor) or keep.dtype != torch.int32:
+                raise TypeError("keep must be an int32 CUDA tensor (LiveDedup.alloc_verdict)")
+            if not keep.is_cuda or keep.device != dev:
+                raise ValueError(f"keep is on {keep.device}, the transmitter on {dev}")
+            if keep.dim() != 1 or int(keep.numel()) != me or not keep.is_contiguous():
+                raise ValueError(f"keep must be a contiguous [max_events={me}], got {list(keep.shape)}")
         cmap, uploaded = self._relay_map(channel_map, n_rx)
         fresh = out is None
         if fresh:
@@ -1551,7 +1579,13 @@ class LiveTransmitter(batch._NativePlan):
                 batch._order_after_current(stream, dev)
             if uploaded and stream is not None:
                 cmap.record_stream(stream)
-            if heard is not None:
+            if keep is not None:
+                _native.check(_native.lib().afsk_live_tx_submit_events_kept(
+                    self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
+                    None if heard is None else heard.data_ptr(), int(res.slots) if heard is not None else 0,
+                    keep.data_ptr(), out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(),
+                    batch._stream_ptr(stream, dev)))
+            elif heard is not None:
                 _native.check(_native.lib().afsk_live_tx_submit_events_rated(
                     self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
                     heard.data_ptr(), int(res.slots), out.status.data_ptr(), out.start.data_ptr(),
@@ -1561,7 +1595,7 @@ class LiveTransmitter(batch._NativePlan):
                     self.handle, buf.data_ptr(), me, mb, stride, n_rx, None if cmap is None else cmap.data_ptr(), skip,
                     out.status.data_ptr(), out.start.data_ptr(), out.n_samples.data_ptr(),
                     batch._stream_ptr(stream, dev)))
-        out._keepalive = (buf, cmap, heard)  # type: ignore[attr-defined]
+        out._keepalive = (buf, cmap, heard, keep)  # type: ignore[attr-defined]
         return out
 
     def pull(self, T: int, out=None, stream=None, lengths=None, hold=None, holdoff: int = 0, persist=None,
@@ -1850,3 +1884,233 @@ class LiveMedium:
                 self.noise_idx_base, None if self.d_pos is None else self.d_pos.data_ptr(),
                 batch._stream_ptr(stream, dev)))
         return out[:, :T]
+
+
+# ------------------------------------------------------------------------------------------- the duplicate filter
+
+DEDUP_STATE_DTYPE = np.dtype([("key", "<u8"), ("time", "<i8")])      # one ring entry; time DEDUP_EMPTY: empty
+DEDUP_EMPTY = -(2 ** 63)
+
+
+def dedup_layout(n_channels: int, depth: int) -> int:
+    """State bytes of a duplicate filter (``afsk_live_dedup_layout``: host-only, needs no device): the entries
+    ``[n_channels, depth]`` of 16 bytes, the int32 heads and 256 bytes of scratch, each part 256-byte aligned."""
+    nbytes = C.c_int64()
+    _native.check(_native.lib().afsk_live_dedup_layout(int(n_channels), int(depth), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def dedup_window(window) -> int:
+    """A window as the C entries take it: an int is samples already, a float is seconds at 48000 samples/s."""
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, float, np.integer, np.floating)):
+        raise TypeError("window is seconds (a float) or samples (an int)")
+    if isinstance(window, (float, np.floating)):
+        if not np.isfinite(window):
+            raise ValueError("window must be finite")
+        window = round(float(window) * _native.SAMPLE_RATE)
+    window = int(window)
+    if not 0 <= window < 1 << 63:
+        raise ValueError("window must lie in 0 ... 2^63 - 1 samples")
+    return window
+
+
+class LiveDedup(batch._NativePlan):
+    """A relay's duplicate list on the device (``afsk_live_dedup_*``): a payload a receiver channel has
+    handled within the last ``window`` is not repeated, so two relays that hear each other fall silent.
+
+        dd   = rx.deduper(depth=8, window=30.0)
+        keep = dd.alloc_verdict(ev.max_events)
+        rx.push(chunk, out=res, events=ev, mute=tx.on_air)
+        dd.filter(ev, out=keep)                                  # LIVE_DEDUP_NEW / _DUP / _PASS / _NONE per record
+        tx.submit_events(ev, keep=keep, out=sub)                 # LIVE_TX_DUPLICATE where keep == 0
+
+    Every channel keeps the keys (a 64-bit hash of the payload bytes and their count) and end times of the last
+    ``depth`` (1 ... 64) distinct payloads it handled; ``window`` is seconds (a float) or samples (an int), 0 remembers
+    everything and drops nothing.  A burst is remembered when it is HEARD, not when it is queued: one the transmitter
+    then refuses (``LIVE_TX_QUEUE_FULL``) is on the list all the same.  A duplicate does not refresh its entry.
+    ``filter`` and ``note`` allocate nothing and read nothing on the host when given ``out=``: both can be captured, and
+    a ``LiveDedup`` must outlive every graph that captured it."""
+    _destroy = "afsk_live_dedup_destroy"
+
+    def __init__(self, n_channels: int, depth: int = 8, window=30.0, device=None):
+        torch = batch._torch()
+        self.n_channels, self.depth = int(n_channels), int(depth)
+        self.window = dedup_window(window)
+        self.state_bytes = dedup_layout(self.n_channels, self.depth)                  # (before the device check)
+        super().__init__(device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().afsk_live_dedup_create(self.n_channels, self.depth, C.byref(self._h)))
+
+    def alloc_verdict(self, max_events: int):
+        """An int32 ``[max_events]`` tensor of ``LIVE_DEDUP_NONE`` for ``filter(out=)`` / ``note(out=)`` and
+        ``submit_events(keep=)``: a fixed address for graphs."""
+        torch = batch._torch()
+        return torch.full((int(max_events),), _native.LIVE_DEDUP_NONE, dtype=torch.int32, device=self.device)
+
+    def _verdict(self, out, n: int, stream):
+        torch = batch._torch()
+        dev = self.device
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                batch._order_after_current(stream, dev)
+            return out
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32:
+            raise TypeError("out must be an int32 CUDA tensor (alloc_verdict)")
+        if not out.is_cuda or out.device != dev:
+            raise ValueError(f"out is on {out.device}, the filter on {dev}")
+        if out.dim() != 1 or int(out.numel()) != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous [{n}], got {list(out.shape)}")
+        return out
+
+    def filter(self, events: "LiveEvents", out=None, skip_flags: int = _native.LIVE_OPEN_END, window=None,
+               stream=None):
+        """Look up and remember the bursts of one push (``afsk_live_dedup_filter``: two launches, no host read).
+        ``events`` is checked as ``LiveTransmitter.submit_events`` checks it.  Returns ``out`` (``alloc_verdict``; None:
+        a new tensor), entry i for record i: ``LIVE_DEDUP_NEW`` (remembered now), ``LIVE_DEDUP_DUP`` (handled within the
+        window), ``LIVE_DEDUP_PASS`` (a record the relay would not queue, or one at or past the first unsorted record:
+        neither looked up nor remembered) and ``LIVE_DEDUP_NONE`` from the push's record count on.  ``skip_flags`` as
+        ``submit_events`` takes it; ``window=None``: the object's."""
+        skip = int(skip_flags)
+        if skip & ~(_native.LIVE_OPEN_END | _native.LIVE_OVERFLOW):
+            raise ValueError("skip_flags may hold LIVE_OPEN_END and LIVE_OVERFLOW alone")
+        win = self.window if window is None else dedup_window(window)
+        _native.require_device()
+        torch = batch._torch()
+        dev = self.device
+        buf, res, n_rx, stride, me, mb = _device_events(events, dev, "filter")
+        out = self._verdict(out, me, stream)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().afsk_live_dedup_filter(self.handle, buf.data_ptr(), me, mb, stride, skip, win,
+                                                               out.data_ptr(), batch._stream_ptr(stream, dev)))
+        return out
+
+    def note(self, channels, payloads, time, out=None, window=None, stream=None, lengths=None):
+        """Put explicit messages on the list (``afsk_live_dedup_note``) -- what an originating station sends itself, so
+        that the echo a neighbour relays back is a duplicate.  ``time`` is the sample at which a listener's burst of the
+        message ends: the submit's ``start + n_samples``.
+
+        Host arguments, as ``LiveTransmitter.submit`` takes them: ``channels`` (a sequence, or one int for all),
+        ``payloads`` (str -- UTF-8 -- or bytes each) and ``time`` (a sequence of ints, one int for all, or an int64
+        ``[n]`` CUDA tensor such as ``sub.start + sub.n_samples``); they are sorted by channel, uploaded, and the verdicts
+        come back in list order.  Device arguments, used in place: ``channels`` int32 ``[n]`` ascending, ``payloads``
+        uint8 ``[n, stride]``, ``lengths`` int32 ``[n]`` (None: every row is ``stride`` bytes) and ``time`` int64 ``[n]``,
+        contiguous CUDA tensors on the filter's device.  Returns the verdicts (``out``: int32 ``[n]``): ``LIVE_DEDUP_NEW``,
+        ``LIVE_DEDUP_DUP``, or ``LIVE_DEDUP_PASS`` for an empty message, a channel outside the filter's or -- device
+        arguments -- a message at or past the first descending channel."""
+        win = self.window if window is None else dedup_window(window)
+        torch = batch._torch()
+        dev = self.device
+        on_device = isinstance(payloads, torch.Tensor)
+        perm = None
+        if on_device:
+            n = int(payloads.shape[0]) if payloads.dim() == 2 else -1
+            stride = int(payloads.shape[1]) if payloads.dim() == 2 else 0
+            if lengths is None:
+                lengths = torch.full((max(n, 0),), stride, dtype=torch.int32, device=dev)
+            for t, dt, shape, name in ((channels, torch.int32, (n,), "channels"), (payloads, torch.uint8, (n, stride), "payloads"),
+                                       (lengths, torch.int32, (n,), "lengths"), (time, torch.int64, (n,), "time")):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                    raise TypeError(f"{name} must be a {dt} CUDA tensor when payloads is one")
+                if not t.is_cuda or t.device != dev:
+                    raise ValueError(f"{name} is on {t.device}, the filter on {dev}")
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous {list(shape)}, got {list(t.shape)}")
+            d_ch, d_pay, d_len, d_time = channels, payloads, lengths, time
+        else:
+            if lengths is not None:
+                raise ValueError("lengths= goes with a payload tensor; host payloads carry their own")
+            data = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in payloads]
+            n = len(data)
+            ch = np.broadcast_to(np.asarray(channels, np.int64), (n,)) if np.ndim(channels) == 0 else \
+                np.asarray(channels, np.int64)
+            if ch.shape != (n,):
+                raise ValueError(f"{ch.size} channels for {n} payloads")
+            ch32 = np.where((ch < 0) | (ch >= self.n_channels), -1, ch).astype(np.int32)      # -1: LIVE_DEDUP_PASS
+            order = np.argsort(ch32, kind="stable")
+            perm = None if bool((order == np.arange(n)).all()) else order
+            idx = order.tolist()
+            stride = max([len(d) for d in data] + [1])
+            rows = np.zeros((n, stride), np.uint8)
+            for r, i in enumerate(idx):
+                rows[r, : len(data[i])] = np.frombuffer(data[i], np.uint8)
+            lens = np.asarray([len(data[i]) for i in idx], np.int32)
+            if isinstance(time, torch.Tensor):
+                if time.dtype != torch.int64 or not time.is_cuda or time.device != dev or tuple(time.shape) != (n,):
+                    raise ValueError(f"time must be ints or an int64 [{n}] CUDA tensor on {dev}")
+                h_time = None
+            else:
+                h_time = np.broadcast_to(np.asarray(time, np.int64), (n,)) if np.ndim(time) == 0 else \
+                    np.asarray(time, np.int64)
+                if h_time.shape != (n,):
+                    raise ValueError(f"{h_time.size} times for {n} payloads")
+        out = self._verdict(out, n, stream)
+        if n == 0:
+            return out
+        _native.require_device()
+        with torch.cuda.device(dev):
+            if not on_device:
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+                d_ch, d_pay, d_len = up(ch32[order]), up(rows), up(lens)
+                d_perm = None if perm is None else up(perm.astype(np.int64))
+                d_time = up(h_time[order]) if h_time is not None else \
+                    (time.contiguous() if d_perm is None else time[d_perm].contiguous())
+                batch._order_after_current(stream, dev)
+                if stream is not None:
+                    for t in (d_ch, d_pay, d_len, d_time):
+                        t.record_stream(stream)
+            sorted_out = out if perm is None else torch.empty_like(out)
+            _native.check(_native.lib().afsk_live_dedup_note(
+                self.handle, d_ch.data_ptr(), d_pay.data_ptr(), stride, d_len.data_ptr(), d_time.data_ptr(), n, win,
+                sorted_out.data_ptr(), batch._stream_ptr(stream, dev)))
+            if perm is not None:
+                with torch.cuda.stream(stream):
+                    out[d_perm] = sorted_out
+        return out
+
+    def reset(self, mask=None, stream=None) -> None:
+        """Empty the list of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool / uint8,
+        host or device) is true."""
+        torch = batch._torch()
+        dev = self.device
+        m = _device_mask(mask, self.n_channels, dev)
+        with torch.cuda.device(dev):
+            if m is not None:
+                batch._order_after_current(stream, dev)
+                if stream is not None:
+                    m.record_stream(stream)
+            _native.check(_native.lib().afsk_live_dedup_reset(self.handle, None if m is None else m.data_ptr(),
+                                                              batch._stream_ptr(stream, dev)))
+
+    def _table_bytes(self) -> tuple[int, int]:
+        o_head = (16 * self.n_channels * self.depth + 255) & ~255
+        return o_head, self.state_bytes - 256
+
+    def state(self) -> tuple[np.ndarray, np.ndarray]:
+        """``(entries, head)`` on the host (it synchronises the device): ``entries`` [n_channels, depth] of
+        ``DEDUP_STATE_DTYPE`` (``time == DEDUP_EMPTY``: empty), ``head`` int32 [n_channels], the entry the next
+        insertion writes."""
+        torch = batch._torch()
+        o_head, nbytes = self._table_bytes()
+        raw = np.zeros(nbytes, np.uint8)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)
+            _native.check(_native.lib().afsk_live_dedup_get_state(self.handle, raw.ctypes.data, nbytes))
+        entries = raw[: 16 * self.n_channels * self.depth].view(DEDUP_STATE_DTYPE).reshape(self.n_channels, self.depth)
+        return entries.copy(), raw[o_head: o_head + 4 * self.n_channels].view(np.int32).copy()
+
+    def load_state(self, entries, head) -> None:
+        """Replace the list by ``(entries, head)`` as ``state`` returns them (it synchronises the device): a station that
+        restarts keeps its list.  A head outside 0 ... depth - 1 is refused."""
+        torch = batch._torch()
+        e = np.ascontiguousarray(entries, DEDUP_STATE_DTYPE)
+        h = np.ascontiguousarray(head, np.int32)
+        if e.shape != (self.n_channels, self.depth) or h.shape != (self.n_channels,):
+            raise ValueError(f"entries must be [{self.n_channels}, {self.depth}] and head [{self.n_channels}]")
+        o_head, nbytes = self._table_bytes()
+        raw = np.zeros(nbytes, np.uint8)
+        raw[: e.nbytes] = e.reshape(-1).view(np.uint8)
+        raw[o_head: o_head + h.nbytes] = h.view(np.uint8)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)
+            _native.check(_native.lib().afsk_live_dedup_set_state(self.handle, raw.ctypes.data, nbytes))

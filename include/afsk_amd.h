@@ -1317,6 +1317,117 @@ extern int afsk_live_mix_check(const int32_t *h_row_ptr, const int32_t *h_link_s
                                int32_t n_out, int32_t n_src, int32_t n_links);
 
 /*
+ * The duplicate filter (added after ABI version 2; the version is unchanged): the list every digipeater keeps so that
+ * two relays that hear each other do not repeat each other for ever -- a payload already handled within the last
+ * `window` samples is not repeated.  The reference protocol has no framing, no addresses and no hop count, so payload
+ * identity within a time window is the only loop breaker it can have.  afsk_live_push_muted breaks the loop of a station
+ * with itself; this breaks the loop between stations.  All of it is integer and exact, and
+ *   push_muted -> busy -> dedup_filter -> submit_events_kept -> pull_csma -> mix
+ * stays one captured graph.
+ *
+ * State.  Every receiver channel owns a ring of `depth` entries (1 ... 64), an entry {uint64 key; int64 time}, time
+ * INT64_MIN: the entry is empty; and an int32 head, the entry the next insertion writes.  One DEVICE allocation:
+ *   [0, 16 * n_channels * depth)      the entries, channel-major
+ *   [o_head, + 4 * n_channels)        the heads; o_head = the entries' bytes rounded up to 256
+ *   [o_scratch, + 256)                scratch of the order kernels; o_scratch = o_head + (4 * n_channels rounded up to 256)
+ * 65536 channels at depth 8 hold 8 MiB of entries.
+ *
+ * The key of a payload p[0 .. n), all arithmetic mod 2^64:
+ *   mix64(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *              z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   key = mix64( (sum over i < n of mix64(((uint64)i << 8) | p[i])) ^ ((uint64)n << 32) )
+ * (the sum commutes: a wave adds its lanes' terms in any order and still gets the exact value).
+ *
+ * The rule, for the eligible items of ONE channel in list order, each with its key and a time t:
+ *   duplicate  some non-empty entry of the channel has the same key, entry.time <= t and t - entry.time < window (the
+ *              age is taken without overflow): AFSK_LIVE_DEDUP_DUP.  The table stays as it is; the entry's time is NOT
+ *              refreshed.
+ *   new        otherwise: {key, t} is written at ring[head], head becomes (head + 1) % depth: AFSK_LIVE_DEDUP_NEW.  This
+ *              replaces the oldest insertion whether or not it has expired.
+ * A later item of the same list sees the insertion an earlier one made: two equal bursts in one list are NEW, then DUP.
+ * window (int64 samples, >= 0) comes with every call; window 0 remembers everything and drops nothing.  An entry from
+ * the future (t < entry.time: the stream restarted after a reset or a flush) is no duplicate.  (A time of exactly
+ * INT64_MIN is stored as it is and reads as an empty entry.)
+ * A burst is remembered when it is HEARD, not when it is queued: a burst the transmitter then refuses
+ * (AFSK_LIVE_TX_QUEUE_FULL, _TOO_LONG ...) is on the list all the same, and a second copy of it within the window is a
+ * duplicate.
+ *
+ *  afsk_live_dedup_layout   host-only (no device needed): the state's bytes as above.  AFSK_E_INVALID_ARG: n_channels
+ *                           < 1, depth outside 1 ... 64.
+ *  afsk_live_dedup_create   allocates the state on the current device, every ring empty, every head 0 (synchronous).
+ *  afsk_live_dedup_destroy  after the launches that use the filter have completed (NULL is fine).
+ *  afsk_live_dedup_reset    empties the rings of every channel (d_mask_or_null NULL) or of the channels whose DEVICE
+ *                           uint8 mask entry is non-zero and sets their heads to 0; one launch on hip_stream.
+ *  afsk_live_dedup_get_state / _set_state  synchronous copies of the entries and the heads -- bytes [0, o_scratch) of
+ *                           the state, `bytes` must be exactly that -- to and from HOST memory: a station that restarts
+ *                           keeps its list.  _set_state refuses a head outside 0 ... depth - 1.
+ *  afsk_live_dedup_filter   filters the packed event list of one push.  The records are read exactly as
+ *                           afsk_live_tx_submit_events reads them: `stored` is clamped to 0 ... max_events and the first
+ *                           unsorted record is found by the same order kernel, writing into the filter's own scratch.
+ *                           d_verdict (DEVICE int32 [max_events], all written by every call), entry i:
+ *                             i >= stored                                   AFSK_LIVE_DEDUP_NONE
+ *                             at or past the first unsorted record, or the
+ *                             record is not eligible                        AFSK_LIVE_DEDUP_PASS: neither looked up nor
+ *                                                                           remembered; whatever consumes the list
+ *                                                                           decides (the relay answers _UNSORTED,
+ *                                                                           _SKIPPED ... as it does without a filter)
+ *                             otherwise                                     the rule with t = burst_start + burst_len
+ *                           A record is eligible when its channel lies in 0 ... n_channels - 1, its status is
+ *                           AFSK_ST_OK, 1 <= nbytes <= out_stride, payload_offset >= 0, payload_offset + nbytes <=
+ *                           max_bytes and flags & (skip_flags | AFSK_LIVE_OVERFLOW) is 0: the relay's relayable
+ *                           condition without the channel map.  Two launches in order on hip_stream (the order kernel,
+ *                           live_dedup_kernel), no allocation, no synchronisation, no host read: capturable.  Nothing of
+ *                           the events buffer is written, and whatever it holds no access leaves the buffers given.
+ *  afsk_live_dedup_note     the same rule on explicit messages, so that an originating station puts what it sends on its
+ *                           own list: d_channels int32 [n_messages], ascending (a message at or past the first one whose
+ *                           channel is below its predecessor's gets _PASS); d_payload uint8 [n_messages,
+ *                           payload_stride], row i the bytes of message i; d_payload_len int32 [n_messages]; d_time
+ *                           int64 [n_messages], the message's t -- typically the submit's start + n_samples, the sample
+ *                           at which a listener's burst of it ends.  A message whose length lies outside 1 ...
+ *                           payload_stride or whose channel lies outside the filter's gets _PASS.  All DEVICE arrays.
+ *                           Two launches (afsk_live_tx_submit's order kernel, live_dedup_note_kernel), capturable.
+ *  afsk_live_tx_submit_events_kept  afsk_live_tx_submit_events_rated's arguments with d_rx_bit_frames_or_null nullable
+ *                           (NULL: afsk_live_tx_submit_events' behaviour, on a rated transmitter table entry 0) and
+ *                           d_keep (DEVICE int32 [max_events]) behind rx_slots.  A relayable record whose d_keep entry is
+ *                           0 answers AFSK_LIVE_TX_DUPLICATE, start -1, n_samples 0, and takes no queue slot: the check
+ *                           comes behind the _SKIPPED conditions and in front of _BAD_CHANNEL.  Any other d_keep value:
+ *                           exactly what afsk_live_tx_submit_events / _rated do.  d_keep is read for relayable records
+ *                           alone.  Uniform, mixed and rated transmitters; two launches, capturable.  Besides
+ *                           afsk_live_tx_submit_events' refusals: a NULL d_keep; d_rx_bit_frames with rx_slots < 1 or
+ *                           with a transmitter that is not rated.
+ * AFSK_E_INVALID_ARG, nothing launched: a NULL filter, events, verdict or message array; a negative size or window;
+ * skip_flags with bits other than AFSK_LIVE_OPEN_END | AFSK_LIVE_OVERFLOW; an events pointer that is not 16-byte aligned.
+ * max_events == 0 or n_messages == 0: AFSK_OK, no launch.  Calls on one filter must run in order.
+ * Not part of the rule: a window per channel, keys that ignore part of the payload, one list shared across channels,
+ * refreshing an entry on a duplicate, a compacted copy of the event list.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_DEDUP_SIGNATURES.)
+ */
+#define AFSK_LIVE_DEDUP_NONE (-1) /* the entry is at or past `stored`: no record                                      */
+#define AFSK_LIVE_DEDUP_DUP 0     /* handled within the window: do not repeat it                                       */
+#define AFSK_LIVE_DEDUP_NEW 1     /* not on the list: remembered now                                                   */
+#define AFSK_LIVE_DEDUP_PASS 2    /* not eligible or unsorted: not looked up, not remembered                           */
+#define AFSK_LIVE_TX_DUPLICATE 7  /* afsk_live_tx_submit_events_kept: d_keep says 0 for this record: nothing queued    */
+typedef struct afsk_live_dedup afsk_live_dedup;
+extern int afsk_live_dedup_layout(int32_t n_channels, int32_t depth, int64_t *out_state_bytes);
+extern int afsk_live_dedup_create(int32_t n_channels, int32_t depth, afsk_live_dedup **out);
+extern int afsk_live_dedup_destroy(afsk_live_dedup *dd);
+extern int afsk_live_dedup_reset(afsk_live_dedup *dd, const uint8_t *d_mask_or_null, void *hip_stream);
+extern int afsk_live_dedup_get_state(afsk_live_dedup *dd, void *host_out, int64_t bytes);
+extern int afsk_live_dedup_set_state(afsk_live_dedup *dd, const void *host_in, int64_t bytes);
+extern int afsk_live_dedup_filter(afsk_live_dedup *dd, const void *events, int32_t max_events, int32_t max_bytes,
+                                  int32_t out_stride, int32_t skip_flags, int64_t window, int32_t *d_verdict,
+                                  void *hip_stream);
+extern int afsk_live_dedup_note(afsk_live_dedup *dd, const int32_t *d_channels, const uint8_t *d_payload,
+                                int32_t payload_stride, const int32_t *d_payload_len, const int64_t *d_time,
+                                int32_t n_messages, int64_t window, int32_t *d_verdict, void *hip_stream);
+extern int afsk_live_tx_submit_events_kept(afsk_live_tx *tx, const void *events, int32_t max_events, int32_t max_bytes,
+                                           int32_t out_stride, int32_t n_rx_channels,
+                                           const int32_t *d_channel_map_or_null, int32_t skip_flags,
+                                           const int32_t *d_rx_bit_frames_or_null, int32_t rx_slots,
+                                           const int32_t *d_keep, int32_t *out_status, int64_t *out_start,
+                                           int32_t *out_n_samples, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
