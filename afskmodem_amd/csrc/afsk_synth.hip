@@ -60,7 +60,8 @@ constexpr uint32_t kHi2 = 0x7FFF7FFFu, kLo2 = 0x80008000u;    // two samples at 
 // 8 samples of a block that lies entirely inside the tones.  A tone is constant over a quarter
 // symbol (q = bf/4 frames: space = hi,hi,lo,lo ref:68-77, mark = hi,lo,hi,lo ref:80-85), so the
 // block keeps ONE bit per quarter symbol in LDS (qb, bit r = quarter 4*Sb + r is high) and a
-// store needs the quarter of its first frame (one exact float division: x0 < 2^14) plus
+// store needs the quarter of its first frame (x0 < bit_frames + 16384 <= 2^20 + 2^14, the block's phase plus its
+// offset in the block; (x0 + 0.5f) * (1.0f / q) floors to x0 / q for every q <= 2^18 there: tests/test_kernel_math.py) plus
 //   q >= 8 : at most one quarter boundary inside the 8 frames -> compare against its position
 //   q <  8 : the quarter offset of every frame by a 16-bit reciprocal multiply (exact below 14)
 template <bool QUIRK, bool SMALLQ>

@@ -365,7 +365,9 @@ int afsk_wav_egress(const char *const *paths, int32_t n_files, const int16_t *d_
  *  payload      uint8 [n, payload_stride]; payload_len [n] bytes used per row
  *  bit_frames   [n] 48000 / baud; a positive multiple of 4 (every baud rate the reference's
  *               Waveforms accept, :69-70/:81-82, gives one); any other value yields an
- *               all-zero stream (device arrays are not validated on the host)
+ *               all-zero stream (device arrays are not validated on the host).  Every multiple
+ *               of 4 from 4 up to 2^20 = 1048576 is rendered, whether or not it divides 48000;
+ *               a value above 2^20 yields the all-zero stream too
  *  ts_cycles    [n] int(baud * training_time / 2)   (:438)
  *  max_stream_len  host-side upper bound of stream_len[] (sizes the grid); a stream whose device-side
  *               stream_len[s] is negative or above it is skipped (nothing written for it)

@@ -81,3 +81,31 @@ def mix(src, row_ptr, link_src, link_gain_q15, n_out: int, T: int, src_lens=None
             row = noise_row(row, seed, (noise_idx_base + r) & 0xFFFFFFFF, int(noise_scale_q24[r]), pos)
         out[r] = row
     return out
+
+
+# ------------------------------------------------------------------------------------- tables at the header's limits
+
+def limit_links():
+    """``(n_src, n_out, links)``: source 0 is to be held at -32768, source 1 is any.  Row 0: MAX_DEGREE links at gain
+    -MAX_GAIN on source 0 -- 32768 * 65535 = 2147450880, the bound the header gives for a row's int32 sum.  Row 1, of
+    MAX_DEGREE links too: 16383 such links, 16383 at +MAX_GAIN on the same source, one unity link to source 1 and one
+    of gain 0 -- the sum climbs to 1073659905, comes back to 0 and ends as source 1's sample, unless something wrapped or
+    saturated on the way.  (16384 of each and the unity link would be 32769 links: one more than a row may have.)"""
+    half = MAX_DEGREE // 2 - 1
+    links = [(0, 0, -MAX_GAIN)] * MAX_DEGREE + [(1, 0, -MAX_GAIN)] * half + [(1, 0, MAX_GAIN)] * half + \
+        [(1, 1, UNITY), (1, 0, 0)]
+    return 2, 2, links
+
+
+SPAN_TAIL = 7400                             # links of row 1 in ``span_links``: row_ptr[1] = 40000 stays inside them
+
+
+def span_links():
+    """``(n_src, n_out, links)`` for a ``row_ptr`` span above MAX_DEGREE written onto the device: row 0 holds exactly
+    MAX_DEGREE links whose sum is source 1's sample (a unity link, 16383 pairs of +-unity on source 2 that cancel, a
+    link of gain 0), row 1 the ``SPAN_TAIL`` links that follow them in the arrays, a quarter of source 3 each.  With
+    ``row_ptr[1]`` raised to 32769 or 40000 every index up to it names a real link, so a missing clamp to MAX_DEGREE
+    links shows as source 3 in row 0's sum -- never as a read outside the arrays."""
+    row0 = [(0, 1, UNITY)] + [(0, 2, UNITY), (0, 2, -UNITY)] * (MAX_DEGREE // 2 - 1) + [(0, 2, 0)]
+    assert len(row0) == MAX_DEGREE
+    return 4, 2, row0 + [(1, 3, UNITY // 4)] * SPAN_TAIL

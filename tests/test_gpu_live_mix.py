@@ -463,3 +463,89 @@ def test_wrong_arguments_raise_before_anything_is_launched(torch_cuda):
     got = medium.mix(src, out=out)
     assert bool((got == 9).all()) and medium.pos == 0
     assert afskmodem.LiveMedium is LiveMedium
+
+
+# ----------------------------------------------------------------------------------------- 10. the header's limits
+
+T_LIMIT = 2049                                                   # a tile and the first column of the next
+
+
+def test_a_row_of_32768_links_reaches_2147450880_and_a_balanced_one_returns_to_its_source(torch_cuda):
+    """The header promises that a row's sum fits int32 at 32768 links of gain +-65535: row 0 reaches that sum on a
+    source held at -32768 and clips; row 1 climbs half as high, comes back down and ends as its one unity source -- the
+    sum neither wrapped nor saturated on the way.  Rows at odd bases, the output beyond T poisoned."""
+    torch = torch_cuda
+    n_src, n_out, links = M.limit_links()
+    rng = np.random.default_rng(10)
+    host = np.stack([np.full(T_LIMIT + 3, -32768, np.int16), rng.integers(-32768, 32768, T_LIMIT + 3, dtype=np.int16)])
+    src, _ = strided(torch, n_src, T_LIMIT, 1)
+    upload(torch, host, src)
+    out, flat = strided(torch, n_out, T_LIMIT, 3, fill=POISON)
+    medium = LiveMedium(n_src, n_out, links, device=DEV)
+    assert np.diff(medium.row_ptr).tolist() == [M.MAX_DEGREE, M.MAX_DEGREE]
+    got = medium.mix(src, T_LIMIT, out=out)
+    want = model_of(medium, host, T_LIMIT)
+    same(got, want, "the limit rows")
+    assert (want[0] == 32767).all() and (want[1] == host[1, :T_LIMIT]).all()
+    rest = torch.ones_like(flat, dtype=torch.bool)
+    rest.as_strided((n_out, T_LIMIT), (T_LIMIT + 3, 1), 3).fill_(False)
+    assert bool((flat[rest] == POISON).all()), "out was written outside its T columns"
+
+
+@pytest.mark.parametrize("span", [M.MAX_DEGREE + 1, 40000])
+def test_a_row_ptr_span_above_32768_counts_the_first_32768_links(torch_cuda, span):
+    """``row_ptr[1]`` is overwritten where it lies.  The link arrays hold every entry up to it (row 1's links follow row
+    0's), so the kernel that forgot the clamp would add source 3 to row 0 -- a wrong sum, not a read out of bounds."""
+    torch = torch_cuda
+    n_src, n_out, links = M.span_links()
+    rng = np.random.default_rng(11)
+    host = rng.integers(-32768, 32768, (n_src, T_LIMIT), dtype=np.int16)
+    host[3] = np.where(np.abs(host[3]) < 4, 400, host[3])       # a quarter of it is never 0
+    src = torch.from_numpy(host).to(DEV)
+    medium = LiveMedium(n_src, n_out, links, device=DEV)
+    n = medium.n_links
+    assert medium.row_ptr.tolist() == [0, M.MAX_DEGREE, n] and span <= n == int(medium.d_link_src.numel())
+    medium.d_row_ptr.copy_(torch.tensor([0, span, n], dtype=torch.int32))
+    want = model_of(medium, host, T_LIMIT)
+    same(medium.mix(src), want, span)
+    assert (want[0] == host[1]).all()                             # its first 32768 links, and no more
+    one_more = (M.UNITY // 4 * host[3].astype(np.int64)) >> 15
+    assert (one_more != 0).all()
+
+
+def test_two_rows_of_2_20_columns(torch_cuda):
+    torch = torch_cuda
+    T = 1 << 20
+    host = np.random.default_rng(12).integers(-32768, 32768, (1, T), dtype=np.int16)
+    medium = LiveMedium(1, 2, [(0, 0, U), (1, 0, -U // 2)], device=DEV)
+    got = medium.mix(torch.from_numpy(host).to(DEV))
+    assert tuple(got.shape) == (2, T)
+    same(got, model_of(medium, host, T), "2^20 columns")
+    with pytest.raises(ValueError):
+        medium.mix(torch.zeros((1, T + 1), dtype=torch.int16, device=DEV))
+
+
+def test_a_source_length_at_every_residue_around_every_tile_edge(torch_cuda):
+    """T = 3 * 2048 - 3; source s ends at 2048 t + d, t in 0 ... 2, d in -9 ... 9 (below 0: silent).  Every source has
+    a unity row of its own, one more row hears them all; the sources are poisoned from their length on."""
+    torch = torch_cuda
+    T = 3 * 2048 - 3
+    lens = [2048 * t + d for t in range(3) for d in range(-9, 10)]
+    n = len(lens)
+    rng = np.random.default_rng(13)
+    host = rng.integers(-32768, 32768, (n, T + 3), dtype=np.int16)
+    for s, ln in enumerate(lens):
+        host[s, max(ln, 0):] = POISON
+    src, _ = strided(torch, n, T, 1)
+    upload(torch, host, src)
+    links = [(s, s, U) for s in range(n)] + [(n, s, U // 64) for s in range(n)]
+    medium = LiveMedium(n, n + 1, links, device=DEV)
+    out, flat = strided(torch, n + 1, T, 3, fill=POISON)
+    got = medium.mix(src, T, out=out, lengths=torch.tensor(lens, dtype=torch.int32, device=DEV))
+    want = model_of(medium, host, T, lens)
+    same(got, want, "lengths around the tile edges")
+    for s, ln in enumerate(lens):
+        assert not want[s, max(ln, 0):].any() and (want[s, : max(ln, 0)] == host[s, : max(ln, 0)]).all(), s
+    rest = torch.ones_like(flat, dtype=torch.bool)
+    rest.as_strided((n + 1, T), (T + 3, 1), 3).fill_(False)
+    assert bool((flat[rest] == POISON).all()), "out was written outside its T columns"

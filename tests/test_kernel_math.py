@@ -78,6 +78,25 @@ def test_float_quarter_division_of_the_modulator_is_exact():
         assert np.array_equal(got, (x0.astype(np.uint32) // q)), q
 
 
+def test_float_quarter_division_of_the_modulator_is_exact_over_the_whole_domain():
+    """The same floor over the modulator's real domain: every quarter width q = bit_frames / 4 up to 2^18 (bit_frames up
+    to 2^20, include/afsk_amd.h) and x0 < bit_frames + 16384 (the block's phase inside its first symbol plus the offset
+    inside the block).  x0 + 0.5 is exact in float below 2^23 and a float multiply by a positive constant is monotone,
+    so the floor is right everywhere once it is right either side of every multiple of q: at k * q - 1 and k * q."""
+    q = np.arange(1, (1 << 18) + 1, dtype=np.int64)
+    rcp = np.float32(1.0) / q.astype(np.float32)
+    k, checked = 1, 0
+    while q.size:
+        for x, want in ((k * q - 1, k - 1), (k * q, k)):
+            got = ((x.astype(np.float32) + np.float32(0.5)) * rcp).astype(np.int64)
+            assert np.array_equal(got, np.full(q.size, want)), (k, q[got != want][:4])
+        checked += 2 * q.size
+        k += 1
+        keep = k * q < 4 * q + 16384                               # the next multiple is still inside the domain
+        q, rcp = q[keep], rcp[keep]
+    assert k > 16384 and checked > 2 * 4 * (1 << 18)
+
+
 TX_BFS = tuple(bf for bf in range(4, 48001, 4) if 48000 % bf == 0)      # the live transmitter's 48 rates
 
 

@@ -234,3 +234,37 @@ def test_a_medium_checks_its_links_before_it_needs_a_device():
     if _native.device_count() <= 0:
         with pytest.raises(_native.AfskNativeError, match="no HIP device"):
             live.LiveMedium(4, 2, [(0, 1, U)])
+
+
+# ---------------------------------------------------------------------------------- the model at the header's limits
+
+def test_the_model_at_32768_links_reaches_the_header_limit_and_clips():
+    """The tables tests/test_gpu_live_mix.py mixes on the device, through the model at a few columns: a row of 32768
+    links at -65535 on -32768 sums to 2147450880 -- the model asserts every partial sum below 2^31 -- and clips; the
+    balanced row comes back to its unity source."""
+    n_src, n_out, links = M.limit_links()
+    row_ptr, link_src, gain = live.medium_csr(n_out, links)
+    assert np.diff(row_ptr).tolist() == [M.MAX_DEGREE, M.MAX_DEGREE]
+    assert M.MAX_DEGREE * ((-M.MAX_GAIN * -32768) >> 15) == 2147450880 == 2 ** 31 - 32768
+    assert (M.MAX_DEGREE // 2 - 1) * ((-M.MAX_GAIN * -32768) >> 15) == 1073659905
+    rng = np.random.default_rng(12)
+    src = np.stack([np.full(5, -32768, np.int16), rng.integers(-32768, 32768, 5, dtype=np.int16)])
+    got = M.mix(src, row_ptr, link_src, gain, n_out, 5)
+    assert (got[0] == 32767).all() and (got[1] == src[1]).all()
+
+
+def test_the_model_counts_the_first_32768_links_of_a_longer_span():
+    n_src, n_out, links = M.span_links()
+    row_ptr, link_src, gain = live.medium_csr(n_out, links)
+    n = link_src.size
+    assert row_ptr.tolist() == [0, M.MAX_DEGREE, n] and n == M.MAX_DEGREE + M.SPAN_TAIL > 40000
+    rng = np.random.default_rng(13)
+    src = rng.integers(-32768, 32768, (n_src, 6), dtype=np.int16)
+    src[3] = np.array([4, -4, 400, -400, 32767, -32768])          # a quarter of it is never 0
+    for span in (M.MAX_DEGREE, M.MAX_DEGREE + 1, 40000):
+        got = M.mix(src, [0, span, n], link_src, gain, n_out, 6)
+        assert (got[0] == src[1]).all(), span                     # row 0: its first 32768 links and no more
+        tail = (n - span) * ((M.UNITY // 4 * src[3].astype(np.int64)) >> 15)
+        assert (got[1] == np.clip(tail, -32768, 32767)).all(), span
+    # the clamp is what keeps source 3 out of row 0: one more link would be heard
+    assert (((M.UNITY // 4) * src[3].astype(np.int64)) >> 15 != 0).all()
