@@ -279,6 +279,17 @@ LIVE_MIX_SIGNATURES = {
     "afsk_live_mix_check": (C.c_int, [_i32p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
 }
 
+# The delayed live medium (afsk_live_mix_delayed, afsk_live_mix_delayed_check), likewise: afsk_live_mix's arguments with
+# the DEVICE delay array behind the gains and the history and its length behind the position.
+LIVE_DELAY_SIGNATURES = {
+    "afsk_live_mix_delayed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p]),
+    "afsk_live_mix_delayed_check": (C.c_int, [_i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+}
+LIVE_DELAY_MIN_HIST, LIVE_DELAY_MAX_HIST = 8, 1 << 20
+
 # The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept), likewise.
 LIVE_DEDUP_SIGNATURES = {
     "afsk_live_dedup_layout": (C.c_int, [C.c_int32, C.c_int32, _i64p]),
@@ -319,7 +330,7 @@ def lib() -> C.CDLL:
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
                                   *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items(),
-                                  *LIVE_DEDUP_SIGNATURES.items()):
+                                  *LIVE_DEDUP_SIGNATURES.items(), *LIVE_DELAY_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

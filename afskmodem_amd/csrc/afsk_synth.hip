@@ -329,3 +329,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept) closes the unit, behind afsk_live_relay.hip:
 // it launches that file's order kernel and queues with its RelayArgs and RelayRated.
 #include "afsk_live_dedup.hip"
+
+// The delayed live medium (afsk_live_mix_delayed, afsk_live_mix_delayed_check) comes behind afsk_live_mix.hip, whose
+// MixArgs, constants and advance kernel it uses.
+#include "afsk_live_delay.hip"

@@ -1732,7 +1732,7 @@ def medium_csr(n_out: int, links) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     int32, the links of a row in the order they were given.  An ``out`` outside 0 ... n_out - 1 is a ValueError; sources
     and gains are checked by ``afsk_live_mix_check``."""
     rows = [[] for _ in range(int(n_out))]
-    for o, s, g in links:
+    for o, s, g, *_ in links:                                   # (a fourth entry is the link's delay: medium_delays)
         o = int(o)
         if not 0 <= o < n_out:
             raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
@@ -1747,12 +1747,50 @@ def medium_csr(n_out: int, links) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return row_ptr, clip([s for s, _ in flat]), clip([g for _, g in flat])
 
 
-def medium_matrix_links(gain, n_channels: int, extra=()) -> tuple[int, int, list]:
+def medium_delay(delay) -> int:
+    """A link's delay (or a medium's ``max_delay``) in samples: an int is samples already, a float is seconds at 48000
+    samples/s (``round(delay * 48000)``) -- ``dedup_window``'s convention."""
+    if isinstance(delay, (bool, np.bool_)) or not isinstance(delay, (int, float, np.integer, np.floating)):
+        raise TypeError("a delay is seconds (a float) or samples (an int)")
+    if isinstance(delay, (float, np.floating)):
+        if not np.isfinite(delay):
+            raise ValueError("a delay must be finite")
+        delay = round(float(delay) * _native.SAMPLE_RATE)
+    return int(delay)
+
+
+def medium_delays(n_out: int, links) -> np.ndarray:
+    """``medium_csr``'s sibling: the delays in samples (int32 ``[n_links]``, in ``link_src``'s order) of links given as
+    ``(out, src, gain)`` -- delay 0 -- or ``(out, src, gain, delay)``.  The range 0 ... hist_len is checked by
+    ``afsk_live_mix_delayed_check``."""
+    rows = [[] for _ in range(int(n_out))]
+    for link in links:
+        if len(link) not in (3, 4):
+            raise ValueError("a link is (out, src, gain) or (out, src, gain, delay)")
+        o = int(link[0])
+        if not 0 <= o < n_out:
+            raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
+        rows[o].append(medium_delay(link[3]) if len(link) == 4 else 0)
+    flat = [d for r in rows for d in r]
+    return np.clip(np.asarray(flat, np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+
+
+def medium_hist_len(max_delay: int) -> int:
+    """The history a delayed medium keeps per source row: the power of two at or above ``max_delay``, at least 8."""
+    n = _native.LIVE_DELAY_MIN_HIST
+    while n < max_delay:
+        n *= 2
+    return n
+
+
+def medium_matrix_links(gain, n_channels: int, extra=(), delay=None) -> tuple[int, int, list]:
     """``(n_src, n_out, links)`` of a station-level gain matrix ``gain`` [n_listeners, n_stations] expanded over the
     ``n_channels`` channels every station has: output row ``l * P + c`` hears source row ``s * P + c`` at ``gain[l][s]``;
     a zero entry makes no link (a listener that station does not reach).  ``extra``: source rows behind the stations'
     that every listener hears -- an int E for E groups of P rows at unity (group e's row c on channel c), or a sequence
-    of gains, one per group."""
+    of gains, one per group.  ``delay`` (None: the links are triples): one value for every link, or a matrix
+    [n_listeners, n_stations + the extra groups] -- ints are samples, floats seconds -- and the links are
+    ``(out, src, gain, delay in samples)``."""
     g = np.asarray(gain)
     if g.ndim != 2 or g.size == 0:
         raise ValueError("gain must be an [n_listeners, n_stations] matrix")
@@ -1764,6 +1802,16 @@ def medium_matrix_links(gain, n_channels: int, extra=()) -> tuple[int, int, list
     q = [[medium_gain_q15(g[l, s].item()) for s in range(n_s)] + extras for l in range(n_l)]
     links = [(l * P + c, s * P + c, q[l][s]) for l in range(n_l) for c in range(P) for s in range(n_s + len(extras))
              if q[l][s] != 0]
+    if delay is not None:
+        try:
+            d = np.asarray(delay, dtype=object)                 # (every entry keeps its type: samples or seconds)
+        except ValueError:
+            d = np.empty(0, dtype=object)                       # ragged rows
+        if d.ndim == 0:
+            d = np.full((n_l, n_s + len(extras)), d.item(), dtype=object)
+        if d.shape != (n_l, n_s + len(extras)):
+            raise ValueError(f"delay must be one value or a [{n_l}, {n_s + len(extras)}] matrix (the extra groups included)")
+        links = [(o, s, g, medium_delay(d[o // P, s // P])) for o, s, g in links]
     return (n_s + len(extras)) * P, n_l * P, links
 
 
@@ -1784,10 +1832,18 @@ class LiveMedium:
     gets the noise of ``batch.add_noise_batch`` stream ``noise_idx_base + r`` with ``seed``, sample index ``pos + j``;
     every mix then advances ``pos`` by T on the device, so two mixes of T equal one of 2 T.  A medium without noise
     keeps no position (``pos`` is 0) and its mix is one launch.  Like a receiver or a transmitter, the medium must outlive
-    every graph that captured its ``mix``: the graph reads its device arrays."""
+    every graph that captured its ``mix``: the graph reads its device arrays.
+
+    A link may be ``(out, src, gain, delay)`` (``afsk_live_mix_delayed``): ``out`` hears ``src`` as it was
+    ``delay`` earlier -- an int is samples, a float seconds at 48000 samples/s -- across mixes; the same source on two
+    links at two delays is an echo.  ``max_delay`` (samples or seconds; None: the largest link delay) sizes the history
+    the medium keeps of every source row: ``hist_len = max(8, the power of two >= max_delay)`` samples, at most 2^20; a
+    link delay above ``max_delay`` is a ValueError.  A medium is ``delayed`` when ``max_delay > 0`` or a link has a
+    delay: it keeps a position whether it has noise or not, every mix is three launches, and ``reset`` forgets what was
+    sent.  A medium that is not delayed allocates and launches exactly what it did before delays existed."""
 
     def __init__(self, n_src: int, n_out: int, links, device=None, noise_scale_q24=None, seed: int = 0,
-                 noise_idx_base: int = 0):
+                 noise_idx_base: int = 0, max_delay=None):
         torch = batch._torch()
         self.n_src, self.n_out = int(n_src), int(n_out)
         if self.n_src < 0 or self.n_out < 0:
@@ -1795,11 +1851,29 @@ class LiveMedium:
         if not 0 <= int(seed) < 1 << 32 or not 0 <= int(noise_idx_base) < 1 << 32:
             raise ValueError("seed and noise_idx_base must be uint32")
         self.seed, self.noise_idx_base = int(seed), int(noise_idx_base)
+        links = list(links)
         self.row_ptr, self.link_src, self.link_gain_q15 = medium_csr(self.n_out, links)
+        self.link_delay = medium_delays(self.n_out, links)
         self.n_links = int(self.link_src.size)
-        _native.check(_native.lib().afsk_live_mix_check(
-            _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
-            _i32_ptr(self.link_gain_q15) if self.n_links else None, self.n_out, self.n_src, self.n_links))
+        largest = int(self.link_delay.max(initial=0))
+        self.max_delay = largest if max_delay is None else medium_delay(max_delay)
+        if not 0 <= self.max_delay <= _native.LIVE_DELAY_MAX_HIST:
+            raise ValueError("max_delay must lie in 0 ... 2^20 samples")
+        if largest > self.max_delay:
+            raise ValueError(f"a link has a delay of {largest} samples, above max_delay = {self.max_delay}")
+        self.delayed = self.max_delay > 0 or bool(self.link_delay.any())
+        self.hist_len = medium_hist_len(self.max_delay) if self.delayed else 0
+        self.history_bytes = 2 * self.n_src * self.hist_len
+        if self.delayed:
+            _native.check(_native.lib().afsk_live_mix_delayed_check(
+                _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
+                _i32_ptr(self.link_gain_q15) if self.n_links else None,
+                _i32_ptr(self.link_delay) if self.n_links else None, self.n_out, self.n_src, self.n_links,
+                self.hist_len))
+        else:
+            _native.check(_native.lib().afsk_live_mix_check(
+                _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
+                _i32_ptr(self.link_gain_q15) if self.n_links else None, self.n_out, self.n_src, self.n_links))
         scale = None
         if noise_scale_q24 is not None:
             scale = np.asarray(noise_scale_q24)
@@ -1816,13 +1890,18 @@ class LiveMedium:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
         self.d_row_ptr, self.d_link_src, self.d_link_gain_q15 = up(self.row_ptr), up(self.link_src), up(self.link_gain_q15)
         self.d_noise_scale_q24 = None if scale is None else up(scale)
-        self.d_pos = None if scale is None else torch.zeros(1, dtype=torch.int64, device=self.device)
+        keeps_pos = scale is not None or self.delayed
+        self.d_pos = torch.zeros(1, dtype=torch.int64, device=self.device) if keeps_pos else None
+        self.d_link_delay = up(self.link_delay) if self.delayed else None
+        self.d_history = torch.zeros((self.n_src, self.hist_len), dtype=torch.int16, device=self.device) \
+            if self.delayed else None
 
     @classmethod
-    def from_matrix(cls, gain, n_channels: int, extra=(), **kw) -> "LiveMedium":
-        """The medium of ``medium_matrix_links(gain, n_channels, extra)``: ``gain`` [n_listeners, n_stations] per station,
-        expanded over the stations' ``n_channels`` channels; keywords as the constructor's."""
-        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra)
+    def from_matrix(cls, gain, n_channels: int, extra=(), delay=None, **kw) -> "LiveMedium":
+        """The medium of ``medium_matrix_links(gain, n_channels, extra, delay)``: ``gain`` [n_listeners, n_stations] per
+        station, expanded over the stations' ``n_channels`` channels; ``delay`` one value or a matrix shaped like ``gain``
+        plus the extra groups; keywords as the constructor's."""
+        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra, delay)
         return cls(n_src, n_out, links, **kw)
 
     @property
@@ -1831,7 +1910,8 @@ class LiveMedium:
         return 0 if self.d_pos is None else int(self.d_pos.item())
 
     def reset(self, pos: int = 0, stream=None) -> None:
-        """Set the position (the noise's sample index) to ``pos``, 0 ... 2^63 - 1; asynchronous on ``stream``."""
+        """Set the position (the noise's sample index) to ``pos``, 0 ... 2^63 - 1; a delayed medium also forgets what was
+        sent (its history becomes zeros).  Asynchronous on ``stream``."""
         pos = int(pos)
         if not 0 <= pos < 1 << 63:
             raise ValueError("pos must lie in 0 ... 2^63 - 1")
@@ -1842,6 +1922,38 @@ class LiveMedium:
         torch = batch._torch()
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             self.d_pos.fill_(pos)
+            if self.delayed:
+                self.d_history.zero_()
+
+    def state(self):
+        """``(pos, history)`` for a restart (host reads: it synchronises): ``history`` is an int16 numpy array
+        ``[n_src, hist_len]`` in time order, oldest first -- column i is what the sources held at medium time
+        ``pos - hist_len + i``.  A medium that is not delayed has ``hist_len`` 0."""
+        pos = self.pos
+        if not self.delayed:
+            return pos, np.zeros((self.n_src, 0), np.int16)
+        ring = self.d_history.cpu().numpy()
+        return pos, np.ascontiguousarray(np.roll(ring, -(pos % self.hist_len), axis=1))
+
+    def load_state(self, pos: int, history, stream=None) -> None:
+        """Put back what ``state`` of a medium with the same sources and ``hist_len`` returned; asynchronous on
+        ``stream``."""
+        pos = int(pos)
+        if not 0 <= pos < 1 << 63:
+            raise ValueError("pos must lie in 0 ... 2^63 - 1")
+        history = np.asarray(history)
+        if history.dtype != np.int16 or history.shape != (self.n_src, self.hist_len):
+            raise ValueError(f"history must be int16 [{self.n_src}, {self.hist_len}]")
+        if self.d_pos is None:
+            if pos:
+                raise ValueError("a medium without noise keeps no position")
+            return
+        torch = batch._torch()
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            self.d_pos.fill_(pos)
+            if self.delayed:
+                ring = np.ascontiguousarray(np.roll(history, pos % self.hist_len, axis=1))
+                self.d_history.copy_(torch.from_numpy(ring))
 
     def mix(self, src, T: int | None = None, out=None, lengths=None, stream=None):
         """Mix columns ``[0, T)`` of ``src`` ([n_src, >= T] int16 CUDA tensor, contiguous rows, any row stride; ``T`` None:
@@ -1874,6 +1986,18 @@ class LiveMedium:
                 batch._order_after_current(stream, dev)
             if lens_up and stream is not None:
                 lens.record_stream(stream)
+            if self.delayed:
+                _native.check(_native.lib().afsk_live_mix_delayed(
+                    src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,
+                    None if lens is None else lens.data_ptr(), self.d_row_ptr.data_ptr(),
+                    self.d_link_src.data_ptr() if self.n_links else None,
+                    self.d_link_gain_q15.data_ptr() if self.n_links else None,
+                    self.d_link_delay.data_ptr() if self.n_links else None, self.n_links,
+                    out.data_ptr(), int(out.stride(0)), self.n_out, T,
+                    None if self.d_noise_scale_q24 is None else self.d_noise_scale_q24.data_ptr(), self.seed,
+                    self.noise_idx_base, self.d_pos.data_ptr(), self.d_history.data_ptr() if self.n_src else None,
+                    self.hist_len, batch._stream_ptr(stream, dev)))
+                return out[:, :T]
             _native.check(_native.lib().afsk_live_mix(
                 src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,
                 None if lens is None else lens.data_ptr(), self.d_row_ptr.data_ptr(),

@@ -1306,8 +1306,8 @@ extern int afsk_live_push_auto_muted(afsk_live *live, const int16_t *chunk, int6
  *                       start at 0, falls, or does not end at n_links; a row with more than 32768 links; a source
  *                       outside 0 ... n_src - 1; a gain outside -65535 ... 65535; a negative count or a NULL array
  *                       (the link arrays may be NULL when n_links is 0).
- * Not part of the rule: a delay per link, filters or fading, more than one source matrix per call, a length per output
- * row.
+ * Not part of the rule: filters or fading, more than one source matrix per call, a length per output row.  (A delay
+ * per link: afsk_live_mix_delayed, below.)
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_MIX_SIGNATURES.)
  */
 extern int afsk_live_mix(const int16_t *src, int64_t src_row_stride, int32_t n_src, const int32_t *d_src_lens_or_null,
@@ -1317,6 +1317,62 @@ extern int afsk_live_mix(const int16_t *src, int64_t src_row_stride, int32_t n_s
                          int64_t *d_pos_or_null, void *hip_stream);
 extern int afsk_live_mix_check(const int32_t *h_row_ptr, const int32_t *h_link_src, const int32_t *h_link_gain_q15,
                                int32_t n_out, int32_t n_src, int32_t n_links);
+
+/*
+ * The delayed live medium (added after ABI version 2; the version is unchanged): afsk_live_mix with a delay in samples
+ * per link -- the latency between stations that makes carrier sense imperfect (a station senses its neighbour only D
+ * samples after it keyed up), and multipath (the same source on two links at two delays).  All of it is integer and
+ * sample-exact.
+ *
+ * State, both on the DEVICE and owned by the caller:
+ *   pos      int64 [1], as the noisy medium keeps it: the medium time the next mix begins at.
+ *   history  int16 [n_src, hist_len], contiguous; hist_len a power of two in 8 ... 2^20.  The sample source s had at
+ *            medium time t lies at history[s][t & (hist_len - 1)].  All zeros: nothing was sent yet.
+ * X_s(t) is source row s as ONE signal over medium time: column j of the mix that began at position p is time p + j, a
+ * column at or beyond that mix's clamp(src_lens[s], 0, T) is 0 (and is not read), and everything before the first mix,
+ * or since the history was last zeroed, is 0.
+ *
+ *  afsk_live_mix_delayed   afsk_live_mix's arguments plus d_link_delay (DEVICE int32 [n_links], read when the kernel
+ *                          runs), d_history and hist_len; d_pos is required.  With T = n_samples and pos = *d_pos read
+ *                          when the kernel runs, for output row r and column j in [0, T):
+ *                            d_k        = clamp(link_delay[k], 0, hist_len)
+ *                            x_k(j)     = X_{link_src[k]}(pos + j - d_k)    (0 for a source outside 0 ... n_src - 1)
+ *                            term_k(j)  = (g_k * x_k(j)) >> 15
+ *                          and lo, hi, g_k, the clamp of the sum, out[r][j] and the noise on top exactly as
+ *                          afsk_live_mix defines them.  x_k(j) comes from src when j - d_k >= 0 and from the history
+ *                          otherwise.  Behind the mix, in order on hip_stream, a second launch writes
+ *                            history[s][(pos + j) & (hist_len - 1)] = (j < len_s ? src[s][j] : 0)
+ *                          for j in [max(0, T - hist_len), T) and every source row s (no launch when n_src is 0), and
+ *                          a third, of one thread, adds T to pos.  The history is written only after the mix has read
+ *                          it, so a delay equal to hist_len is legal: it reads the slot about to be overwritten.
+ *                          With every delay 0 the output is afsk_live_mix's, bit for bit, noise included; two mixes
+ *                          of T equal one of 2 T; T may be smaller than, equal to or larger than hist_len.  A delay
+ *                          or a source out of range in the device table is clamped or ignored as written above before
+ *                          anything is read through it.
+ *                          AFSK_E_INVALID_ARG: everything afsk_live_mix refuses; a hist_len that is not a power of two
+ *                          in 8 ... 2^20; a NULL d_pos; a NULL d_history when n_src > 0; a NULL d_link_delay when
+ *                          n_links > 0; a history whose bytes [d_history, + 2 * n_src * hist_len) overlap src's or
+ *                          out's byte range; n_out * ceil(T / 2048) or n_src * ceil(min(T, hist_len) / 2048) above
+ *                          2^31 - 1.  n_samples == 0 or n_out == 0 launches nothing and leaves pos and the history
+ *                          as they were.  Otherwise three launches (live_mix_delay_kernel, live_mix_history_kernel,
+ *                          live_mix_advance_kernel), no allocation, no host read: capturable.
+ *  afsk_live_mix_delayed_check  host-only (no device needed), HOST arrays: afsk_live_mix_check's rules, and
+ *                          AFSK_E_INVALID_ARG for a hist_len as above, a NULL h_link_delay when n_links > 0 or a delay
+ *                          outside 0 ... hist_len.
+ * Not part of the rule: fractional-sample delays, delays that change while the medium runs (the table is the caller's,
+ * but the history holds no more than hist_len samples), filters or fading, clearing the history of single rows, a length
+ * per output row, more than one source matrix per call.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_DELAY_SIGNATURES.)
+ */
+extern int afsk_live_mix_delayed(const int16_t *src, int64_t src_row_stride, int32_t n_src,
+                                 const int32_t *d_src_lens_or_null, const int32_t *d_row_ptr, const int32_t *d_link_src,
+                                 const int32_t *d_link_gain_q15, const int32_t *d_link_delay, int32_t n_links,
+                                 int16_t *out, int64_t out_row_stride, int32_t n_out, int32_t n_samples,
+                                 const int32_t *d_noise_scale_q24_or_null, uint32_t noise_seed, uint32_t noise_idx_base,
+                                 int64_t *d_pos, int16_t *d_history, int32_t hist_len, void *hip_stream);
+extern int afsk_live_mix_delayed_check(const int32_t *h_row_ptr, const int32_t *h_link_src,
+                                       const int32_t *h_link_gain_q15, const int32_t *h_link_delay, int32_t n_out,
+                                       int32_t n_src, int32_t n_links, int32_t hist_len);
 
 /*
  * The duplicate filter (added after ABI version 2; the version is unchanged): the list every digipeater keeps so that
