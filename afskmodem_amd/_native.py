@@ -290,6 +290,18 @@ LIVE_DELAY_SIGNATURES = {
 }
 LIVE_DELAY_MIN_HIST, LIVE_DELAY_MAX_HIST = 8, 1 << 20
 
+# The filtered live medium (afsk_live_mix_filtered, afsk_live_mix_filtered_check), likewise: the delayed entries'
+# arguments with the DEVICE filter index per link behind the delays and the filter table (filter_ptr, filter_taps,
+# n_filters, n_taps) behind the history's length.
+_delayed_args = LIVE_DELAY_SIGNATURES["afsk_live_mix_delayed"][1]
+LIVE_FIR_SIGNATURES = {
+    "afsk_live_mix_filtered": (C.c_int, _delayed_args[:8] + [C.c_void_p] + _delayed_args[8:19]
+                               + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + _delayed_args[19:]),
+    "afsk_live_mix_filtered_check": (C.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, _i32p, _i16p, C.c_int32, C.c_int32]),
+}
+LIVE_FIR_MAX_TAPS, LIVE_FIR_MAX_L1, LIVE_FIR_UNITY = 256, 65535, 16384
+
 # The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept), likewise.
 LIVE_DEDUP_SIGNATURES = {
     "afsk_live_dedup_layout": (C.c_int, [C.c_int32, C.c_int32, _i64p]),
@@ -330,7 +342,8 @@ def lib() -> C.CDLL:
                                   *LIVE_AUTO_SIGNATURES.items(), *LIVE_RELAY_SIGNATURES.items(),
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
                                   *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items(),
-                                  *LIVE_DEDUP_SIGNATURES.items(), *LIVE_DELAY_SIGNATURES.items()):
+                                  *LIVE_DEDUP_SIGNATURES.items(), *LIVE_DELAY_SIGNATURES.items(),
+                                  *LIVE_FIR_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -333,3 +333,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The delayed live medium (afsk_live_mix_delayed, afsk_live_mix_delayed_check) comes behind afsk_live_mix.hip, whose
 // MixArgs, constants and advance kernel it uses.
 #include "afsk_live_delay.hip"
+
+// The filtered live medium (afsk_live_mix_filtered, afsk_live_mix_filtered_check) comes behind afsk_live_delay.hip,
+// whose MixDelayArgs, mix_add8 and history kernel it uses.
+#include "afsk_live_fir.hip"

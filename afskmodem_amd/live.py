@@ -1732,8 +1732,8 @@ def medium_csr(n_out: int, links) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     int32, the links of a row in the order they were given.  An ``out`` outside 0 ... n_out - 1 is a ValueError; sources
     and gains are checked by ``afsk_live_mix_check``."""
     rows = [[] for _ in range(int(n_out))]
-    for o, s, g, *_ in links:                                   # (a fourth entry is the link's delay: medium_delays)
-        o = int(o)
+    for o, s, g, *_ in links:                                   # (a fourth entry is the link's delay: medium_delays;
+        o = int(o)                                              # a fifth its filter: medium_filters)
         if not 0 <= o < n_out:
             raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
         rows[o].append((int(s), medium_gain_q15(g)))
@@ -1783,14 +1783,76 @@ def medium_hist_len(max_delay: int) -> int:
     return n
 
 
-def medium_matrix_links(gain, n_channels: int, extra=(), delay=None) -> tuple[int, int, list]:
+def medium_filter_q14(taps) -> list[int]:
+    """One filter as the C entry takes it: a sequence of taps, an int is Q14 already (unity 16384), a float is
+    ``round(tap * 16384)``.  1 ... 256 taps, each inside -32768 ... 32767, their sum of magnitudes at most 65535."""
+    out = []
+    for t in taps:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)):
+            raise TypeError("a tap is an int (Q14) or a float")
+        if isinstance(t, (float, np.floating)):
+            if not np.isfinite(t):
+                raise ValueError("a tap must be finite")
+            t = round(float(t) * _native.LIVE_FIR_UNITY)
+        out.append(int(t))
+    if not 1 <= len(out) <= _native.LIVE_FIR_MAX_TAPS:
+        raise ValueError(f"a filter has 1 ... {_native.LIVE_FIR_MAX_TAPS} taps, not {len(out)}")
+    if min(out) < -32768 or max(out) > 32767:
+        raise ValueError("a tap must lie in -32768 ... 32767 (Q14: -2 ... just below 2)")
+    if sum(abs(t) for t in out) > _native.LIVE_FIR_MAX_L1:
+        raise ValueError(f"the taps' magnitudes sum to {sum(abs(t) for t in out)}, above {_native.LIVE_FIR_MAX_L1}")
+    return out
+
+
+def medium_filters(n_out: int, links) -> np.ndarray:
+    """``medium_delays``' sibling: the filter index (int32 ``[n_links]``, in ``link_src``'s order, -1 for none) of links
+    given as ``(out, src, gain)``, ``(out, src, gain, delay)`` or ``(out, src, gain, delay, filter)`` with ``filter`` an
+    index or None.  The range -1 ... n_filters - 1 is checked by ``afsk_live_mix_filtered_check``."""
+    rows = [[] for _ in range(int(n_out))]
+    for link in links:
+        if len(link) not in (3, 4, 5):
+            raise ValueError("a link is (out, src, gain), (out, src, gain, delay) or (out, src, gain, delay, filter)")
+        o = int(link[0])
+        if not 0 <= o < n_out:
+            raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
+        f = link[4] if len(link) == 5 else None
+        if isinstance(f, (bool, np.bool_)) or not (f is None or isinstance(f, (int, np.integer))):
+            raise TypeError("a link's filter is an index or None")
+        rows[o].append(-1 if f is None else int(f))
+    flat = [f for r in rows for f in r]
+    return np.clip(np.asarray(flat, np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+
+
+def fir_design(n_taps: int, low_hz: float = 0, high_hz: float | None = None) -> list[int]:
+    """The Hamming windowed sinc of ``n_taps`` taps (1 ... 256) at 48000 samples/s as Q14 ints: a low-pass below
+    ``high_hz`` (None: 24000) when ``low_hz`` is 0, the band-pass ``low_hz`` ... ``high_hz`` otherwise --
+    ``h[n] = (2 fh / 48000 sinc(2 fh / 48000 m) - [the same with fl]) hamming(K)[n]``, ``m = n - (K - 1) / 2``, rounded
+    to Q14.  A design whose magnitudes sum above 65535 is a ValueError."""
+    K = int(n_taps)
+    if not 1 <= K <= _native.LIVE_FIR_MAX_TAPS:
+        raise ValueError(f"n_taps must lie in 1 ... {_native.LIVE_FIR_MAX_TAPS}")
+    rate = float(_native.SAMPLE_RATE)
+    fh = rate / 2 if high_hz is None else float(high_hz)
+    fl = float(low_hz)
+    if not 0 <= fl < fh <= rate / 2:
+        raise ValueError("0 <= low_hz < high_hz <= 24000 is required")
+    m = np.arange(K, dtype=np.float64) - (K - 1) / 2
+    h = 2 * fh / rate * np.sinc(2 * fh / rate * m)
+    if fl > 0:
+        h -= 2 * fl / rate * np.sinc(2 * fl / rate * m)
+    return medium_filter_q14([float(v) for v in h * np.hamming(K)])
+
+
+def medium_matrix_links(gain, n_channels: int, extra=(), delay=None, filter=None) -> tuple[int, int, list]:
     """``(n_src, n_out, links)`` of a station-level gain matrix ``gain`` [n_listeners, n_stations] expanded over the
     ``n_channels`` channels every station has: output row ``l * P + c`` hears source row ``s * P + c`` at ``gain[l][s]``;
     a zero entry makes no link (a listener that station does not reach).  ``extra``: source rows behind the stations'
     that every listener hears -- an int E for E groups of P rows at unity (group e's row c on channel c), or a sequence
     of gains, one per group.  ``delay`` (None: the links are triples): one value for every link, or a matrix
     [n_listeners, n_stations + the extra groups] -- ints are samples, floats seconds -- and the links are
-    ``(out, src, gain, delay in samples)``."""
+    ``(out, src, gain, delay in samples)``.  ``filter`` (None: no fifth entry): one filter index for every link, or a
+    matrix shaped like ``delay``'s whose entries are an index, -1 or None; the links are then
+    ``(out, src, gain, delay in samples, filter or None)``."""
     g = np.asarray(gain)
     if g.ndim != 2 or g.size == 0:
         raise ValueError("gain must be an [n_listeners, n_stations] matrix")
@@ -1812,6 +1874,21 @@ def medium_matrix_links(gain, n_channels: int, extra=(), delay=None) -> tuple[in
         if d.shape != (n_l, n_s + len(extras)):
             raise ValueError(f"delay must be one value or a [{n_l}, {n_s + len(extras)}] matrix (the extra groups included)")
         links = [(o, s, g, medium_delay(d[o // P, s // P])) for o, s, g in links]
+    if filter is not None:
+        try:
+            f = np.asarray(filter, dtype=object)
+        except ValueError:
+            f = np.empty(0, dtype=object)                       # ragged rows
+        if f.ndim == 0:
+            f = np.full((n_l, n_s + len(extras)), f.item(), dtype=object)
+        if f.shape != (n_l, n_s + len(extras)):
+            raise ValueError(f"filter must be one index or a [{n_l}, {n_s + len(extras)}] matrix (the extra groups included)")
+
+        def index(v):
+            if isinstance(v, (bool, np.bool_)) or not (v is None or isinstance(v, (int, np.integer))):
+                raise TypeError("a link's filter is an index, -1 or None")
+            return None if v is None or v == -1 else int(v)
+        links = [(*x[:3], x[3] if len(x) == 4 else 0, index(f[x[0] // P, x[1] // P])) for x in links]
     return (n_s + len(extras)) * P, n_l * P, links
 
 
@@ -1840,10 +1917,17 @@ class LiveMedium:
     the medium keeps of every source row: ``hist_len = max(8, the power of two >= max_delay)`` samples, at most 2^20; a
     link delay above ``max_delay`` is a ValueError.  A medium is ``delayed`` when ``max_delay > 0`` or a link has a
     delay: it keeps a position whether it has noise or not, every mix is three launches, and ``reset`` forgets what was
-    sent.  A medium that is not delayed allocates and launches exactly what it did before delays existed."""
+    sent.  A medium that is not delayed allocates and launches exactly what it did before delays existed.
+
+    ``filters`` (``afsk_live_mix_filtered``): a sequence of FIR filters, each a sequence of 1 ... 256
+    taps -- an int is Q14 (unity 16384), a float ``round(tap * 16384)``, the magnitudes summing to at most 65535;
+    ``fir_design`` makes band limits.  A link ``(out, src, gain, delay, filter)`` hears ``src`` through filter number
+    ``filter`` (None: unfiltered): ``clamp((sum_i h[i] * x[t - delay - i]) >> 14)`` takes the sample's place.  A medium
+    with filters is ``filtered`` and also ``delayed``; a filtered link reaches ``delay + taps - 1`` samples back, and
+    ``hist_len`` covers the largest reach.  A medium without filters allocates and launches exactly what it did."""
 
     def __init__(self, n_src: int, n_out: int, links, device=None, noise_scale_q24=None, seed: int = 0,
-                 noise_idx_base: int = 0, max_delay=None):
+                 noise_idx_base: int = 0, max_delay=None, filters=None):
         torch = batch._torch()
         self.n_src, self.n_out = int(n_src), int(n_out)
         if self.n_src < 0 or self.n_out < 0:
@@ -1853,18 +1937,42 @@ class LiveMedium:
         self.seed, self.noise_idx_base = int(seed), int(noise_idx_base)
         links = list(links)
         self.row_ptr, self.link_src, self.link_gain_q15 = medium_csr(self.n_out, links)
-        self.link_delay = medium_delays(self.n_out, links)
+        self.link_delay = medium_delays(self.n_out, [x[:4] for x in links])
+        self.link_filter = medium_filters(self.n_out, links)
         self.n_links = int(self.link_src.size)
-        largest = int(self.link_delay.max(initial=0))
+        taps = [medium_filter_q14(h) for h in (() if filters is None else filters)]
+        self.n_filters = len(taps)
+        self.filtered = self.n_filters > 0
+        self.filter_ptr = np.zeros(self.n_filters + 1, np.int32)
+        self.filter_ptr[1:] = np.cumsum([len(h) for h in taps])
+        self.filter_taps = np.asarray([t for h in taps for t in h], np.int16)
+        if not self.filtered and (self.link_filter != -1).any():
+            raise ValueError(f"a link names filter {int(self.link_filter[self.link_filter != -1][0])}, "
+                             "but the medium has no filters")
+        # a link's reach: how far back it reads -- its delay, plus its filter's taps - 1
+        named = (self.link_filter >= 0) & (self.link_filter < self.n_filters)
+        span = np.diff(self.filter_ptr)[self.link_filter[named]] - 1 if self.filtered else 0
+        reach = self.link_delay.astype(np.int64)
+        reach[named] += span
+        largest = int(reach.max(initial=0))
         self.max_delay = largest if max_delay is None else medium_delay(max_delay)
         if not 0 <= self.max_delay <= _native.LIVE_DELAY_MAX_HIST:
             raise ValueError("max_delay must lie in 0 ... 2^20 samples")
         if largest > self.max_delay:
-            raise ValueError(f"a link has a delay of {largest} samples, above max_delay = {self.max_delay}")
-        self.delayed = self.max_delay > 0 or bool(self.link_delay.any())
-        self.hist_len = medium_hist_len(self.max_delay) if self.delayed else 0
+            raise ValueError(f"a link has a reach (its delay plus its filter's taps - 1) of {largest} samples, "
+                             f"above max_delay = {self.max_delay}")
+        self.delayed = self.filtered or self.max_delay > 0 or bool(self.link_delay.any())
+        self.hist_len = medium_hist_len(max(self.max_delay, largest)) if self.delayed else 0
         self.history_bytes = 2 * self.n_src * self.hist_len
-        if self.delayed:
+        if self.filtered:
+            _native.check(_native.lib().afsk_live_mix_filtered_check(
+                _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
+                _i32_ptr(self.link_gain_q15) if self.n_links else None,
+                _i32_ptr(self.link_delay) if self.n_links else None,
+                _i32_ptr(self.link_filter) if self.n_links else None, self.n_out, self.n_src, self.n_links,
+                self.hist_len, _i32_ptr(self.filter_ptr), self.filter_taps.ctypes.data_as(_native._i16p),
+                self.n_filters, int(self.filter_taps.size)))
+        elif self.delayed:
             _native.check(_native.lib().afsk_live_mix_delayed_check(
                 _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
                 _i32_ptr(self.link_gain_q15) if self.n_links else None,
@@ -1895,13 +2003,17 @@ class LiveMedium:
         self.d_link_delay = up(self.link_delay) if self.delayed else None
         self.d_history = torch.zeros((self.n_src, self.hist_len), dtype=torch.int16, device=self.device) \
             if self.delayed else None
+        self.d_link_filter = up(self.link_filter) if self.filtered else None
+        self.d_filter_ptr = up(self.filter_ptr) if self.filtered else None
+        self.d_filter_taps = up(self.filter_taps) if self.filtered else None
 
     @classmethod
-    def from_matrix(cls, gain, n_channels: int, extra=(), delay=None, **kw) -> "LiveMedium":
-        """The medium of ``medium_matrix_links(gain, n_channels, extra, delay)``: ``gain`` [n_listeners, n_stations] per
-        station, expanded over the stations' ``n_channels`` channels; ``delay`` one value or a matrix shaped like ``gain``
-        plus the extra groups; keywords as the constructor's."""
-        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra, delay)
+    def from_matrix(cls, gain, n_channels: int, extra=(), delay=None, filter=None, **kw) -> "LiveMedium":
+        """The medium of ``medium_matrix_links(gain, n_channels, extra, delay, filter)``: ``gain`` [n_listeners,
+        n_stations] per station, expanded over the stations' ``n_channels`` channels; ``delay`` one value or a matrix
+        shaped like ``gain`` plus the extra groups; ``filter`` one index into ``filters=`` or a matrix shaped like
+        ``delay``'s; keywords as the constructor's."""
+        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra, delay, filter)
         return cls(n_src, n_out, links, **kw)
 
     @property
@@ -1986,6 +2098,20 @@ class LiveMedium:
                 batch._order_after_current(stream, dev)
             if lens_up and stream is not None:
                 lens.record_stream(stream)
+            if self.filtered:
+                _native.check(_native.lib().afsk_live_mix_filtered(
+                    src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,
+                    None if lens is None else lens.data_ptr(), self.d_row_ptr.data_ptr(),
+                    self.d_link_src.data_ptr() if self.n_links else None,
+                    self.d_link_gain_q15.data_ptr() if self.n_links else None,
+                    self.d_link_delay.data_ptr() if self.n_links else None,
+                    self.d_link_filter.data_ptr() if self.n_links else None, self.n_links,
+                    out.data_ptr(), int(out.stride(0)), self.n_out, T,
+                    None if self.d_noise_scale_q24 is None else self.d_noise_scale_q24.data_ptr(), self.seed,
+                    self.noise_idx_base, self.d_pos.data_ptr(), self.d_history.data_ptr() if self.n_src else None,
+                    self.hist_len, self.d_filter_ptr.data_ptr(), self.d_filter_taps.data_ptr(), self.n_filters,
+                    int(self.filter_taps.size), batch._stream_ptr(stream, dev)))
+                return out[:, :T]
             if self.delayed:
                 _native.check(_native.lib().afsk_live_mix_delayed(
                     src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,

@@ -1306,8 +1306,8 @@ extern int afsk_live_push_auto_muted(afsk_live *live, const int16_t *chunk, int6
  *                       start at 0, falls, or does not end at n_links; a row with more than 32768 links; a source
  *                       outside 0 ... n_src - 1; a gain outside -65535 ... 65535; a negative count or a NULL array
  *                       (the link arrays may be NULL when n_links is 0).
- * Not part of the rule: filters or fading, more than one source matrix per call, a length per output row.  (A delay
- * per link: afsk_live_mix_delayed, below.)
+ * Not part of the rule: fading, more than one source matrix per call, a length per output row.  (A delay per link:
+ * afsk_live_mix_delayed, a filter per link: afsk_live_mix_filtered, both below.)
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_MIX_SIGNATURES.)
  */
 extern int afsk_live_mix(const int16_t *src, int64_t src_row_stride, int32_t n_src, const int32_t *d_src_lens_or_null,
@@ -1360,8 +1360,8 @@ extern int afsk_live_mix_check(const int32_t *h_row_ptr, const int32_t *h_link_s
  *                          AFSK_E_INVALID_ARG for a hist_len as above, a NULL h_link_delay when n_links > 0 or a delay
  *                          outside 0 ... hist_len.
  * Not part of the rule: fractional-sample delays, delays that change while the medium runs (the table is the caller's,
- * but the history holds no more than hist_len samples), filters or fading, clearing the history of single rows, a length
- * per output row, more than one source matrix per call.
+ * but the history holds no more than hist_len samples), fading (a filter per link: afsk_live_mix_filtered, below),
+ * clearing the history of single rows, a length per output row, more than one source matrix per call.
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_DELAY_SIGNATURES.)
  */
 extern int afsk_live_mix_delayed(const int16_t *src, int64_t src_row_stride, int32_t n_src,
@@ -1373,6 +1373,65 @@ extern int afsk_live_mix_delayed(const int16_t *src, int64_t src_row_stride, int
 extern int afsk_live_mix_delayed_check(const int32_t *h_row_ptr, const int32_t *h_link_src,
                                        const int32_t *h_link_gain_q15, const int32_t *h_link_delay, int32_t n_out,
                                        int32_t n_src, int32_t n_links, int32_t hist_len);
+
+/*
+ * The filtered live medium (added after ABI version 2; the version is unchanged): afsk_live_mix_delayed with an FIR
+ * filter in Q14 taps per link -- the band limit of a radio audio path, a telephone line or a speaker into a microphone,
+ * multipath on one link as several taps, pre- and de-emphasis.  All of it is integer and sample-exact.
+ *
+ * The filter table, on the DEVICE and owned by the caller, is n_filters filters stored as CSR:
+ *   filter_ptr   int32 [n_filters + 1]: filter f has K_f = filter_ptr[f + 1] - filter_ptr[f] taps, 1 <= K_f <= 256.
+ *   filter_taps  int16 [n_taps], Q14: unity is 16384, a tap lies in -32768 ... 32767; for every filter the sum of |h|
+ *                is at most 65535 (an L1 gain below 4), so that sum |h| * 32768 < 2^31.
+ *   link_filter  int32 [n_links]: the link's filter, -1 for none.
+ * pos, the history and X_s(t) are afsk_live_mix_delayed's, unchanged.
+ *
+ *  afsk_live_mix_filtered   afsk_live_mix_delayed's arguments plus d_link_filter (behind d_link_delay) and
+ *                          d_filter_ptr, d_filter_taps, n_filters and n_taps (behind hist_len).  For a link k with
+ *                          filter f = link_filter[k] >= 0, taps h = filter_taps + filter_ptr[f] and K = K_f:
+ *                            d_k        = clamp(link_delay[k], 0, hist_len - (K - 1))
+ *                            v_k(j)     = sum_{i = 0 .. K - 1} h[i] * X_{link_src[k]}(pos + j - d_k - i)     (int32, exact)
+ *                            f_k(j)     = clamp(v_k(j) >> 14, -32768, 32767)          (arithmetic shift: floor)
+ *                            term_k(j)  = (g_k * f_k(j)) >> 15
+ *                          A link with link_filter[k] == -1 contributes afsk_live_mix_delayed's term, bit for bit.
+ *                          The row sum, the clip, the noise, the position and the history ring are that entry's.  The
+ *                          reach of a filtered link is d + K - 1 and must not exceed hist_len.  So the identity filter
+ *                          {16384} on every link gives afsk_live_mix_delayed's output bit for bit, noise included; n
+ *                          zero taps in front of {16384} on a link at delay d equal that link unfiltered at delay
+ *                          d + n; and two mixes of T equal one of 2 T, for any T against hist_len and against K.
+ *                          Device clamps, applied before anything is read through an entry: afsk_live_mix_delayed's;
+ *                          a link_filter below -1 or >= n_filters makes the link silent; filter_ptr entries are clamped
+ *                          into [0, n_taps] and the second not below the first; K to 0 ... min(256, hist_len + 1), and
+ *                          K = 0 is silent; the delay as written above.  Taps are values, not addresses: a table whose
+ *                          sum of |h| exceeds 65535 (afsk_live_mix_filtered_check refuses it) may wrap v_k in 32 bits
+ *                          -- that result is not defined here -- and is memory-safe all the same.
+ *                          AFSK_E_INVALID_ARG: everything afsk_live_mix_delayed refuses; a negative n_filters or
+ *                          n_taps; a NULL d_filter_ptr; a NULL d_filter_taps when n_taps > 0; a NULL d_link_filter
+ *                          when n_links > 0.  n_samples == 0 or n_out == 0 launches nothing.  Otherwise three launches
+ *                          (live_mix_fir_kernel, live_mix_history_kernel, live_mix_advance_kernel), no allocation, no
+ *                          host read: capturable.
+ *  afsk_live_mix_filtered_check  host-only (no device needed), HOST arrays: afsk_live_mix_delayed_check's rules, and
+ *                          AFSK_E_INVALID_ARG, naming the filter or the link, for a filter_ptr that does not start at
+ *                          0, or does not rise to n_taps; a filter with K outside 1 ... 256 or a sum of |h| above
+ *                          65535; a link_filter outside -1 ... n_filters - 1; a filtered link whose reach exceeds
+ *                          hist_len; a NULL array (h_filter_taps may be NULL when n_taps is 0).
+ * Not part of the rule: taps that change while the medium runs (fading), IIR sections, fractional-sample delays, a
+ * filter per output row, filters longer than 256 taps.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_FIR_SIGNATURES.)
+ */
+extern int afsk_live_mix_filtered(const int16_t *src, int64_t src_row_stride, int32_t n_src,
+                                  const int32_t *d_src_lens_or_null, const int32_t *d_row_ptr, const int32_t *d_link_src,
+                                  const int32_t *d_link_gain_q15, const int32_t *d_link_delay,
+                                  const int32_t *d_link_filter, int32_t n_links, int16_t *out, int64_t out_row_stride,
+                                  int32_t n_out, int32_t n_samples, const int32_t *d_noise_scale_q24_or_null,
+                                  uint32_t noise_seed, uint32_t noise_idx_base, int64_t *d_pos, int16_t *d_history,
+                                  int32_t hist_len, const int32_t *d_filter_ptr, const int16_t *d_filter_taps,
+                                  int32_t n_filters, int32_t n_taps, void *hip_stream);
+extern int afsk_live_mix_filtered_check(const int32_t *h_row_ptr, const int32_t *h_link_src,
+                                        const int32_t *h_link_gain_q15, const int32_t *h_link_delay,
+                                        const int32_t *h_link_filter, int32_t n_out, int32_t n_src, int32_t n_links,
+                                        int32_t hist_len, const int32_t *h_filter_ptr, const int16_t *h_filter_taps,
+                                        int32_t n_filters, int32_t n_taps);
 
 /*
  * The duplicate filter (added after ABI version 2; the version is unchanged): the list every digipeater keeps so that
