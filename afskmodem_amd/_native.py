@@ -302,6 +302,19 @@ LIVE_FIR_SIGNATURES = {
 }
 LIVE_FIR_MAX_TAPS, LIVE_FIR_MAX_L1, LIVE_FIR_UNITY = 256, 65535, 16384
 
+# The faded live medium (afsk_live_mix_faded, afsk_live_mix_faded_check), likewise: the filtered entry's arguments with
+# the DEVICE fade tables (link_fade, link_fade_offset, fade_ptr, fade_shift, fade_knots, n_fades, n_knots) behind
+# n_taps; the check takes h_link_fade behind h_link_filter and (fade_ptr, fade_shift, n_fades, n_knots) at its end.
+_filtered_args = LIVE_FIR_SIGNATURES["afsk_live_mix_filtered"][1]
+_filtered_check_args = LIVE_FIR_SIGNATURES["afsk_live_mix_filtered_check"][1]
+LIVE_FADE_SIGNATURES = {
+    "afsk_live_mix_faded": (C.c_int, _filtered_args[:-1] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32]
+                            + _filtered_args[-1:]),
+    "afsk_live_mix_faded_check": (C.c_int, _filtered_check_args[:5] + [_i32p] + _filtered_check_args[5:]
+                                  + [_i32p, _i32p, C.c_int32, C.c_int32]),
+}
+LIVE_FADE_MAX_KNOTS, LIVE_FADE_MIN_SHIFT, LIVE_FADE_MAX_SHIFT, LIVE_FADE_MAX_GAIN = 65536, 3, 15, 65535
+
 # The duplicate filter (afsk_live_dedup_*, afsk_live_tx_submit_events_kept), likewise.
 LIVE_DEDUP_SIGNATURES = {
     "afsk_live_dedup_layout": (C.c_int, [C.c_int32, C.c_int32, _i64p]),
@@ -343,7 +356,7 @@ def lib() -> C.CDLL:
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
                                   *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items(),
                                   *LIVE_DEDUP_SIGNATURES.items(), *LIVE_DELAY_SIGNATURES.items(),
-                                  *LIVE_FIR_SIGNATURES.items()):
+                                  *LIVE_FIR_SIGNATURES.items(), *LIVE_FADE_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

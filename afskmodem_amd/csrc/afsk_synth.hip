@@ -337,3 +337,7 @@ hipError_t launch_noise(NoiseArgs a, int32_t max_len, hipStream_t stream) {
 // The filtered live medium (afsk_live_mix_filtered, afsk_live_mix_filtered_check) comes behind afsk_live_delay.hip,
 // whose MixDelayArgs, mix_add8 and history kernel it uses.
 #include "afsk_live_fir.hip"
+
+// The faded live medium (afsk_live_mix_faded, afsk_live_mix_faded_check) comes behind afsk_live_fir.hip, whose
+// MixFirArgs, staging helpers and dot2 it uses.
+#include "afsk_live_fade.hip"

@@ -1716,6 +1716,7 @@ class LiveTransmitter(batch._NativePlan):
 MEDIUM_UNITY = 32768                         # a link's unity gain (Q15)
 MEDIUM_MAX_GAIN = 65535                      # |gain_q15| of a link
 MEDIUM_MAX_SAMPLES = 1 << 20                 # columns of one mix
+MEDIUM_FADE_SPREAD = 0x9E3779B1              # from_matrix(fade_offset="spread"): link k's offset is k times this, mod 2^32
 
 
 def medium_gain_q15(gain) -> int:
@@ -1843,7 +1844,103 @@ def fir_design(n_taps: int, low_hz: float = 0, high_hz: float | None = None) -> 
     return medium_filter_q14([float(v) for v in h * np.hamming(K)])
 
 
-def medium_matrix_links(gain, n_channels: int, extra=(), delay=None, filter=None) -> tuple[int, int, list]:
+def _pow2_in(n: int, lo: int, hi: int) -> bool:
+    return lo <= n <= hi and n & (n - 1) == 0
+
+
+def medium_fade_period(period) -> int:
+    """A fade track's samples per knot: an int is samples, a float seconds at 48000 samples/s; a power of two in
+    8 ... 32768."""
+    n = medium_delay(period)
+    if not _pow2_in(n, 1 << _native.LIVE_FADE_MIN_SHIFT, 1 << _native.LIVE_FADE_MAX_SHIFT):
+        raise ValueError(f"a fade track's period must be a power of two in 8 ... 32768 samples, not {n}")
+    return n
+
+
+def medium_fade_q15(knots, period) -> tuple[list[int], int]:
+    """One fade track as the C entry takes it, ``(knots, shift)``: a power of two of 1 ... 65536 knots, an int is Q15
+    already (unity 32768), a float is ``round(knot * 32768)``, each inside 0 ... 65535; ``shift`` is log2 of
+    ``medium_fade_period(period)``."""
+    out = []
+    for v in knots:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("a knot is an int (Q15) or a float")
+        if isinstance(v, (float, np.floating)):
+            if not np.isfinite(v):
+                raise ValueError("a knot must be finite")
+            v = round(float(v) * MEDIUM_UNITY)
+        out.append(int(v))
+    if not _pow2_in(len(out), 1, _native.LIVE_FADE_MAX_KNOTS):
+        raise ValueError(f"a fade track has a power of two of 1 ... {_native.LIVE_FADE_MAX_KNOTS} knots, not {len(out)}")
+    if min(out) < 0 or max(out) > _native.LIVE_FADE_MAX_GAIN:
+        raise ValueError("a knot must lie in 0 ... 65535 (Q15: 0 ... just below 2)")
+    return out, medium_fade_period(period).bit_length() - 1
+
+
+def medium_fade_offset(offset) -> int:
+    """A link's offset into its fade track in samples, mod 2^32: an int is samples, a float seconds at 48000
+    samples/s."""
+    return medium_delay(offset) % (1 << 32)
+
+
+def medium_fades(n_out: int, links) -> tuple[np.ndarray, np.ndarray]:
+    """``medium_filters``' sibling: ``(link_fade, link_fade_offset)`` -- the fade track (int32 ``[n_links]``, -1 for
+    none) and the offset into it in samples (uint32 ``[n_links]``), in ``link_src``'s order -- of links given as
+    ``(out, src, gain[, delay[, filter]])`` (no track), ``(out, src, gain, delay, filter, fade)`` or
+    ``(out, src, gain, delay, filter, fade, fade_offset)`` with ``fade`` an index, -1 or None.  The range
+    -1 ... n_fades - 1 is checked by ``afsk_live_mix_faded_check``."""
+    rows = [[] for _ in range(int(n_out))]
+    for link in links:
+        if not 3 <= len(link) <= 7:
+            raise ValueError("a link is (out, src, gain[, delay[, filter[, fade[, fade_offset]]]])")
+        o = int(link[0])
+        if not 0 <= o < n_out:
+            raise ValueError(f"a link names output row {o} outside 0 ... {n_out - 1}")
+        f = link[5] if len(link) >= 6 else None
+        if isinstance(f, (bool, np.bool_)) or not (f is None or isinstance(f, (int, np.integer))):
+            raise TypeError("a link's fade is an index, -1 or None")
+        rows[o].append((-1 if f is None else int(f), medium_fade_offset(link[6]) if len(link) == 7 else 0))
+    flat = [e for r in rows for e in r]
+    fade = np.clip(np.asarray([f for f, _ in flat], np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+    return fade, np.asarray([o for _, o in flat], np.uint32)
+
+
+def fade_design(n_knots: int, period, doppler_hz: float, k_factor=None, seed: int = 0) -> tuple[list[int], int]:
+    """A fading envelope as a fade track, ``(knots, period in samples)`` for ``LiveMedium(fades=)``: Rayleigh
+    (``k_factor`` None) or Rician (``k_factor``: the power of the line-of-sight path over the scattered power).  The
+    scattered part is a sum of sinusoids at the whole multiples ``k`` of ``f0 = 48000 / (n_knots * period)`` with
+    ``|k| f0 <= doppler_hz`` -- whole periods of the track, so the cyclic track has no seam -- with complex normal
+    amplitudes from ``numpy.random.default_rng(seed)`` weighted by the classic Doppler spectrum
+    ``(1 - (k / (k_max + 1/2))^2)^(-1/4)``; a Rician track adds ``sqrt(k_factor)`` times the scatter's RMS.  The sum is
+    scaled to unit mean power, its magnitude rounded to Q15 and clipped at 65535.  ``k_max`` must stay below
+    ``n_knots / 2`` (the knots must sample the fastest sinusoid).  Host numpy only."""
+    L, per = int(n_knots), medium_fade_period(period)
+    if not _pow2_in(L, 1, _native.LIVE_FADE_MAX_KNOTS):
+        raise ValueError(f"n_knots must be a power of two in 1 ... {_native.LIVE_FADE_MAX_KNOTS}")
+    fd = float(doppler_hz)
+    if not (np.isfinite(fd) and fd >= 0):
+        raise ValueError("doppler_hz must be finite and >= 0")
+    if k_factor is not None and not (np.isfinite(k_factor) and k_factor >= 0):
+        raise ValueError("k_factor must be None or finite and >= 0")
+    kmax = int(np.floor(fd * L * per / _native.SAMPLE_RATE))
+    if kmax > 0 and 2 * kmax >= L:
+        raise ValueError(f"doppler_hz = {fd} needs {2 * kmax + 1} knots per track period or more, the track has {L}")
+    k = np.arange(-kmax, kmax + 1)
+    amp = np.random.default_rng(int(seed)).standard_normal((2, k.size))
+    coef = (amp[0] + 1j * amp[1]) * (1 - (k / (kmax + 0.5)) ** 2) ** -0.25
+    bins = np.zeros(L, np.complex128)
+    bins[k % L] = coef
+    z = np.fft.ifft(bins) * L                                   # z[n] = sum_k coef_k exp(2 pi i k n / L)
+    z = z / np.sqrt(np.mean(np.abs(z) ** 2))
+    if k_factor is not None:
+        z = z + np.sqrt(float(k_factor))
+        z = z / np.sqrt(np.mean(np.abs(z) ** 2))
+    q = np.minimum(np.round(np.abs(z) * MEDIUM_UNITY), _native.LIVE_FADE_MAX_GAIN)
+    return [int(v) for v in q], per
+
+
+def medium_matrix_links(gain, n_channels: int, extra=(), delay=None, filter=None, fade=None,
+                        fade_offset=None) -> tuple[int, int, list]:
     """``(n_src, n_out, links)`` of a station-level gain matrix ``gain`` [n_listeners, n_stations] expanded over the
     ``n_channels`` channels every station has: output row ``l * P + c`` hears source row ``s * P + c`` at ``gain[l][s]``;
     a zero entry makes no link (a listener that station does not reach).  ``extra``: source rows behind the stations'
@@ -1852,7 +1949,11 @@ def medium_matrix_links(gain, n_channels: int, extra=(), delay=None, filter=None
     [n_listeners, n_stations + the extra groups] -- ints are samples, floats seconds -- and the links are
     ``(out, src, gain, delay in samples)``.  ``filter`` (None: no fifth entry): one filter index for every link, or a
     matrix shaped like ``delay``'s whose entries are an index, -1 or None; the links are then
-    ``(out, src, gain, delay in samples, filter or None)``."""
+    ``(out, src, gain, delay in samples, filter or None)``.  ``fade`` (None: no sixth entry): one fade track for every
+    link, or a matrix shaped like ``delay``'s of indices, -1 or None; ``fade_offset``: one offset (an int is samples, a
+    float seconds), such a matrix, or ``"spread"`` -- the link at CSR index k gets ``(k * 0x9E3779B1) mod 2^32``, so
+    that the channels of a station pair fade independently off one track.  The links are then
+    ``(out, src, gain, delay in samples, filter or None, fade or None, offset in samples)``."""
     g = np.asarray(gain)
     if g.ndim != 2 or g.size == 0:
         raise ValueError("gain must be an [n_listeners, n_stations] matrix")
@@ -1889,6 +1990,34 @@ def medium_matrix_links(gain, n_channels: int, extra=(), delay=None, filter=None
                 raise TypeError("a link's filter is an index, -1 or None")
             return None if v is None or v == -1 else int(v)
         links = [(*x[:3], x[3] if len(x) == 4 else 0, index(f[x[0] // P, x[1] // P])) for x in links]
+    if fade is None and fade_offset is not None:
+        raise ValueError("fade_offset needs fade")
+    if fade is not None:
+        def matrix(value, name):
+            try:
+                m = np.asarray(value, dtype=object)
+            except ValueError:
+                m = np.empty(0, dtype=object)                   # ragged rows
+            if m.ndim == 0:
+                m = np.full((n_l, n_s + len(extras)), m.item(), dtype=object)
+            if m.shape != (n_l, n_s + len(extras)):
+                raise ValueError(f"{name} must be one value or a [{n_l}, {n_s + len(extras)}] matrix (the extra groups included)")
+            return m
+
+        def track(v):
+            if isinstance(v, (bool, np.bool_)) or not (v is None or isinstance(v, (int, np.integer))):
+                raise TypeError("a link's fade is an index, -1 or None")
+            return None if v is None or v == -1 else int(v)
+        fm = matrix(fade, "fade")
+        if isinstance(fade_offset, str):
+            if fade_offset != "spread":
+                raise ValueError('fade_offset is one value, a matrix or "spread"')
+            offs = [(k * MEDIUM_FADE_SPREAD) % (1 << 32) for k in range(len(links))]   # (links are in CSR order)
+        else:
+            om = matrix(0 if fade_offset is None else fade_offset, "fade_offset")
+            offs = [medium_fade_offset(om[x[0] // P, x[1] // P]) for x in links]
+        links = [(*x[:3], x[3] if len(x) >= 4 else 0, x[4] if len(x) >= 5 else None, track(fm[x[0] // P, x[1] // P]), o)
+                 for x, o in zip(links, offs)]
     return (n_s + len(extras)) * P, n_l * P, links
 
 
@@ -1924,10 +2053,23 @@ class LiveMedium:
     ``fir_design`` makes band limits.  A link ``(out, src, gain, delay, filter)`` hears ``src`` through filter number
     ``filter`` (None: unfiltered): ``clamp((sum_i h[i] * x[t - delay - i]) >> 14)`` takes the sample's place.  A medium
     with filters is ``filtered`` and also ``delayed``; a filtered link reaches ``delay + taps - 1`` samples back, and
-    ``hist_len`` covers the largest reach.  A medium without filters allocates and launches exactly what it did."""
+    ``hist_len`` covers the largest reach.  A medium without filters allocates and launches exactly what it did.
+
+    ``fades`` (``afsk_live_mix_faded``): a sequence of fade tracks ``(knots, period)`` -- a power of
+    two of 1 ... 65536 knots, an int is a Q15 gain (unity 32768, 0 ... 65535), a float ``round(knot * 32768)``;
+    ``period`` the samples per knot (an int) or seconds (a float), a power of two in 8 ... 32768 samples; ``fade_design``
+    makes Rayleigh and Rician tracks.  A link ``(out, src, gain, delay, filter, fade)`` or ``(..., fade, fade_offset)``
+    hears ``src`` through the cyclic track ``fade`` (None or -1: none), read at the listener's time plus ``fade_offset``
+    (an int is samples, mod 2^32; a float seconds) and interpolated linearly between knots: with envelope ``e`` the
+    link's sample ``x`` becomes ``clamp((e * x) >> 15)`` before the gain.  The same source on two links at two delays
+    and two offsets of one track is the two-ray channel.  A medium with fades is ``faded`` and also ``delayed``
+    (``hist_len`` at least 8); the envelope is a function of the position and the tables alone, so ``reset``, ``state``,
+    ``load_state`` and graph capture are unchanged.  ``d_fade_knots`` (uint16) is read when the kernels run: it may be
+    rewritten in place between mixes, by a scripted event or a track that is updated live.  A medium without fades
+    allocates and launches exactly what it did."""
 
     def __init__(self, n_src: int, n_out: int, links, device=None, noise_scale_q24=None, seed: int = 0,
-                 noise_idx_base: int = 0, max_delay=None, filters=None):
+                 noise_idx_base: int = 0, max_delay=None, filters=None, fades=None):
         torch = batch._torch()
         self.n_src, self.n_out = int(n_src), int(n_out)
         if self.n_src < 0 or self.n_out < 0:
@@ -1938,7 +2080,8 @@ class LiveMedium:
         links = list(links)
         self.row_ptr, self.link_src, self.link_gain_q15 = medium_csr(self.n_out, links)
         self.link_delay = medium_delays(self.n_out, [x[:4] for x in links])
-        self.link_filter = medium_filters(self.n_out, links)
+        self.link_filter = medium_filters(self.n_out, [x[:5] for x in links])
+        self.link_fade, self.link_fade_offset = medium_fades(self.n_out, links)
         self.n_links = int(self.link_src.size)
         taps = [medium_filter_q14(h) for h in (() if filters is None else filters)]
         self.n_filters = len(taps)
@@ -1949,6 +2092,16 @@ class LiveMedium:
         if not self.filtered and (self.link_filter != -1).any():
             raise ValueError(f"a link names filter {int(self.link_filter[self.link_filter != -1][0])}, "
                              "but the medium has no filters")
+        tracks = [medium_fade_q15(*f) for f in (() if fades is None else fades)]
+        self.n_fades = len(tracks)
+        self.faded = self.n_fades > 0
+        self.fade_ptr = np.zeros(self.n_fades + 1, np.int32)
+        self.fade_ptr[1:] = np.cumsum([len(kn) for kn, _ in tracks])
+        self.fade_shift = np.asarray([p for _, p in tracks], np.int32)
+        self.fade_knots = np.asarray([v for kn, _ in tracks for v in kn], np.uint16)
+        if not self.faded and (self.link_fade != -1).any():
+            raise ValueError(f"a link names fade track {int(self.link_fade[self.link_fade != -1][0])}, "
+                             "but the medium has no fades")
         # a link's reach: how far back it reads -- its delay, plus its filter's taps - 1
         named = (self.link_filter >= 0) & (self.link_filter < self.n_filters)
         span = np.diff(self.filter_ptr)[self.link_filter[named]] - 1 if self.filtered else 0
@@ -1961,10 +2114,20 @@ class LiveMedium:
         if largest > self.max_delay:
             raise ValueError(f"a link has a reach (its delay plus its filter's taps - 1) of {largest} samples, "
                              f"above max_delay = {self.max_delay}")
-        self.delayed = self.filtered or self.max_delay > 0 or bool(self.link_delay.any())
+        self.delayed = self.filtered or self.faded or self.max_delay > 0 or bool(self.link_delay.any())
         self.hist_len = medium_hist_len(max(self.max_delay, largest)) if self.delayed else 0
         self.history_bytes = 2 * self.n_src * self.hist_len
-        if self.filtered:
+        if self.faded:
+            _native.check(_native.lib().afsk_live_mix_faded_check(
+                _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
+                _i32_ptr(self.link_gain_q15) if self.n_links else None,
+                _i32_ptr(self.link_delay) if self.n_links else None,
+                _i32_ptr(self.link_filter) if self.n_links else None,
+                _i32_ptr(self.link_fade) if self.n_links else None, self.n_out, self.n_src, self.n_links,
+                self.hist_len, _i32_ptr(self.filter_ptr), self.filter_taps.ctypes.data_as(_native._i16p),
+                self.n_filters, int(self.filter_taps.size), _i32_ptr(self.fade_ptr), _i32_ptr(self.fade_shift),
+                self.n_fades, int(self.fade_knots.size)))
+        elif self.filtered:
             _native.check(_native.lib().afsk_live_mix_filtered_check(
                 _i32_ptr(self.row_ptr), _i32_ptr(self.link_src) if self.n_links else None,
                 _i32_ptr(self.link_gain_q15) if self.n_links else None,
@@ -2003,17 +2166,24 @@ class LiveMedium:
         self.d_link_delay = up(self.link_delay) if self.delayed else None
         self.d_history = torch.zeros((self.n_src, self.hist_len), dtype=torch.int16, device=self.device) \
             if self.delayed else None
-        self.d_link_filter = up(self.link_filter) if self.filtered else None
-        self.d_filter_ptr = up(self.filter_ptr) if self.filtered else None
-        self.d_filter_taps = up(self.filter_taps) if self.filtered else None
+        self.d_link_filter = up(self.link_filter) if self.filtered or self.faded else None
+        self.d_filter_ptr = up(self.filter_ptr) if self.filtered or self.faded else None
+        self.d_filter_taps = up(self.filter_taps) if self.filtered or self.faded else None
+        self.d_link_fade = up(self.link_fade) if self.faded else None
+        self.d_link_fade_offset = up(self.link_fade_offset) if self.faded else None
+        self.d_fade_ptr = up(self.fade_ptr) if self.faded else None
+        self.d_fade_shift = up(self.fade_shift) if self.faded else None
+        self.d_fade_knots = up(self.fade_knots) if self.faded else None    # (read by every mix: may be rewritten between mixes)
 
     @classmethod
-    def from_matrix(cls, gain, n_channels: int, extra=(), delay=None, filter=None, **kw) -> "LiveMedium":
+    def from_matrix(cls, gain, n_channels: int, extra=(), delay=None, filter=None, fade=None, fade_offset=None,
+                    **kw) -> "LiveMedium":
         """The medium of ``medium_matrix_links(gain, n_channels, extra, delay, filter)``: ``gain`` [n_listeners,
         n_stations] per station, expanded over the stations' ``n_channels`` channels; ``delay`` one value or a matrix
         shaped like ``gain`` plus the extra groups; ``filter`` one index into ``filters=`` or a matrix shaped like
-        ``delay``'s; keywords as the constructor's."""
-        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra, delay, filter)
+        ``delay``'s; ``fade`` one index into ``fades=`` or such a matrix, ``fade_offset`` one offset, such a matrix or
+        ``"spread"`` (every link its own offset into the track); keywords as the constructor's."""
+        n_src, n_out, links = medium_matrix_links(gain, n_channels, extra, delay, filter, fade, fade_offset)
         return cls(n_src, n_out, links, **kw)
 
     @property
@@ -2098,6 +2268,24 @@ class LiveMedium:
                 batch._order_after_current(stream, dev)
             if lens_up and stream is not None:
                 lens.record_stream(stream)
+            if self.faded:
+                _native.check(_native.lib().afsk_live_mix_faded(
+                    src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,
+                    None if lens is None else lens.data_ptr(), self.d_row_ptr.data_ptr(),
+                    self.d_link_src.data_ptr() if self.n_links else None,
+                    self.d_link_gain_q15.data_ptr() if self.n_links else None,
+                    self.d_link_delay.data_ptr() if self.n_links else None,
+                    self.d_link_filter.data_ptr() if self.n_links else None, self.n_links,
+                    out.data_ptr(), int(out.stride(0)), self.n_out, T,
+                    None if self.d_noise_scale_q24 is None else self.d_noise_scale_q24.data_ptr(), self.seed,
+                    self.noise_idx_base, self.d_pos.data_ptr(), self.d_history.data_ptr() if self.n_src else None,
+                    self.hist_len, self.d_filter_ptr.data_ptr(),
+                    self.d_filter_taps.data_ptr() if self.filter_taps.size else None, self.n_filters,
+                    int(self.filter_taps.size), self.d_link_fade.data_ptr() if self.n_links else None,
+                    self.d_link_fade_offset.data_ptr() if self.n_links else None, self.d_fade_ptr.data_ptr(),
+                    self.d_fade_shift.data_ptr(), self.d_fade_knots.data_ptr(), self.n_fades,
+                    int(self.fade_knots.size), batch._stream_ptr(stream, dev)))
+                return out[:, :T]
             if self.filtered:
                 _native.check(_native.lib().afsk_live_mix_filtered(
                     src.data_ptr() if self.n_src else None, int(src.stride(0)), self.n_src,

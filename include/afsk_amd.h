@@ -1360,8 +1360,9 @@ extern int afsk_live_mix_check(const int32_t *h_row_ptr, const int32_t *h_link_s
  *                          AFSK_E_INVALID_ARG for a hist_len as above, a NULL h_link_delay when n_links > 0 or a delay
  *                          outside 0 ... hist_len.
  * Not part of the rule: fractional-sample delays, delays that change while the medium runs (the table is the caller's,
- * but the history holds no more than hist_len samples), fading (a filter per link: afsk_live_mix_filtered, below),
- * clearing the history of single rows, a length per output row, more than one source matrix per call.
+ * but the history holds no more than hist_len samples; a filter per link: afsk_live_mix_filtered, fading:
+ * afsk_live_mix_faded, both below), clearing the history of single rows, a length per output row, more than one source
+ * matrix per call.
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_DELAY_SIGNATURES.)
  */
 extern int afsk_live_mix_delayed(const int16_t *src, int64_t src_row_stride, int32_t n_src,
@@ -1415,8 +1416,8 @@ extern int afsk_live_mix_delayed_check(const int32_t *h_row_ptr, const int32_t *
  *                          0, or does not rise to n_taps; a filter with K outside 1 ... 256 or a sum of |h| above
  *                          65535; a link_filter outside -1 ... n_filters - 1; a filtered link whose reach exceeds
  *                          hist_len; a NULL array (h_filter_taps may be NULL when n_taps is 0).
- * Not part of the rule: taps that change while the medium runs (fading), IIR sections, fractional-sample delays, a
- * filter per output row, filters longer than 256 taps.
+ * Not part of the rule: taps that change while the medium runs (a gain that does: afsk_live_mix_faded, below), IIR
+ * sections, fractional-sample delays, a filter per output row, filters longer than 256 taps.
  * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_FIR_SIGNATURES.)
  */
 extern int afsk_live_mix_filtered(const int16_t *src, int64_t src_row_stride, int32_t n_src,
@@ -1432,6 +1433,82 @@ extern int afsk_live_mix_filtered_check(const int32_t *h_row_ptr, const int32_t 
                                         const int32_t *h_link_filter, int32_t n_out, int32_t n_src, int32_t n_links,
                                         int32_t hist_len, const int32_t *h_filter_ptr, const int16_t *h_filter_taps,
                                         int32_t n_filters, int32_t n_taps);
+
+/*
+ * The faded live medium (added after ABI version 2; the version is unchanged): afsk_live_mix_filtered with a gain per
+ * link that moves along a cyclic Q15 track while the medium runs -- a signal that sinks under a receiver's gate for
+ * half a second, a station in reach on one tick and hidden on the next, the two delayed copies of a two-ray HF channel
+ * fading independently.  All of it is integer and sample-exact, and the envelope is a pure function of the position and
+ * the tables: a faded medium has no state beyond the delayed medium's.
+ *
+ * The fade table, on the DEVICE and owned by the caller, is n_fades tracks stored as CSR:
+ *   fade_ptr     int32 [n_fades + 1]: track f has L_f = fade_ptr[f + 1] - fade_ptr[f] knots, a power of two in
+ *                1 ... 65536.
+ *   fade_shift   int32 [n_fades]: p_f in 3 ... 15; the track has 2^p_f samples per knot (8 ... 32768) and is cyclic
+ *                with period L_f * 2^p_f samples, which divides 2^32.
+ *   fade_knots   uint16 [n_knots], Q15 gains: 32768 is unity, 0 no signal, 65535 just under x 2.
+ *   link_fade    int32 [n_links]: the link's track, -1 for none.
+ *   link_fade_offset  uint32 [n_links]: where in its track the link is at medium time 0, in samples (any value).
+ * pos, the history, X_s(t), d_k, v_k and f_k are afsk_live_mix_filtered's, unchanged.
+ *
+ *  afsk_live_mix_faded     afsk_live_mix_filtered's arguments plus d_link_fade, d_link_fade_offset, d_fade_ptr,
+ *                          d_fade_shift, d_fade_knots, n_fades and n_knots (behind n_taps).  For a link k with track
+ *                          f = link_fade[k] >= 0, knots = fade_knots + fade_ptr[f], L = L_f and p = p_f, at column j
+ *                          (medium time pos + j, the LISTENER's time: not pos + j - d_k):
+ *                            u        = (uint32)(pos + j) + link_fade_offset[k]                    (mod 2^32)
+ *                            n        = (u >> p) & (L - 1);   m = (n + 1) & (L - 1);   q = u & (2^p - 1)
+ *                            e_k(j)   = knots[n] + (((int32)(knots[m] - knots[n]) * q) >> p)
+ *                                       (arithmetic shift: floor; |product| < 65536 * 2^15 = 2^31)
+ *                            x_k(j)   = X_{link_src[k]}(pos + j - d_k) without a filter, f_k(j) with one
+ *                            term_k(j) = (g_k * clamp((e_k(j) * x_k(j)) >> 15, -32768, 32767)) >> 15
+ *                          e_k lies between its two knots, so in 0 ... 65535, and e_k * x_k fits int32
+ *                          (65535 * 32768 < 2^31).  With e_k = 32768 the term is the filtered medium's exactly, so a
+ *                          unity track on every link gives afsk_live_mix_filtered's output bit for bit, noise included.
+ *                          A link with link_fade[k] == -1 contributes afsk_live_mix_filtered's term, bit for bit.  The
+ *                          row sum, the clip, the noise, the position and the history ring are that entry's.  Since
+ *                          L * 2^p divides 2^32 the envelope depends on the low 32 bits of pos alone and is continuous
+ *                          past 2^32 samples; since it depends on nothing but pos and the tables, two mixes of T
+ *                          equal one of 2 T, afsk_live_mix_delayed's state is the whole state, and a captured graph
+ *                          replays.  fade_knots is read when the kernels run: the caller may rewrite it between
+ *                          calls (a scripted event, a track updated live), in stream order.
+ *                          Device clamps, applied before anything is read through an entry: afsk_live_mix_filtered's;
+ *                          a link_fade below -1 or >= n_fades makes the link silent; fade_ptr entries are clamped into
+ *                          [0, n_knots] and the second not below the first; L is their difference rounded down to a
+ *                          power of two, at most 65536, and no knots make the link silent; the shift is clamped to
+ *                          3 ... 15.  Knots and offsets are values, not addresses.
+ *                          AFSK_E_INVALID_ARG: everything afsk_live_mix_filtered refuses; a negative n_fades or
+ *                          n_knots; a NULL d_fade_ptr; a NULL d_fade_shift when n_fades > 0; a NULL d_fade_knots when
+ *                          n_knots > 0; a NULL d_link_fade or d_link_fade_offset when n_links > 0.  n_samples == 0 or
+ *                          n_out == 0 launches nothing.  Otherwise three launches (live_mix_fade_kernel,
+ *                          live_mix_history_kernel, live_mix_advance_kernel), no allocation, no host read: capturable.
+ *  afsk_live_mix_faded_check  host-only (no device needed), HOST arrays: afsk_live_mix_filtered_check's rules
+ *                          (n_filters = 0 with filter_ptr = {0} is legal), and AFSK_E_INVALID_ARG, naming the track or
+ *                          the link, for a fade_ptr that does not start at 0, or does not rise to n_knots; a track
+ *                          whose L is not a power of two in 1 ... 65536 or whose shift is outside 3 ... 15; a
+ *                          link_fade outside -1 ... n_fades - 1; a NULL array (h_fade_shift may be NULL when n_fades
+ *                          is 0).  The knots and the offsets need no check: every value is legal.
+ * Not part of the rule: phase or complex fading, tracks whose length or period is no power of two, a track per output
+ * row, generating tracks on the device.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_FADE_SIGNATURES.)
+ */
+extern int afsk_live_mix_faded(const int16_t *src, int64_t src_row_stride, int32_t n_src,
+                               const int32_t *d_src_lens_or_null, const int32_t *d_row_ptr, const int32_t *d_link_src,
+                               const int32_t *d_link_gain_q15, const int32_t *d_link_delay,
+                               const int32_t *d_link_filter, int32_t n_links, int16_t *out, int64_t out_row_stride,
+                               int32_t n_out, int32_t n_samples, const int32_t *d_noise_scale_q24_or_null,
+                               uint32_t noise_seed, uint32_t noise_idx_base, int64_t *d_pos, int16_t *d_history,
+                               int32_t hist_len, const int32_t *d_filter_ptr, const int16_t *d_filter_taps,
+                               int32_t n_filters, int32_t n_taps, const int32_t *d_link_fade,
+                               const uint32_t *d_link_fade_offset, const int32_t *d_fade_ptr,
+                               const int32_t *d_fade_shift, const uint16_t *d_fade_knots, int32_t n_fades,
+                               int32_t n_knots, void *hip_stream);
+extern int afsk_live_mix_faded_check(const int32_t *h_row_ptr, const int32_t *h_link_src,
+                                     const int32_t *h_link_gain_q15, const int32_t *h_link_delay,
+                                     const int32_t *h_link_filter, const int32_t *h_link_fade, int32_t n_out,
+                                     int32_t n_src, int32_t n_links, int32_t hist_len, const int32_t *h_filter_ptr,
+                                     const int16_t *h_filter_taps, int32_t n_filters, int32_t n_taps,
+                                     const int32_t *h_fade_ptr, const int32_t *h_fade_shift, int32_t n_fades,
+                                     int32_t n_knots);
 
 /*
  * The duplicate filter (added after ABI version 2; the version is unchanged): the list every digipeater keeps so that
