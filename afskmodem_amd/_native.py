@@ -337,6 +337,25 @@ LIVE_DEDUP_MAX_DEPTH = 64
 LIVE_TX_DUPLICATE = 7                        # AFSK_LIVE_TX_DUPLICATE
 
 
+class LiveLevelParams(C.Structure):
+    """afsk_live_level_params: the level tracker's eight parameters, passed by value."""
+    _fields_ = [(name, C.c_int32) for name in ("start_q15", "end_q15", "floor_start_q8", "floor_end_q8", "min_start",
+                                               "min_end", "decay_shift", "rise_shift")]
+
+
+# The level tracker (afsk_live_create_stream_leveled, afsk_live_level_check, afsk_live_level, afsk_live_level_reset),
+# likewise.
+LIVE_LEVEL_SIGNATURES = {
+    # afsk_live_create_stream_auto's arguments, the HOST bit_frames (or NULL) behind n_channels
+    "afsk_live_create_stream_leveled": (C.c_int, [C.c_int32, _i32p, _i32p, C.c_int32, C.c_int32, _i32p, _i32p,
+                                                  C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "afsk_live_level_check": (C.c_int, [LiveLevelParams]),
+    "afsk_live_level": (C.c_int, [C.c_void_p, C.c_void_p, LiveLevelParams, C.c_void_p, C.c_int64, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afsk_live_level_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+}
+
+
 def lib() -> C.CDLL:
     """Load the HIP shared library, failing loudly when it was not built."""
     global _lib
@@ -356,7 +375,8 @@ def lib() -> C.CDLL:
                                   *LIVE_TX_RATED_SIGNATURES.items(), *LIVE_TX_HOLD_SIGNATURES.items(),
                                   *LIVE_CSMA_SIGNATURES.items(), *LIVE_MIX_SIGNATURES.items(),
                                   *LIVE_DEDUP_SIGNATURES.items(), *LIVE_DELAY_SIGNATURES.items(),
-                                  *LIVE_FIR_SIGNATURES.items(), *LIVE_FADE_SIGNATURES.items()):
+                                  *LIVE_FIR_SIGNATURES.items(), *LIVE_FADE_SIGNATURES.items(),
+                                  *LIVE_LEVEL_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -168,6 +168,9 @@ hipError_t launch_clear_i32(int32_t* out, int64_t n, hipStream_t stream) {
 // Every receiver's push (afsk_live_push / afsk_live_push_tap / afsk_live_push_ragged / afsk_live_push_auto: the one kernel
 // template over the sinks, its table of instantiations and the one host path), behind every sink.
 #include "afsk_live_push.hip"
+// The level tracker (afsk_live_create_stream_leveled / afsk_live_level: a noise floor and a peak per channel, and the
+// threshold pair the PER_CHANNEL cells of the push read, set from them ahead of every push), for the same reason.
+#include "afsk_live_level.hip"
 // The packed lists of a push (afsk_live_events_layout / afsk_live_pack: the slot outputs of a push compacted into a
 // count, records and payload bytes; afsk_live_segments_layout / afsk_live_pack_tap: likewise what the payload tap of a
 // progressive push handed out; one header, scan, layout and launch path under both), for the same reason.

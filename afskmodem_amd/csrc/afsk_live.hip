@@ -499,6 +499,7 @@ struct afsk_live {
     // amp_end int32 [n] behind it; a stored receiver of two or more squelch classes also the classes' slot lists
     // (o_list: int32 [n * slots]) and, with mixed rates, every slot's bit_frames (o_slot_bf: int32 [n * slots])
     bool per_channel = false;
+    bool leveled = false;               // afsk_live_create_stream_leveled: afsk_live_level may rewrite the pair arrays
     int64_t o_thr = 0, o_list = 0, o_slot_bf = 0;
     std::vector<afsk::SquelchClasses::Class> classes;     // (one class: today's demod launch, no list)
     ~afsk_live() {

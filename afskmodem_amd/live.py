@@ -44,6 +44,54 @@ DEFAULT_MAX_CHUNK_LEN = 8192
 DEFAULT_MAX_PAYLOAD_LEN = 256                       # the live transmitter's and the streaming receiver's default
 
 
+@dataclass(frozen=True)
+class LevelSpec:
+    """The level tracker's parameters (``LiveReceiver(..., level=)``, ``afsk_live_level``).  Per 2048-sample block of
+    amplitude A a channel's peak P rises to A at once and decays towards it by ``(P - A) >> decay_shift`` (rounded up);
+    its noise floor F, while no burst records, falls towards A by a quarter of the distance and rises by
+    ``(A - F) >> rise_shift``.  Ahead of every push the channel's pair becomes
+    ``start = min(65535, max(start_q15 * P' >> 15, floor_start_q8 * F >> 8, min_start))`` (P': the highest peak of the
+    push's blocks or the one before them) and ``end`` likewise -- unless a burst is recording, which keeps its pair.
+    The four ratios may be given as floats: ``round(x * 32768)`` for the Q15 pair (0.55 -> 18022), ``round(x * 256)`` for
+    the Q8 pair (2.0 -> 512)."""
+    start_q15: "int | float" = 18000
+    end_q15: "int | float" = 14000
+    floor_start_q8: "int | float" = 512
+    floor_end_q8: "int | float" = 384
+    min_start: int = 1024
+    min_end: int = 768
+    decay_shift: int = 2
+    rise_shift: int = 6
+
+    def __post_init__(self):
+        for name, one in (("start_q15", 32768), ("end_q15", 32768), ("floor_start_q8", 256), ("floor_end_q8", 256)):
+            v = getattr(self, name)
+            if isinstance(v, (float, np.floating)):
+                if not np.isfinite(v):
+                    raise ValueError(f"level: {name} must be finite, got {v!r}")
+                object.__setattr__(self, name, int(round(float(v) * one)))
+        for name in self.FIELDS:
+            v = getattr(self, name)
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"level: {name} must be an integer, got {v!r}")
+            object.__setattr__(self, name, int(v))
+        ordered = lambda lo, hi: 0 <= lo <= hi <= 65535  # noqa: E731
+        if not ordered(self.end_q15, self.start_q15):
+            raise ValueError("level: 0 <= end_q15 <= start_q15 <= 65535 must hold")
+        if not ordered(self.floor_end_q8, self.floor_start_q8):
+            raise ValueError("level: 0 <= floor_end_q8 <= floor_start_q8 <= 65535 must hold")
+        if not ordered(self.min_end, self.min_start):
+            raise ValueError("level: 0 <= min_end <= min_start <= 65535 must hold")
+        if not (0 <= self.decay_shift <= 15 and 0 <= self.rise_shift <= 15):
+            raise ValueError("level: decay_shift and rise_shift must lie in 0 ... 15")
+
+    FIELDS = ("start_q15", "end_q15", "floor_start_q8", "floor_end_q8", "min_start", "min_end", "decay_shift",
+              "rise_shift")
+
+    def native(self) -> "_native.LiveLevelParams":
+        return _native.LiveLevelParams(*(getattr(self, f) for f in self.FIELDS))
+
+
 def _per_channel(value, n_channels: int, name: str):
     """None for a scalar ``value``, else its entries as a list of length n_channels (ValueError otherwise)."""
     if np.ndim(value) == 0:
@@ -755,6 +803,15 @@ class LiveReceiver(batch._NativePlan):
     True, ``bit_frames`` None and ``channel_bit_frames`` all 0 on such a receiver; everything else -- ``progressive``,
     thresholds per channel, ragged pushes, ``events=``, ``segments=``, ``out=`` -- works as on the streaming receiver.
 
+    ``level=True`` or ``level=LevelSpec(...)`` (streaming only, ValueError otherwise; one threshold pair for all
+    channels) builds a LEVELED receiver (``afsk_live_create_stream_leveled``): every ``push`` / ``flush`` first runs the
+    level tracker (``afsk_live_level``, one launch on the same stream), which follows every channel's noise floor and
+    peak over the blocks the push is about to walk and sets the channel's threshold pair from them, so a channel at any
+    level opens its gate; a burst keeps the pair it opened with.  The thresholds given are the pair before the first
+    push and after ``reset``.  ``leveled`` is True, ``level_spec`` the parameters and ``level_state`` an int32
+    ``[n_channels, 4]`` device tensor at a fixed address -- rows ``(floor, peak, start, end)``.  A receiver without
+    ``level=`` allocates and launches exactly what it did.
+
     The receiver belongs to the device that was current (or ``device``); ``close()`` only after its pushes have
     completed."""
     _destroy = "afsk_live_destroy"
@@ -762,9 +819,22 @@ class LiveReceiver(batch._NativePlan):
     def __init__(self, n_channels: int, bit_frames, amp_start_threshold=18000, amp_end_threshold=14000,
                  max_burst_len: int | None = DEFAULT_MAX_BURST_LEN, max_chunk_len: int = DEFAULT_MAX_CHUNK_LEN,
                  device=None, max_payload_len: int = DEFAULT_MAX_PAYLOAD_LEN, progressive: bool = False,
-                 candidates=None, max_score: int | None = None):
+                 candidates=None, max_score: int | None = None, level=None):
         torch = batch._torch()
         self.n_channels = int(n_channels)
+        if level is None or level is False:
+            self.level_spec = None
+        elif level is True:
+            self.level_spec = LevelSpec()
+        elif isinstance(level, LevelSpec):
+            self.level_spec = level
+        else:
+            raise ValueError(f"level must be None, True or a LevelSpec, got {level!r}")
+        self.leveled = self.level_spec is not None
+        self.level_state = None
+        if self.leveled and max_burst_len is not None:
+            raise ValueError("level= needs the streaming receiver (max_burst_len=None): the stored receiver has no level "
+                             "tracker")
         self.auto = isinstance(bit_frames, str) and bit_frames == "auto"
         if self.auto:
             if max_burst_len is not None:
@@ -796,6 +866,9 @@ class LiveReceiver(batch._NativePlan):
                                                    batch.threshold_lt)
         one = lambda a: int(a[0]) if a.size and bool(np.all(a == a[0])) else None  # noqa: E731
         self.amp_start_threshold, self.amp_end_threshold = one(self.channel_amp_start), one(self.channel_amp_end)
+        if self.leveled and self.n_channels > 0 and (self.amp_start_threshold is None or self.amp_end_threshold is None):
+            raise ValueError("level= takes one threshold pair for all channels (the pair before the first push and "
+                             "after a reset): the tracker sets every channel's own")
         self.streaming = max_burst_len is None
         self.max_burst_len = None if self.streaming else int(max_burst_len)
         self.max_payload_len = int(max_payload_len) if self.streaming else None
@@ -822,7 +895,19 @@ class LiveReceiver(batch._NativePlan):
         nbytes = C.c_int64()
         with torch.cuda.device(self.device):
             # (one rate / one threshold pair in every entry: the C entries build the one-rate / one-pair receiver)
-            if self.auto:
+            if self.leveled:
+                cands = np.asarray(self.candidates if self.auto else [], np.int32)
+                _native.check(_native.lib().afsk_live_create_stream_leveled(
+                    self.n_channels, None if self.auto else _i32_ptr(self.channel_bit_frames),
+                    _i32_ptr(cands) if self.auto else None, int(cands.size),
+                    -1 if not self.auto or self.max_score is None else self.max_score,
+                    _i32_ptr(self.channel_amp_start), _i32_ptr(self.channel_amp_end), self.max_payload_len,
+                    self.max_chunk_len, int(self.progressive), C.byref(self._h)))
+                # rows (floor, peak, start, end): nothing known, the pair the receiver was given
+                self.level_state = torch.tensor([[-1, 0, self.amp_start_threshold, self.amp_end_threshold]],
+                                                dtype=torch.int32).repeat(self.n_channels, 1).to(self.device)
+                torch.cuda.current_stream(self.device).synchronize()     # (a push may run on any stream)
+            elif self.auto:
                 cands = np.asarray(self.candidates, np.int32)
                 _native.check(_native.lib().afsk_live_create_stream_auto(
                     self.n_channels, _i32_ptr(cands), int(cands.size), -1 if self.max_score is None else self.max_score,
@@ -848,7 +933,8 @@ class LiveReceiver(batch._NativePlan):
         """One channel per ``Receiver`` (channel c at ``receivers[c]``'s baud rate).  ``thresholds="shared"``: their
         thresholds must agree (ValueError otherwise) and are the receiver's one pair; ``"per_channel"``: channel c
         gets ``receivers[c]``'s pair.  ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples),
-        ``max_payload_len`` (bytes, with ``max_burst_len=None``), ``progressive`` (likewise) and ``device``."""
+        ``max_payload_len`` (bytes, with ``max_burst_len=None``), ``progressive`` and ``level`` (likewise; ``level``
+        with ``thresholds="shared"`` only) and ``device``."""
         receivers = list(receivers)
         if not receivers:
             raise ValueError("from_receivers needs at least one Receiver")
@@ -1083,6 +1169,11 @@ class LiveReceiver(batch._NativePlan):
                 t = out.tap
                 taps = (t.bytes.data_ptr(), t.n.data_ptr(), t.len.data_ptr(), t.open_start.data_ptr(),
                         t.open_nbytes.data_ptr())
+            if self.leveled:                         # the tracker sets the pairs this push gates with
+                _native.check(_native.lib().afsk_live_level(
+                    self.handle, self.level_state.data_ptr(), self.level_spec.native(), *head[1:],
+                    None if lens is None else lens.data_ptr(), None if ranges is None else ranges.data_ptr(),
+                    batch._stream_ptr(stream, dev)))
             if ranges is not None:
                 rates = (out.bit_frames.data_ptr(), out.rate_score.data_ptr()) if self.auto else ()
                 entry = _native.lib().afsk_live_push_auto_muted if self.auto else _native.lib().afsk_live_push_muted
@@ -1122,7 +1213,8 @@ class LiveReceiver(batch._NativePlan):
 
     def reset(self, mask=None, stream=None) -> None:
         """Drop the state of every channel (``mask`` None) or of the channels where ``mask`` ([n_channels] bool /
-        uint8, host or device) is true, without reporting anything; they start new streams."""
+        uint8, host or device) is true, without reporting anything; they start new streams.  A leveled receiver's
+        ``level_state`` rows of those channels go back to (-1, 0, the constructor's pair), and so do their thresholds."""
         torch = batch._torch()
         dev = self.device
         m = _device_mask(mask, self.n_channels, dev)
@@ -1133,6 +1225,10 @@ class LiveReceiver(batch._NativePlan):
                     m.record_stream(stream)
             _native.check(_native.lib().afsk_live_reset(self.handle, None if m is None else m.data_ptr(),
                                                         batch._stream_ptr(stream, dev)))
+            if self.leveled:
+                _native.check(_native.lib().afsk_live_level_reset(
+                    self.handle, self.level_state.data_ptr(), None if m is None else m.data_ptr(),
+                    self.amp_start_threshold, self.amp_end_threshold, batch._stream_ptr(stream, dev)))
 
     def busy(self, out=None, stream=None):
         """int32 ``[n_channels]`` CUDA tensor: 1 for every channel whose gate is recording a burst after the last

@@ -437,7 +437,9 @@ class Receiver:
         """A ``live.LiveReceiver`` of ``n_channels`` channels with this Receiver's baud rate and thresholds: the gate of
         ``receive`` (ref:299-319) fed chunk by chunk, every burst demodulated in the push that closes it.
         ``capacities``: ``max_burst_len`` / ``max_chunk_len`` (samples), ``device``, and for the streaming receiver
-        (``max_burst_len=None``) ``max_payload_len`` and ``progressive`` (payload bytes push by push)."""
+        (``max_burst_len=None``) ``max_payload_len``, ``progressive`` (payload bytes push by push) and ``level``
+        (True or a ``live.LevelSpec``: the thresholds follow every channel's own level, this Receiver's pair being the
+        one before the first push)."""
         from .live import LiveReceiver
         return LiveReceiver(n_channels, self.__bit_frames, self.__amp_start_threshold, self.__amp_end_threshold,
                             **capacities)

@@ -1622,6 +1622,63 @@ extern int afsk_live_tx_submit_events_kept(afsk_live_tx *tx, const void *events,
                                            int32_t *out_n_samples, void *hip_stream);
 
 /*
+ * The level tracker of the streaming live receivers: a noise floor F and a decaying peak P per channel, followed on the
+ * device block by block, and the channel's gate / squelch pair set from them ahead of every push -- so a channel at any
+ * level opens its gate without the caller knowing that level.  Integer and exact:
+ *   blocks   for channel c the whole 2048-sample blocks the push of the same arguments will walk: cl = pos & 2047 carried
+ *            samples, len = chunk_len or clamp(d_chunk_lens[c], 0, chunk_len), nblk = (cl + len) / 2048, block 0 of a push
+ *            with a carry = carry[0, cl) + chunk[0, 2048 - cl).  Nothing at or beyond column len is read.  A block's
+ *            amplitude A is the gate's: sum |x| >> 11.  A block with any column inside the channel's clamped mute range
+ *            (afsk_live_push_muted's clamp of d_mute[c]) is skipped: it is not loaded and updates nothing.
+ *   update   rec = (the channel's gate is recording when the push starts), pp = P; for every block that is not skipped
+ *              P  = A > P ? A : P - ((P - A + (1 << decay_shift) - 1) >> decay_shift)
+ *              pp = max(pp, P)
+ *              if (!rec)  F = F < 0 ? A : (A < F ? F - ((F - A + 3) >> 2) : F + ((A - F) >> rise_shift))
+ *   pair     F and P are stored; unless rec, with Fz = max(F, 0)
+ *              start = min(65535, max((start_q15 * pp) >> 15, (floor_start_q8 * Fz) >> 8, min_start))
+ *              end   = min(65535, max((end_q15   * pp) >> 15, (floor_end_q8   * Fz) >> 8, min_end))
+ *            go to the receiver's own pair of channel c and to the channel's state row.  While a burst records the pair
+ *            stays what it was when the burst opened.
+ *  afsk_live_create_stream_leveled  the streaming receiver of afsk_live_create_stream_thresholds (tap = 0) /
+ *                           afsk_live_create_stream_tap (tap = 1) with bit_frames_host_or_null [n_channels] and n_cand = 0
+ *                           (cand_bit_frames_host is then not read), or of afsk_live_create_stream_auto with n_cand > 0
+ *                           (bit_frames_host_or_null is then not read), with those entries' checks -- kept in the
+ *                           per-channel threshold layout even when all pairs agree, so that afsk_live_level can rewrite
+ *                           the pairs.  It is pushed with the entries its kind is pushed with.
+ *  afsk_live_level_check    host-only: AFSK_OK when 0 <= end_q15 <= start_q15 <= 65535, 0 <= floor_end_q8 <=
+ *                           floor_start_q8 <= 65535, 0 <= min_end <= min_start <= 65535 and both shifts lie in 0 ... 15.
+ *  afsk_live_level          d_state: DEVICE int32 [n_channels, 4], a row = (floor, peak, start, end), the caller's (rows
+ *                           start as (-1, 0, amp_start, amp_end): afsk_live_level_reset).  chunk, chunk_row_stride,
+ *                           chunk_len, d_chunk_lens_or_null, d_mute_or_null: what the push behind it is given.  ONE launch
+ *                           (live_level_kernel, a wave per channel), asynchronous on hip_stream, no allocation, no host
+ *                           read: capturable, and a graph of tracker + push is a linear chain.  chunk_len == 0: AFSK_OK,
+ *                           no launch.  AFSK_E_INVALID_ARG, nothing launched: a stored receiver, a receiver of another
+ *                           create entry, a NULL live, d_state or (chunk_len > 0) chunk, a negative size, chunk_len above
+ *                           the receiver's max_chunk_len, params that afsk_live_level_check refuses.
+ *  afsk_live_level_reset    rows of the channels where d_mask_or_null is non-zero (NULL: all) go back to (-1, 0,
+ *                           amp_start0, amp_end0), and so do those channels' entries of the receiver's pair.  One launch.
+ * Not part of the rule: the stored receiver, thresholds that move inside a burst, parameters per channel, scaling the
+ * samples.
+ * (Declared `extern int`: afskmodem_amd/_native.py binds them from a table of their own, LIVE_LEVEL_SIGNATURES.)
+ */
+typedef struct afsk_live_level_params {
+    int32_t start_q15, end_q15;             /* the pair as Q15 ratios of the peak (18000 / 14000: the reference's) */
+    int32_t floor_start_q8, floor_end_q8;   /* ... and as Q8 multiples of the noise floor (512 / 384)              */
+    int32_t min_start, min_end;             /* ... and their least values (1024 / 768)                             */
+    int32_t decay_shift, rise_shift;        /* the peak's decay and the floor's rise per block (2 / 6)             */
+} afsk_live_level_params;
+extern int afsk_live_create_stream_leveled(int32_t n_channels, const int32_t *bit_frames_host_or_null,
+                                           const int32_t *cand_bit_frames_host, int32_t n_cand, int32_t max_score,
+                                           const int32_t *amp_start_host, const int32_t *amp_end_host,
+                                           int32_t max_payload_len, int32_t max_chunk_len, int32_t tap, afsk_live **out);
+extern int afsk_live_level_check(afsk_live_level_params params);
+extern int afsk_live_level(afsk_live *live, int32_t *d_state, afsk_live_level_params params, const int16_t *chunk,
+                           int64_t chunk_row_stride, int32_t chunk_len, const int32_t *d_chunk_lens_or_null,
+                           const int32_t *d_mute_or_null, void *hip_stream);
+extern int afsk_live_level_reset(afsk_live *live, int32_t *d_state, const uint8_t *d_mask_or_null, int32_t amp_start0,
+                                 int32_t amp_end0, void *hip_stream);
+
+/*
  * Deterministic additive noise (build-owned test/benchmark input generator, no
  * reference counterpart): per sample an Irwin-Hall sum of 16 uniform u16 drawn
  * from a counter hash of (seed, stream_idx_base + s, sample index), centred,
